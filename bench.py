@@ -12,7 +12,7 @@ already resident in HBM.  N=1: the single-GPU path (dnagpu_count_kmers_unordered
   python bench.py --gpus N                       ONE process drives N GPUs through the C-ABI (dnagpu_multi_init +
                                                  dnagpu_count_multi_unordered: every rank cuts the super-k-mer records of
                                                  its own rows, owners pull their buckets' pieces over xGMI and count them
-                                                 while later pieces are in flight).  No torch.  This is the call a
+                                                 while later pieces are in flight).  No torch (but with --dump-outputs).  This is the call a
                                                  PostgreSQL backend makes (one backend process, nothing PARALLEL SAFE:
                                                  dna--1.0.sql:188-195).  On a box with fewer than N devices the ranks
                                                  share devices and the line says "rehearsal": true.
@@ -25,9 +25,17 @@ Rank 0 prints ONE JSON line.
 Besides the contract fields the line carries
   roofline      the dominant kernel of the step: algorithmic bytes / its device time (HIP events on
                 the library's stream) against the 8 TB/s HBM peak
+  job_roofline  SURVEY.md 8(d)'s two whole-job fractions (read_fraction, alg_fraction)
+and with --full (off by default: a plain run sets up, warms up, times the steps and prints the line) also
+  digest        one more count after the timed steps, digested on the device and compared with the CPU
+                oracle's digest of the same workload (tests/golden/config_digests.json); exit 3 on a mismatch
+  sorted_view_ms  --engine tree: what the ascending-key view of the histogram costs on the device
   cpu_baseline  the CPU oracle (faithful restatement of the reference's per-base loops + hash
                 aggregate) timed on this box's host cores on a bounded sample of the same stream
-  job_roofline  SURVEY.md 8(d)'s two whole-job fractions (read_fraction, alg_fraction)
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64, see dump_hists / dump_rows):
+the histogram's digest and a fixed sample of its groups (about 2^20, chosen by a hash of the key, ascending keys), or
+for config 5 a fixed sample of the matching rows.  The inputs are seeded: the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -40,6 +48,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 CPU_SAMPLE_BASES = 24_000_000  # bounded sample for the CPU baseline (about 10-20 s on one core)
+DUMP_SAMPLE_LOG2 = 20          # --dump-outputs: about 2^20 groups (or rows) of a larger result go to the files
 
 # BASELINE.json configs: synthetic packed words, word w = splitmix64(seed + w)
 CONFIGS = {
@@ -114,7 +123,12 @@ def main():
                     help="count configs: auto = dnagpu_count_kmers_unordered (GROUP BY semantics: group order "
                          "unspecified; super-k-mer partitioning for k >= 21 on long sequences), tree = "
                          "dnagpu_count_kmers (groups in ascending key order, MSD radix tree)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks and extra figures after the timed steps: the digest against the CPU oracle's, "
+                         "the sorted view's cost (--engine tree) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64; a fixed sample of a large result)")
     ap.add_argument("--launcher", choices=["one-process", "torchrun"], default="one-process",
                     help="--gpus N > 1 without WORLD_SIZE in the environment: one-process = this process drives all N GPUs "
                          "through the C-ABI (default); torchrun = spawn torch.distributed.run as a child, one process per GPU")
@@ -128,6 +142,8 @@ def main():
     args = ap.parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         if args.launcher == "torchrun":
+            if args.dump_outputs:
+                raise SystemExit("--dump-outputs: the single-process paths only (not --launcher torchrun)")
             raise SystemExit(spawn_torchrun(args.gpus))
         return main_one_process(args)
 
@@ -148,6 +164,8 @@ def main():
     is_filter = cfg["kind"] == "filter"
     if is_filter and world > 1:
         raise SystemExit("config 5 is a single-GPU workload (BASELINE.json)")
+    if args.dump_outputs and world > 1:
+        raise SystemExit("--dump-outputs: the single-process paths only (not one process per GPU)")
 
     import torch
     from __graft_entry__ import load_package
@@ -182,6 +200,7 @@ def main():
     matches = [0]
     extra = {}
     sorted_result = [True]
+    last = []                  # --dump-outputs: the last timed step's result, freed after it is written
 
     if is_filter:
         import ctypes as C
@@ -191,7 +210,7 @@ def main():
         kb = ctx.buffer_alloc(n_kmers * 8)
         pb = None if args.keys_only else ctx.buffer_alloc(n_kmers * 8)
 
-        def step():
+        def step(keep=False):
             matches[0] = ctx.count_matches_device(dna, k, flt, 0, n_kmers, C.c_void_p(kb), C.c_void_p(pb), n_kmers)
             for name, ms in ctx.last_phase_times():
                 phases_acc.setdefault(name, []).append(ms)
@@ -212,13 +231,16 @@ def main():
         def count_fn(dna_, k_):
             return ctx.count_kmers_batch(dna_, starts, k_) if args.table_host_starts else ctx.count_kmers_table(dna_, k_)
 
-        def step():
+        def step(keep=False):
             h = count_fn(dna, k)
             sorted_result[0] = h.is_sorted
             distinct[0] = h.distinct
             for name, ms in ctx.last_phase_times():
                 phases_acc.setdefault(name, []).append(ms)
-            h.free()
+            if keep:
+                last.append(h)
+            else:
+                h.free()
     elif world == 1:
         if args.genome_like:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -230,13 +252,16 @@ def main():
 
         count_fn = ctx.count_kmers if args.engine == "tree" else ctx.count_kmers_unordered
 
-        def step():
+        def step(keep=False):
             h = count_fn(dna, k)
             sorted_result[0] = h.is_sorted
             distinct[0] = h.distinct
             for name, ms in ctx.last_phase_times():
                 phases_acc.setdefault(name, []).append(ms)
-            h.free()
+            if keep:
+                last.append(h)
+            else:
+                h.free()
     else:
         import importlib
         if args.motif:
@@ -250,7 +275,7 @@ def main():
         extra["exchange"] = ("records: own rows -> super-k-mer records -> all-to-all by coarse bucket -> count" if use_records else
                              "sequence: all-gather of the packed chunks -> every rank counts the key range it owns")
 
-        def step():
+        def step(keep=False):
             if use_records:
                 h, state["chunk"] = sh.count_sharded_exchange_records(engine, seed, n_bases, k, rank, world, state["chunk"],
                                                                       parts=max(args.parts, 1))
@@ -271,10 +296,17 @@ def main():
     phases_acc.clear()
     sync_all()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        step(bool(args.dump_outputs) and i == args.steps - 1)
     sync_all()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        if is_filter:
+            dump_rows(ctx, local_rank, args.dump_outputs, kb, pb, matches[0], n_kmers)
+        else:
+            dump_hists([(h, local_rank) for h in last], args.dump_outputs, n_kmers)
+        for h in last:
+            h.free()
     if dist is not None:
         red_dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
@@ -287,7 +319,7 @@ def main():
     # ---- outside the timed region: one more count whose histogram is digested on the device and compared with the CPU
     # oracle's digest of the same workload (every rank's share summed: the histograms are disjoint)
     digest = None
-    if not is_filter:
+    if args.full and not is_filter:
         if world == 1:
             hv = count_fn(dna, k)
         elif use_records:
@@ -305,10 +337,11 @@ def main():
         digest = digest_check(args.config if not args.genome_like else 0, n_bases, k, seed, args.motif, mine, rows=n_kmers)
 
     if rank == 0 and world == 1 and not is_filter and not sorted_result[0]:
-        extra["sorted_view_ms"] = None
+        if args.full:
+            extra["sorted_view_ms"] = None
         extra["group_order"] = ("unspecified (bucket order of the super-k-mer engine; PostgreSQL's GROUP BY order is "
                                 "unspecified too, test.sql:95-104); --engine tree gives ascending keys")
-    elif rank == 0 and world == 1 and not is_filter:
+    elif args.full and rank == 0 and world == 1 and not is_filter:
         # outside the timed region: what the ascending-key view of the same histogram costs on the device
         # (dnagpu_hist_sorted_view: segment directory -> two dense uint64 arrays); groups are stored in
         # completion order, PostgreSQL's GROUP BY order is unspecified too (test.sql:95-104)
@@ -404,7 +437,7 @@ def main():
             line["exchange_transport"] = (f"{dist.get_backend()} " + ("all_to_all_single" if use_records and max(args.parts, 1) == 1 else
                                           ("batch_isend_irecv" if use_records else "all_gather")))
             line["rccl_ranks"] = world if dist.get_backend() == "nccl" else 0
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_filter(cfg, seed) if is_filter else cpu_baseline(k, seed)
         print(json.dumps(line), flush=True)
 
@@ -463,6 +496,9 @@ def main_one_process(args):
     global SK_RUN
     SK_RUN = (max(k - (15 if k >= 23 else 13 if k >= 21 else 12) + 1, 1) + 1) / 2.0
 
+    if args.dump_outputs:
+        # the dump reads the histograms through torch, whose HIP runtime has to come up before the library's (as in main())
+        import torch  # noqa: F401
     from __graft_entry__ import load_package
     pkg = load_package()
     n_dev = pkg.device_count()
@@ -492,7 +528,9 @@ def main_one_process(args):
     phases_acc, xacc = {}, {}
     distinct = [0]
 
-    def step():
+    last = []                                      # --dump-outputs: the last timed step's histograms
+
+    def step(keep=False):
         hs = count_fn(mdna, k)
         distinct[0] = sum(h.distinct for h in hs)
         per_step = {}                              # (the pipelined exchange counts an owner's buckets group by group: a phase
@@ -503,6 +541,9 @@ def main_one_process(args):
         if use_records:
             for name, v in multi.last_times().items():
                 xacc.setdefault(name, []).append(v)
+        if keep:
+            last.extend(hs)
+            return
         for h in hs:
             h.free()
 
@@ -512,20 +553,26 @@ def main_one_process(args):
     xacc.clear()
     sync_all()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        step(bool(args.dump_outputs) and i == args.steps - 1)
     sync_all()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_hists([(h, devices[r]) for r, h in enumerate(last)], args.dump_outputs, n_kmers)
+        for h in last:
+            h.free()
 
-    # outside the timed region: one more count, every rank's histogram digested on its device, the sums against the CPU
-    # oracle's digest of the same workload
-    hs = count_fn(mdna, k)
-    sums = [0, 0, 0, 0]
-    for h in hs:
-        for i, v in enumerate(h.summary()):
-            sums[i] = (sums[i] + int(v)) & 0xFFFFFFFFFFFFFFFF
-        h.free()
-    digest = digest_check(args.config, n_bases, k, seed, 0, sums)
+    # --full, outside the timed region: one more count, every rank's histogram digested on its device, the sums against
+    # the CPU oracle's digest of the same workload
+    digest = None
+    if args.full:
+        hs = count_fn(mdna, k)
+        sums = [0, 0, 0, 0]
+        for h in hs:
+            for i, v in enumerate(h.summary()):
+                sums[i] = (sums[i] + int(v)) & 0xFFFFFFFFFFFFFFFF
+            h.free()
+        digest = digest_check(args.config, n_bases, k, seed, 0, sums)
     exchange_transport = multi.exchange_transport
 
     ms_per_step = elapsed / args.steps * 1e3
@@ -582,11 +629,12 @@ def main_one_process(args):
     if rehearsal:
         line["rehearsal_note"] = (f"{W} ranks share {n_dev} device(s): the code path of the N-GPU run (chunk residency, halo "
                                   "word, per-rank records, owners' pulls, pipelined count), NOT a scaling measurement")
-    line.update(digest)
+    if digest is not None:
+        line.update(digest)
     print(json.dumps(line), flush=True)
     multi.dna_free(mdna)
     multi.close()
-    if digest_failed(digest):
+    if digest is not None and digest_failed(digest):
         raise SystemExit(3)                       # the groups differ from the CPU oracle's: the number above is void
 
 
@@ -629,6 +677,103 @@ def digest_check(config, n_bases, k, seed, motif, got, rows=None):
 
 def digest_failed(d):
     return d.get("digest_ok") is False or d.get("digest_total_ok") is False
+
+
+_MIX = 0x9E3779B97F4A7C15 - (1 << 64)       # splitmix64's odd constant as an int64 (the products wrap)
+
+
+def sample_shift(n_rows):
+    """--dump-outputs: a value is in the fixed sample when `shift` bits of its hash are zero; about 2^DUMP_SAMPLE_LOG2 of
+    n_rows (the input's rows, so that the sample does not depend on what was computed from them)"""
+    return max(0, int(n_rows).bit_length() - DUMP_SAMPLE_LOG2)
+
+
+def _sampled(vals, shift):
+    """int64 tensor -> mask of the fixed sample: bits 32 .. 32 + shift - 1 of vals * _MIX all zero"""
+    import torch
+    if shift == 0:
+        return torch.ones_like(vals, dtype=torch.bool)
+    return (((vals * _MIX) >> 32) & ((1 << shift) - 1)) == 0
+
+
+def _device_view(ptr, n, typestr, device):
+    """n elements of the library's device memory as a torch tensor on cuda:device (no copy)"""
+    import types
+    import torch
+    arr = types.SimpleNamespace(__cuda_array_interface__={"shape": (int(n),), "typestr": typestr,
+                                                          "data": (int(ptr), False), "version": 2})
+    return torch.as_tensor(arr, device=torch.device("cuda", device))
+
+
+def _save(out_dir, **arrays):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def _split_u64(a):
+    """uint64 -> (high, low) 32-bit halves, each exact in float64"""
+    import numpy as np
+    return a >> np.uint64(32), a & np.uint64(0xFFFFFFFF)
+
+
+def dump_hists(hists, out_dir, n_rows):
+    """--dump-outputs of a count: hists = [(Hist, device)], the last timed step's result (one per rank, disjoint groups).
+      hist_summary.npy                      [total, distinct, unique, checksum >> 32, checksum & 0xFFFFFFFF] (dnagpu_hist_summary,
+                                            summed over the ranks; the checksum is a wrapping sum over the groups)
+      group_key_hi / _lo, group_count.npy   the groups whose key is in the fixed sample, ascending key (the group order of
+                                            an unordered histogram is unspecified); a key as its two 32-bit halves"""
+    import numpy as np
+    import torch
+    shift = sample_shift(n_rows)
+    chunk = 1 << 27
+    sums = [0, 0, 0, 0]
+    keys, counts = [], []
+    for h, dev in hists:
+        for i, v in enumerate(h.summary()):
+            sums[i] = (sums[i] + int(v)) & 0xFFFFFFFFFFFFFFFF
+        h.ctx.synchronize()
+        for p in range(h.n_parts):
+            kp, cp, ext = h.part_arrays(p)
+            if ext == 0:
+                continue
+            kv, cv = _device_view(kp, ext, "<i8", dev), _device_view(cp, ext, "<i4", dev)
+            for a in range(0, ext, chunk):
+                kc, cc = kv[a:a + chunk], cv[a:a + chunk]
+                m = (cc != 0) & _sampled(kc, shift)          # (count-0 slots are padding)
+                keys.append(kc[m].cpu().numpy())
+                counts.append(cc[m].cpu().numpy())
+        torch.cuda.synchronize(dev)
+    k = np.concatenate(keys).view(np.uint64) if keys else np.zeros(0, np.uint64)
+    c = np.concatenate(counts).view(np.uint32) if counts else np.zeros(0, np.uint32)
+    order = np.argsort(k, kind="stable")
+    k, c = k[order], c[order]
+    khi, klo = _split_u64(k)
+    chi, clo = _split_u64(np.uint64(sums[3]))
+    _save(out_dir, hist_summary=[sums[0], sums[1], sums[2], chi, clo], group_key_hi=khi, group_key_lo=klo, group_count=c)
+
+
+def dump_rows(ctx, device, out_dir, dev_keys, dev_pos, n_match, n_rows):
+    """--dump-outputs of config 5: the matching rows the last timed step wrote to device memory.
+      row_count.npy                           [matches]
+      row_key_hi / _lo (, row_pos).npy        the rows in the fixed sample (by position; by key with --keys-only, which
+                                              writes no positions), ascending position (key); a key as its two halves"""
+    import numpy as np
+    shift = sample_shift(n_rows)
+    ctx.synchronize()
+    out = {"row_count": [n_match]}
+    if n_match:
+        kv = _device_view(dev_keys, n_match, "<i8", device)
+        pv = _device_view(dev_pos, n_match, "<i8", device) if dev_pos else None
+        m = _sampled(kv if pv is None else pv, shift)
+        k = kv[m].cpu().numpy().view(np.uint64)
+        p = pv[m].cpu().numpy() if pv is not None else None
+        order = np.argsort(k if p is None else p, kind="stable")
+        out["row_key_hi"], out["row_key_lo"] = _split_u64(k[order])
+        if p is not None:
+            out["row_pos"] = p[order]
+    _save(out_dir, **out)
 
 
 def job_fractions(b_in, distinct, n_kmers, t_step, world):

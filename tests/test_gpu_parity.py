@@ -1472,7 +1472,7 @@ def test_bench_gpus2_one_process_rehearsal():
     import sys
     from __graft_entry__ import ROOT
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--n-bases", "200000000"], capture_output=True, text=True, timeout=600)
+                          "--n-bases", "200000000", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     pkg = load_package()
@@ -1496,7 +1496,8 @@ def test_bench_digest_check_flips_on_a_wrong_digest(tmp_path):
     import subprocess
     import sys
     from __graft_entry__ import ROOT
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "3", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "3", "--steps", "1", "--warmup", "1", "--full",
+           "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -1512,6 +1513,66 @@ def test_bench_digest_check_flips_on_a_wrong_digest(tmp_path):
     assert out.returncode == 3
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["digest_ok"] is False and line["digest_expected"]["checksum"] == bad["3"]["checksum"]
+
+
+def _dumped(d):
+    return {f[:-len(".npy")]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+
+
+def _u64(hi, lo):
+    return (hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64)
+
+
+def _in_dump_sample(vals, n_rows):
+    """bench.py's fixed sample, restated on the host: bits 32 .. 32 + shift - 1 of vals * 0x9E3779B97F4A7C15 all zero"""
+    import bench
+    shift = bench.sample_shift(n_rows)
+    h = (np.asarray(vals, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)) >> np.uint64(32)
+    return (h & np.uint64((1 << shift) - 1)) == 0
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """a plain bench run (no --full): the contract's fields, --steps honoured, none of the --full extras; --dump-outputs
+    writes the last timed step's result: a count's digest and sampled groups, a filter's sampled rows, both equal to the
+    CPU oracle's"""
+    import json
+    import subprocess
+    import sys
+    from __graft_entry__ import ROOT
+
+    def run(*a):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *a], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        return json.loads(out.stdout.strip().splitlines()[-1])
+
+    n, k, seed = 3_000_000, 21, 0xD2A0001            # configs 2 and 5 at 3 Mbase
+    words = orc.synth_words(seed, n)
+    d = tmp_path / "count"
+    line = run("--config", "2", "--n-bases", str(n), "--steps", "3", "--warmup", "1", "--dump-outputs", str(d))
+    assert all(f in line for f in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"))
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "k-mers/s"
+    assert not {"digest", "digest_ok", "cpu_baseline", "sorted_view_ms"} & set(line)
+    got = _dumped(d)
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64 << 20
+    ok, oc = orc.count_kmers(words, n, k)
+    t, nd, u, cs = orc.hist_summary(ok, oc)
+    assert got["hist_summary"].tolist() == [t, nd, u, cs >> 32, cs & 0xFFFFFFFF]
+    sel = _in_dump_sample(ok, n - k + 1)
+    assert 0 < sel.sum() < len(ok)
+    assert np.array_equal(_u64(got["group_key_hi"], got["group_key_lo"]), ok[sel])
+    assert np.array_equal(got["group_count"], oc[sel].astype(np.float64))
+
+    d5 = tmp_path / "filter"
+    line = run("--config", "5", "--n-bases", str(n), "--steps", "2", "--warmup", "1", "--dump-outputs", str(d5))
+    assert line["steps"] == 2 and line["unit"] == "rows/s" and "cpu_baseline" not in line
+    got = _dumped(d5)
+    wk, wp = orc.generate_kmers_contains(words, n, k, "NNNNNNNNNNWSNNNNNNNNN")
+    assert got["row_count"].tolist() == [len(wk)] and len(wk) > 0
+    sel = _in_dump_sample(wp, n - k + 1)
+    order = np.argsort(wp[sel], kind="stable")
+    assert np.array_equal(got["row_pos"], wp[sel][order].astype(np.float64))
+    assert np.array_equal(_u64(got["row_key_hi"], got["row_key_lo"]), wk[sel][order])
 
 
 def test_count_multi_rccl_one_rank(pkg, ctx):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/ab_cfg.sh <tag> "<bench args>" libA.so libB.so ...: one bench line (any config / variant) with each library in turn, REPS times, on one box
-TAG=$1; ARGS=$2; shift 2
+TAG=$1; ARGS="$2 --full"; shift 2    # (--full: the line carries the digest check printed as ok=)
 mkdir -p gpurun_out/$TAG
 cd $GRAFT_REPO_ROOT
 for rep in $(seq 1 ${REPS:-2}); do

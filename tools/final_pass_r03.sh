@@ -6,7 +6,7 @@ TAG=${1:-r03_final}
 O=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $O
 cd $GRAFT_REPO_ROOT
-B="timeout -k 10 400 python3 bench.py"
+B="timeout -k 10 400 python3 bench.py --full"
 $B > $O/bench.json 2> $O/bench.err || exit 1
 echo "headline: $(python3 -c "import json;l=json.loads(open('$O/bench.json').read().strip().splitlines()[-1]);print(round(l['ms_per_step'],2),'ms',round(l['value']/1e9,1),'G',l['roofline']['kernel'],l['roofline']['frac'])")"
 $B --engine tree --no-cpu-baseline > $O/bench_tree.json 2>> $O/bench.err || exit 1

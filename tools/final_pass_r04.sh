@@ -8,7 +8,7 @@ TAG=${1:-r04_final}; PART=${2:-all}
 O=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $O
 cd $GRAFT_REPO_ROOT
-B="timeout -k 10 400 python3 bench.py"
+B="timeout -k 10 400 python3 bench.py --full"
 if [ "$PART" = "bench" ] || [ "$PART" = "all" ]; then
   $B > $O/bench.json 2> $O/bench.err || exit 1
   echo "headline: $(python3 -c "import json;l=json.loads(open('$O/bench.json').read().strip().splitlines()[-1]);print(round(l['ms_per_step'],2),'ms',round(l['value']/1e9,1),'G',l['roofline']['kernel'],l['roofline']['frac'],'digest_ok',l['digest_ok'])")"

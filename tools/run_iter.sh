@@ -10,7 +10,7 @@ echo "rc=$rc" >> $O/pytest.log; tail -4 $O/pytest.log
 [ $rc -eq 0 ] || exit 1
 timeout -k 10 500 python3 tools/fuzz_unordered.py $FZ > $O/fuzz.log 2>&1; rc=$?; tail -2 $O/fuzz.log
 [ $rc -eq 0 ] || exit 1
-B="timeout -k 10 300 python3 bench.py --no-cpu-baseline"
+B="timeout -k 10 300 python3 bench.py --full --no-cpu-baseline"
 for cfg in "" "--config 3" "--config 2" "--motif 1000" "--config 3 --motif 1000"; do
   n=$(echo "bench$cfg" | tr -d ' -')
   $B $cfg > $O/$n.json 2> $O/$n.err || { echo "bench $cfg failed"; tail -3 $O/$n.err; exit 1; }

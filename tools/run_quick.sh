@@ -10,7 +10,7 @@ echo "rc=$rc" >> $O/pytest.log; tail -3 $O/pytest.log
 [ $rc -eq 0 ] || exit 1
 timeout -k 10 200 python3 tools/fuzz_unordered.py 120 > $O/fuzz.log 2>&1; rc=$?; tail -1 $O/fuzz.log
 [ $rc -eq 0 ] || exit 1
-B="timeout -k 10 300 python3 bench.py --no-cpu-baseline"
+B="timeout -k 10 300 python3 bench.py --full --no-cpu-baseline"
 for cfg in "" "--config 3" "--config 2" "$@"; do
   n=$(echo "bench$cfg" | tr -d ' -')
   $B $cfg > $O/$n.json 2> $O/$n.err || { echo "bench $cfg failed"; tail -3 $O/$n.err; exit 1; }
