@@ -241,6 +241,7 @@ struct dnagpu_hist {
     // group, each group into arrays of its own.  The head then owns no arrays (keys == nullptr); n_distinct / total /
     // extent are the sums over the parts, the groups of part i come before those of part i + 1 in every ordered read.
     std::vector<dnagpu_hist *> parts;
+    int k = 0;        // the k the rows were counted with (0 = unknown): dnagpu_hist_merge refuses two different ones
 };
 
 // DNAGPU_DEBUG_POISON_POOL: no work buffer starts out zeroed (fresh hipMalloc memory) or holding a
@@ -2431,28 +2432,36 @@ static int count_core(dnagpu_ctx *ctx, const dnagpu_dna *dna, u64 first, u64 n, 
     return DNAGPU_OK;
 }
 
+// the histogram a count hands out carries the k it was counted with (dnagpu_hist_merge compares them)
+static int with_k(int rc, dnagpu_hist **out, int k)
+{
+    if (rc == DNAGPU_OK && out && *out)
+        (*out)->k = k;
+    return rc;
+}
+
 extern "C" int dnagpu_count_kmers(dnagpu_ctx *ctx, const dnagpu_dna *dna, int k, uint64_t first,
                                   uint64_t count, dnagpu_hist **out)
 {
-    return guarded([&]() -> int {
+    return with_k(guarded([&]() -> int {
     if (!ctx || !dna || !out)
         return DNAGPU_ERR_BAD_ARG;
     RC_TRY(check_range(dna, k, first, count));
     HIP_TRY(hipSetDevice(ctx->device));
     return count_core(ctx, dna, first, count, k, nullptr, out);
-    });
+    }), out, k);
 }
 
 extern "C" int dnagpu_count_kmers_unordered(dnagpu_ctx *ctx, const dnagpu_dna *dna, int k, uint64_t first,
                                             uint64_t count, dnagpu_hist **out)
 {
-    return guarded([&]() -> int {
+    return with_k(guarded([&]() -> int {
     if (!ctx || !dna || !out)
         return DNAGPU_ERR_BAD_ARG;
     RC_TRY(check_range(dna, k, first, count));
     HIP_TRY(hipSetDevice(ctx->device));
     return count_core(ctx, dna, first, count, k, nullptr, out, 0, 0, 0, 1, true);
-    });
+    }), out, k);
 }
 
 // ---- GROUP BY kmer, count(*) FROM a table of sequences, LATERAL generate_kmers(sequence, k) (test.sql:140-150)
@@ -2489,11 +2498,17 @@ static int count_table(dnagpu_ctx *ctx, const dnagpu_dna *dna, const u32 *marks,
         if (!h)
             return DNAGPU_ERR_OOM;
         prof_begin(ctx);
-        ctx->batch_marks = marks;
-        ctx->batch_mark_words = n_mark_words;
-        const int rc = count_sk(ctx, dna, 0, n_windows, k, h, rows);
-        ctx->batch_marks = nullptr;
-        ctx->batch_mark_words = 0;
+        int rc;
+        {
+            // the marks are this call's (pool memory released behind it): cleared on every way out of count_sk, a
+            // std::bad_alloc included, so that no later count of this context reads them
+            struct MarksScope {
+                dnagpu_ctx *c;
+                MarksScope(dnagpu_ctx *c_, const u32 *m, u64 w) : c(c_) { c->batch_marks = m; c->batch_mark_words = w; }
+                ~MarksScope() { c->batch_marks = nullptr; c->batch_mark_words = 0; }
+            } marks_scope(ctx, marks, n_mark_words);
+            rc = count_sk(ctx, dna, 0, n_windows, k, h, rows);
+        }
         prof_end(ctx);
         if (rc == DNAGPU_OK) {
             *out = h;
@@ -2522,7 +2537,7 @@ static int count_table(dnagpu_ctx *ctx, const dnagpu_dna *dna, const u32 *marks,
 extern "C" int dnagpu_count_kmers_batch(dnagpu_ctx *ctx, const dnagpu_dna *dna, const uint64_t *seq_starts, uint64_t n_seqs,
                                         int k, dnagpu_hist **out)
 {
-    return guarded([&]() -> int {
+    return with_k(guarded([&]() -> int {
     if (!ctx || !dna || !out || (n_seqs && !seq_starts))
         return DNAGPU_ERR_BAD_ARG;
     if (k < 1 || k > 32)
@@ -2549,7 +2564,7 @@ extern "C" int dnagpu_count_kmers_batch(dnagpu_ctx *ctx, const dnagpu_dna *dna, 
     HIP_TRY(launch_batch_marks(d_starts, n_seqs, marks, n_mark_words, st));
     HIP_TRY(hipStreamSynchronize(st));             // (seq_starts is the caller's: not kept behind the call)
     return count_table(ctx, dna, marks, n_mark_words, rows, k, out);
-    });
+    }), out, k);
 }
 
 // The table's boundaries made resident: validated, uploaded, and the marks built ONCE; dnagpu_count_kmers_table then counts
@@ -2605,7 +2620,7 @@ extern "C" uint64_t dnagpu_dna_sequences(const dnagpu_dna *dna) { return dna ? d
 
 extern "C" int dnagpu_count_kmers_table(dnagpu_ctx *ctx, const dnagpu_dna *dna, int k, dnagpu_hist **out)
 {
-    return guarded([&]() -> int {
+    return with_k(guarded([&]() -> int {
     if (!ctx || !dna || !out)
         return DNAGPU_ERR_BAD_ARG;
     if (k < 1 || k > 32)
@@ -2629,7 +2644,7 @@ extern "C" int dnagpu_count_kmers_table(dnagpu_ctx *ctx, const dnagpu_dna *dna, 
     if (dna->n_seqs == 1)
         return count_core(ctx, dna, 0, rows, k, nullptr, out, 0, 0, 0, 1, true);
     return count_table(ctx, dna, dna->seq_marks, dna->n_mark_words, rows, k, out);
-    });
+    }), out, k);
 }
 
 extern "C" int dnagpu_hist_is_sorted(const dnagpu_hist *h) { return h && h->sorted ? 1 : 0; }
@@ -2739,31 +2754,31 @@ extern "C" int dnagpu_count_records(dnagpu_ctx *ctx, const void *const *pieces, 
 extern "C" int dnagpu_count_kmers_owned(dnagpu_ctx *ctx, const dnagpu_dna *dna, int k, uint64_t first,
                                         uint64_t count, int owner, int n_owners, dnagpu_hist **out)
 {
-    return guarded([&]() -> int {
+    return with_k(guarded([&]() -> int {
     if (!ctx || !dna || !out || n_owners < 1 || owner < 0 || owner >= n_owners)
         return DNAGPU_ERR_BAD_ARG;
     RC_TRY(check_range(dna, k, first, count));
     HIP_TRY(hipSetDevice(ctx->device));
     return count_core(ctx, dna, first, count, k, nullptr, out, 0, 0, owner, n_owners);
-    });
+    }), out, k);
 }
 
 extern "C" int dnagpu_count_keys(dnagpu_ctx *ctx, uint64_t *dev_keys, uint64_t n, int k, dnagpu_hist **out)
 {
-    return guarded([&]() -> int {
+    return with_k(guarded([&]() -> int {
     if (!ctx || !out || (n && !dev_keys))
         return DNAGPU_ERR_BAD_ARG;
     if (k <= 0 || k > 32)
         return DNAGPU_ERR_INVALID_K;
     HIP_TRY(hipSetDevice(ctx->device));
     return count_core(ctx, nullptr, 0, n, k, dev_keys, out);
-    });
+    }), out, k);
 }
 
 extern "C" int dnagpu_count_keys_in_range(dnagpu_ctx *ctx, uint64_t *dev_keys, uint64_t n, int k,
                                           uint64_t key_min, uint64_t key_max, dnagpu_hist **out)
 {
-    return guarded([&]() -> int {
+    return with_k(guarded([&]() -> int {
     if (!ctx || !out || (n && !dev_keys) || key_min > key_max)
         return DNAGPU_ERR_BAD_ARG;
     if (k <= 0 || k > 32)
@@ -2779,7 +2794,7 @@ extern "C" int dnagpu_count_keys_in_range(dnagpu_ctx *ctx, uint64_t *dev_keys, u
     const u64 prefix = free_bits >= 64 ? 0 : (key_min >> free_bits) << free_bits;
     // a single possible key (fixed == 2k) still runs through the generic path: rem = 0 leaf
     return count_core(ctx, nullptr, 0, n, k, dev_keys, out, fixed, prefix);
-    });
+    }), out, k);
 }
 
 extern "C" uint64_t dnagpu_hist_distinct(const dnagpu_hist *h) { return h ? h->n_distinct : 0; }
@@ -2926,18 +2941,25 @@ extern "C" int dnagpu_hist_summary(dnagpu_ctx *ctx, const dnagpu_hist *h, uint64
 }
 
 // The groups of a and b added up: equal keys' counts are summed.  Both histograms must live on ctx's device; they are
-// left as they are.
+// left as they are.  Histograms counted with different k are refused (BAD_ARG); the result carries their k.
 extern "C" int dnagpu_hist_merge(dnagpu_ctx *ctx, const dnagpu_hist *a, const dnagpu_hist *b, dnagpu_hist **out)
 {
     return guarded([&]() -> int {
     if (!ctx || !a || !b || !out)
         return DNAGPU_ERR_BAD_ARG;
     *out = nullptr;
+    if (a->k && b->k && a->k != b->k)
+        return DNAGPU_ERR_BAD_ARG;                 // (keys of different k: equal values would be different k-mers)
     if (a->total + b->total > 0xFFFFFFFFull)
         return DNAGPU_ERR_TOO_LARGE;               // (counts are 32-bit in device memory)
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     PoolScope ps(ctx);
+    // (host sources of the copies below: they live until the synchronize before the return)
+    const u64 kk = ~(u64)0;
+    u32 cc = 0;
+    const u64 zero = 0;
+    u32 d32 = 0;
     const u64 n_max = a->n_distinct + b->n_distinct;
     u64 t_slots = 1024;
     while (t_slots < 2 * n_max)
@@ -2971,17 +2993,15 @@ extern "C" int dnagpu_hist_merge(dnagpu_ctx *ctx, const dnagpu_hist *a, const dn
         set_err("hist merge: %llu groups out of %llu", (unsigned long long)D, (unsigned long long)n_max);
         return DNAGPU_ERR_INTERNAL;
     }
+    if (D + (res[0] ? 1 : 0) > 0xFFFFFFFFull)
+        return DNAGPU_ERR_TOO_LARGE;
     if (res[0]) {                                  // the all-ones key goes last (n_max has room: it was a group of a or b)
-        const u64 kk = ~(u64)0;
-        const u32 cc = (u32)res[0];
+        cc = (u32)res[0];
         HIP_TRY(hipMemcpyAsync(ok + D, &kk, 8, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(oc + D, &cc, 4, hipMemcpyHostToDevice, st));
         D++;
     }
-    const u64 zero = 0;
-    const u32 d32 = (u32)D;
-    if (D > 0xFFFFFFFFull)
-        return DNAGPU_ERR_TOO_LARGE;
+    d32 = (u32)D;
     HIP_TRY(hipMemcpyAsync(seg_off, &zero, 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(seg_cnt, &d32, 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -2989,6 +3009,7 @@ extern "C" int dnagpu_hist_merge(dnagpu_ctx *ctx, const dnagpu_hist *a, const dn
     dnagpu_hist *h = new (std::nothrow) dnagpu_hist{ok, oc, D, a->total + b->total, seg_off, seg_cnt, nullptr, 1, false};
     if (!h)
         return DNAGPU_ERR_OOM;
+    h->k = a->k ? a->k : b->k;
     ps.release(ok);
     ps.release(oc);
     ps.release(seg_off);

@@ -252,8 +252,10 @@ int dnagpu_hist_summary(dnagpu_ctx *ctx, const dnagpu_hist *h, uint64_t *total, 
  * batch (dnagpu_count_kmers_batch) does with the batches' histograms; also a PostgreSQL aggregate's combine step.  a and
  * b stay as they are; all three live on ctx's device.  The result is an unordered histogram of one part (dnagpu_hist_is_sorted
  * == 0; here the groups are in no order at all, also inside its one segment).  DNAGPU_ERR_TOO_LARGE when the totals pass
- * 2^32 - 1 (counts are 32-bit in device memory).  A utility (one random probe of a device-memory table per group), not
- * part of the streaming path. */
+ * 2^32 - 1 (counts are 32-bit in device memory).  DNAGPU_ERR_BAD_ARG, and no histogram, when a and b were counted with
+ * different k: every histogram of dnagpu_count_kmers, _unordered, _batch, _table, _owned, dnagpu_count_keys and
+ * _keys_in_range records its k (a merge result takes its inputs'); one that records none (the multi-GPU counts) merges with
+ * any.  A utility (one random probe of a device-memory table per group), not part of the streaming path. */
 int dnagpu_hist_merge(dnagpu_ctx *ctx, const dnagpu_hist *a, const dnagpu_hist *b, dnagpu_hist **out);
 void dnagpu_hist_free(dnagpu_ctx *ctx, dnagpu_hist *h);
 

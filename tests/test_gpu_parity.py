@@ -777,6 +777,13 @@ def genome_like_words(n, seed=0x6E0):
     return genome_like.packed_words(n, seed)
 
 
+def genome_like_codes(n, seed=0x6E0):
+    """tools/genome_like.codes: the same sequence as 2-bit codes"""
+    genome_like_words(1)                     # (puts tools/ on the path)
+    import genome_like
+    return genome_like.codes(n, seed)
+
+
 @pytest.mark.parametrize("kind", ["motif1000", "motif37", "motif100000", "polyA", "half-polyA", "quarter-polyA", "AT",
                                   "small-polyA", "small-AT", "genome-like"])
 @pytest.mark.parametrize("k", [31, 21])
@@ -1227,6 +1234,103 @@ def table_of_sequences(seed, n_seqs, lo, hi):
     return orc.synth_words(seed, n), starts
 
 
+# the super-k-mer engine's geometry (superkmer_kernels.hip): a wave tile emits records for SKW_ROWS = 63 x 32 rows (lane 63
+# only supplies hashes), a workgroup's four waves take one round of SK_TILE_ROWS, chunks are cut at multiples of a round
+SK_WAVE_ROWS = 2016
+SK_ROUND_ROWS = 4 * SK_WAVE_ROWS
+
+
+def sk_m(k):
+    """sk_minimizer_len"""
+    return 15 if k >= 23 else (13 if k >= 21 else 12)
+
+
+def sk_lmax(k):
+    """rows per record at most (a record holds 54 bases)"""
+    return min(55 - k, 32)
+
+
+def sk_chunk_rows(n_rows):
+    """level 0's chunk length: the exact pair's (4096 chunks) and the slab sweep's (1024) formulas in dnagpu_api.hip"""
+    return tuple((max(4 * SK_ROUND_ROWS, (n_rows + c - 1) // c) + SK_ROUND_ROWS - 1) // SK_ROUND_ROWS * SK_ROUND_ROWS
+                 for c in (4096, 1024))
+
+
+def pack_codes_bytes(c):
+    """pack_codes for tens of Mbase: four bases per byte, eight bytes per little-endian word (the same layout)"""
+    n = len(c)
+    pad = np.zeros((n + 31) // 32 * 32, dtype=np.uint8)
+    pad[:n] = c
+    b = pad[0::4] | (pad[1::4] << 2) | (pad[2::4] << 4) | (pad[3::4] << 6)
+    return b.view("<u8").astype(np.uint64)
+
+
+RR_KINDS = ("random", "dup", "tail", "polyA", "polyG", "micro", "tandem37", "genome")
+RR_MICRO = [np.array(u, dtype=np.uint8) for u in ([0, 1], [2, 0, 3], [3, 0, 1, 0])]      # (AT)n, (CAG)n, (GATA)n
+
+
+def repeat_rich_table(seed, n_seqs, lo, hi, mix):
+    """a table of reads such as real ones are: n_seqs reads of lo .. hi bases, back to back in one packed stream, of the
+    kinds `mix` weighs (RR_KINDS): random; exact copies of 300 templates (PCR duplicates: length and bases alike); random
+    with a poly-A or poly-T head or tail of 15 - 60 bases; all A; all G (at k = 32 the all-G key is the value of an empty
+    slot); (AT)n / (CAG)n / (GATA)n in a random phase; a 37-base tandem unit in a random phase; slices of genome_like.codes.
+    Plus edge rows: empty reads, reads shorter than any k, and for every k of reads of k - 1, k, k + 1, k + lmax - 1 and
+    k + lmax bases (lmax: sk_lmax).  -> (words, starts)"""
+    rng = np.random.default_rng(seed)
+    w = np.array([float(mix.get(x, 0)) for x in RR_KINDS])
+    kind = rng.choice(len(RR_KINDS), size=n_seqs, p=w / w.sum())
+    lens = rng.integers(lo, hi + 1, n_seqs)
+    n_tpl = 300
+    tpl_len = rng.integers(lo, hi + 1, n_tpl)
+    tpl = rng.integers(0, 4, (n_tpl, hi), dtype=np.uint8)
+    tid = rng.integers(0, n_tpl, n_seqs)
+    dup = kind == RR_KINDS.index("dup")
+    lens[dup] = tpl_len[tid[dup]]
+    if n_seqs >= 1000:
+        edge = [0, 0, 0, 1, 2, 7] + [x for k in range(1, 33) for x in (k - 1, k, k + 1, k + sk_lmax(k) - 1, k + sk_lmax(k))]
+        at = rng.choice(n_seqs, len(edge), replace=False)
+        lens[at] = edge
+        kind[at] = 0
+    starts = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    n = int(starts[-1])
+    c = rng.integers(0, 4, n, dtype=np.uint8)
+    # per-read parameters drawn at once (a draw per read costs more than the copy)
+    tail_len = rng.integers(15, 61, n_seqs)
+    tail_base = rng.integers(0, 2, n_seqs).astype(np.uint8)           # poly-A or poly-T
+    tail_head = rng.random(n_seqs) < 0.5
+    micro = rng.integers(0, len(RR_MICRO), n_seqs)
+    phase = rng.integers(0, 37, n_seqs)
+    unit37 = rng.integers(0, 4, 37, dtype=np.uint8)
+    g = None
+    if mix.get("genome", 0):
+        g = genome_like_codes(min(n, 4_000_000) + hi + 1, seed)
+        goff = rng.integers(0, len(g) - hi, n_seqs)
+    for i in np.flatnonzero(kind != 0):
+        a, ln = int(starts[i]), int(lens[i])
+        kd = RR_KINDS[kind[i]]
+        if kd == "dup":
+            c[a:a + ln] = tpl[tid[i], :ln]
+        elif kd == "tail":
+            t = min(int(tail_len[i]), ln)
+            if tail_head[i]:
+                c[a:a + t] = tail_base[i]
+            else:
+                c[a + ln - t:a + ln] = tail_base[i]
+        elif kd == "polyA":
+            c[a:a + ln] = 0
+        elif kd == "polyG":
+            c[a:a + ln] = 3
+        elif kd == "micro":
+            u = RR_MICRO[micro[i]]
+            c[a:a + ln] = np.resize(np.roll(u, -int(phase[i] % len(u))), ln)
+        elif kd == "tandem37":
+            c[a:a + ln] = np.resize(np.roll(unit37, -int(phase[i])), ln)
+        else:
+            o = int(goff[i])
+            c[a:a + ln] = g[o:o + ln]
+    return pack_codes_bytes(c), starts.astype(np.uint64)
+
+
 @pytest.mark.parametrize("n_seqs,lo,hi", [(1, 5000, 5000), (2, 50, 10_000), (1000, 50, 10_000), (1_000_000, 50, 250),
                                          (200_000, 140, 160), (3, 1, 40), (40_000, 20, 64)])
 def test_count_kmers_batch_table_of_sequences(ctx, pkg, n_seqs, lo, hi):
@@ -1317,6 +1421,293 @@ def test_hist_merge_adds_the_batches_of_a_table(ctx, pkg, k):
         h.free()
     for d in (da, db, dr):
         d.free()
+
+
+def _count_both(ctx, pkg, d, starts, k, flags, ok, oc, what):
+    """the table through dnagpu_count_kmers_batch and, made resident before, dnagpu_count_kmers_table: both the oracle's
+    groups -> the phases of the two calls (profiling on)"""
+    seen = []
+    for entry in ("batch", "resident"):
+        ctx.set_debug(flags)
+        try:
+            h = ctx.count_kmers_batch(d, starts, k) if entry == "batch" else ctx.count_kmers_table(d, k)
+        finally:
+            ctx.set_debug(0)
+        phases = {a for a, _ in ctx.last_phase_times()}
+        w = f"{what}, k={k}, {entry}"
+        assert h.total == int(oc.sum()), w
+        check_hist(h, ok, oc, w) if h.is_sorted else check_hist_unordered(h, ok, oc, w)
+        seen.append((h.is_sorted, phases))
+        h.free()
+    return seen
+
+
+RR_TABLES = {
+    # mostly PCR duplicates (copies of 300 templates), some tails and homopolymer reads
+    "duplicates": (0x4EAD5, 9_000, 80, 250, dict(dup=0.6, random=0.1, tail=0.2, polyA=0.05, polyG=0.05)),
+    # mostly homopolymers and microsatellites: at the short k one key (all A) holds half the rows
+    "homopolymers": (0x40B01, 9_000, 80, 250, dict(polyA=0.5, polyG=0.1, micro=0.25, tandem37=0.05, tail=0.05, random=0.05)),
+    # every kind alike
+    "even": (0xE7E4, 9_000, 60, 280, {x: 1 for x in RR_KINDS}),
+}
+
+
+@pytest.mark.parametrize("table", list(RR_TABLES))
+def test_count_table_repeat_rich_every_k(ctx, pkg, table):
+    """tables of reads as real ones are (duplicates, poly-A / poly-T tails, homopolymer reads, microsatellites, edge lengths
+    around every k and k + lmax) at every k of the super-k-mer engine, forced (each k is its own window length W =
+    k - m + 1 in sk_front<W, true> / sk_uniform_value<W, true>) and the default choice, and at short k through
+    batch_keys_kernel + the tree / the dense count; both entry points against the oracle's per-sequence rows"""
+    seed, n_seqs, lo, hi, mix = RR_TABLES[table]
+    words, starts = repeat_rich_table(seed, n_seqs, lo, hi, mix)
+    n = int(starts[-1])
+    assert 1_000_000 <= n <= 2_000_000
+    d = ctx.upload(words, n)
+    d.set_sequences(starts)
+    ctx.set_profiling(True)
+    try:
+        for k in list(range(20, 33)) + [3, 8, 10, 12, 16, 19]:
+            ok, oc = orc.count_keys(orc.generate_kmers_table(words, starts, k))
+            if k <= 12 and table == "homopolymers":
+                assert oc.max() * 2 > oc.sum() * 0.9, "one key (all A) holds about half the rows"
+            for flags in ((pkg.DEBUG_FORCE_SUPERKMER, 0) if k >= 20 else (0,)):
+                seen = _count_both(ctx, pkg, d, starts, k, flags, ok, oc, f"repeat-rich table {table}, flags {flags}")
+                if flags:                          # the forced engine: its records, not the keys + tree fall-back
+                    assert all(not srt and "sk_hist0" in ph and "sk_scatter0" in ph for srt, ph in seen), seen
+    finally:
+        ctx.set_profiling(False)
+    d.free()
+
+
+def tile_edge_table(content, k, seed=0x7E1E):
+    """a stream of one periodic content (poly-A, (AT)n, a 7-base unit; "mixed": the 7-base unit with every other sequence
+    random) over 256 wave tiles of rows, cut into sequences whose starts sit at every residue mod 32 (lane edges, tiles
+    2 .. 33), around wave-tile / workgroup-round / chunk edges at {-k, -k + 1, -m, -m + 1, -1, 0, +1, m - 1}, and one start
+    at +1 alone (a tile uniform but for its first row) -> (words, starts, codes, intended starts, clusters, singles, period)"""
+    m = sk_m(k)
+    rng = np.random.default_rng(seed + k)
+    n_rows = 256 * SK_WAVE_ROWS
+    n = n_rows + k - 1
+    unit = {"polyA": [0], "AT": [0, 1], "unit7": [2, 0, 3, 3, 1, 0, 2], "mixed": [2, 0, 3, 3, 1, 0, 2]}[content]
+    c = np.resize(np.array(unit, dtype=np.uint8), n)
+    lane_starts = [(2 + r) * SK_WAVE_ROWS + 32 * (5 + 2 * r) + r for r in range(32)]
+    offs = (-k, -k + 1, -m, -m + 1, -1, 0, 1, m - 1)
+    wave_edges = [41 * SK_WAVE_ROWS, 67 * SK_WAVE_ROWS, 101 * SK_WAVE_ROWS]
+    round_edges = [44 * SK_WAVE_ROWS, 72 * SK_WAVE_ROWS, 108 * SK_WAVE_ROWS]
+    chunk = sk_chunk_rows(n_rows)
+    assert chunk[0] == chunk[1] == 16 * SK_WAVE_ROWS
+    chunk_edges = [3 * chunk[0], 5 * chunk[0], 7 * chunk[0], 8 * chunk[0], 10 * chunk[0]]
+    clusters = wave_edges + round_edges + chunk_edges
+    singles = [150 * SK_WAVE_ROWS, 11 * chunk[0], 201 * SK_WAVE_ROWS]
+    want = sorted(set(lane_starts + [e + o for e in clusters for o in offs] + [e + 1 for e in singles]))
+    starts = np.array([0] + want + [n], dtype=np.int64)
+    if content == "mixed":                          # (the sequences on both sides of a single start stay periodic)
+        keep = {e + 1 for e in singles}
+        for i in range(1, len(starts) - 1, 2):
+            if int(starts[i]) not in keep and int(starts[i + 1]) not in keep:
+                c[starts[i]:starts[i + 1]] = rng.integers(0, 4, int(starts[i + 1] - starts[i]), dtype=np.uint8)
+    return pack_codes(c), starts.astype(np.uint64), c, want, clusters, singles, len(unit)
+
+
+@pytest.mark.parametrize("content", ["polyA", "AT", "unit7", "mixed"])
+def test_count_table_sequence_starts_at_tile_edges(ctx, pkg, content):
+    """level 0's uniform-tile path with BATCH = true (sk_uniform_value<W, true> from sk_hist0 and sk_scatter0, whose records
+    go straight to sk_build<true>): tables of one periodic content (every window's minimum is the same m-mer value) cut at
+    every lane residue and around the edges of wave tiles, workgroup rounds and chunks, at k of seven window lengths"""
+    for k in (20, 21, 22, 23, 27, 31, 32):
+        words, starts, c, want, clusters, singles, p = tile_edge_table(content, k)
+        n = int(starts[-1])
+        m = sk_m(k)
+        # ---- the table is what it was made to be (or the test no longer exercises the path it was written for)
+        s = starts.astype(np.int64)
+        assert set(want) <= set(s.tolist())
+        assert {int(x) % 32 for x in want} == set(range(32))
+        for e in clusters:
+            assert {e - k, e - k + 1, e - m, e - m + 1, e - 1, e, e + 1, e + m - 1} <= set(s.tolist())
+        n_rows = n - k + 1
+        inner = np.zeros(n + 1, dtype=np.int64)            # starts inside the stream (a row reaches across s: r < s <= r + k - 1)
+        inner[np.unique(s[(s > 0) & (s < n)])] = 1
+        pre = np.concatenate([[0], np.cumsum(inner)])       # pre[i] = starts below i
+        r = np.arange(n_rows)
+        spans = (pre[r + k] - pre[r + 1]) > 0               # rows that are no rows of the table
+        assert spans.sum() == n_rows - len(orc.generate_kmers_table(words, starts, k))
+        bad = np.concatenate([np.zeros(p, dtype=np.int64), (c[p:] != c[:-p]).astype(np.int64)])
+        bpre = np.concatenate([[0], np.cumsum(bad)])        # a base that breaks the period p
+        full = n_rows // SK_WAVE_ROWS
+        t0 = np.arange(full) * SK_WAVE_ROWS
+        periodic = (bpre[t0 + SK_WAVE_ROWS + k - 1] - bpre[t0 + p]) == 0
+        n_span = np.add.reduceat(spans[:full * SK_WAVE_ROWS].astype(np.int64), t0)
+        uniform = periodic & (n_span == 0)                  # one m-mer value in every row, no row across a start
+        assert uniform.sum() >= (0.6 if content != "mixed" else 0.25) * full, (uniform.sum(), full)
+        one_off = periodic & (n_span == 1)                  # uniform but for one row across a start (the singles)
+        assert one_off.sum() >= 3 and all(one_off[e // SK_WAVE_ROWS] for e in singles), one_off.sum()
+        # ---- the count
+        ok, oc = orc.count_keys(orc.generate_kmers_table(words, starts, k))
+        d = ctx.upload(words, n)
+        d.set_sequences(starts)
+        for flags in (pkg.DEBUG_FORCE_SUPERKMER, pkg.DEBUG_FORCE_SUPERKMER | pkg.DEBUG_SLAB0):
+            _count_both(ctx, pkg, d, starts, k, flags, ok, oc, f"tile-edge table {content}, flags {flags}")
+        d.free()
+
+
+# What the cases reach (the phases of both entry points at k = 31, 22 and 21, all asserted below): every case but "heavy
+# expand" splits heavy mid buckets (sk_heavy_split) and counts long final buckets with sk_count_big; the plain forced engine
+# overflows its speculative level-1 regions by itself (sk_spec1, then sk_hist1); on "microsatellites" the slab sweep overflows
+# by itself at k = 22 and 21 (sk_sample0, then sk_hist0), and "heavy expand" sends the count to count_table's SKEWED
+# fall-back (batch_keys_kernel + the tree: a sorted histogram, no sk_ phase); on "duplicates+tails" "heavy expand" expands
+# the heavy buckets (sk_expand_flat) and stays on the records.
+RR_ROUTE_TABLES = {
+    "duplicates+tails": (0xD7A15, 33_000, 100, 200, dict(dup=0.55, tail=0.35, polyA=0.05, random=0.05)),
+    "microsatellites": (0x3A7E, 33_000, 100, 200, dict(micro=0.7, tandem37=0.1, polyA=0.1, random=0.1)),
+}
+
+
+@pytest.mark.parametrize("table", list(RR_ROUTE_TABLES))
+def test_count_table_repeat_rich_every_route(ctx, pkg, table):
+    """the routes behind level 0 on repeat-rich tables, the engine forced, both entry points: the slab sweep and its
+    overflow, the exact pair, speculative level 1 and its fall-back, the sampled regions, heavy mid buckets split by the
+    chunked level kernels and counted by sk_count_big, heavy buckets expanded, and the SKEWED fall-back of count_table to
+    batch_keys_kernel + the tree"""
+    seed, n_seqs, lo, hi, mix = RR_ROUTE_TABLES[table]
+    words, starts = repeat_rich_table(seed, n_seqs, lo, hi, mix)
+    n = int(starts[-1])
+    assert 4_500_000 <= n <= 5_500_000
+    d = ctx.upload(words, n)
+    d.set_sequences(starts)
+    F = pkg.DEBUG_FORCE_SUPERKMER
+    cases = (("slabs", pkg.DEBUG_SLAB0), ("exact pair", pkg.DEBUG_NO_SLAB0), ("slab overflow", pkg.DEBUG_SLAB0_OVERFLOW),
+             ("exact level 1", pkg.DEBUG_NO_SPEC1), ("level 1 overflow", pkg.DEBUG_SPEC1_OVERFLOW),
+             ("sampled regions", pkg.DEBUG_SAMPLE1), ("heavy expand", pkg.DEBUG_HEAVY_EXPAND), ("forced", 0))
+    seen = {}
+    ctx.set_profiling(True)
+    try:
+        for k in (31, 22, 21):
+            ok, oc = orc.count_keys(orc.generate_kmers_table(words, starts, k))
+            for name, flag in cases:
+                seen[(k, name)] = _count_both(ctx, pkg, d, starts, k, F | flag, ok, oc, f"{table} {name}")
+    finally:
+        ctx.set_profiling(False)
+    d.free()
+    for (k, name), both in seen.items():
+        for srt, ph in both:
+            if srt:                                 # count_table's SKEWED fall-back: the table's keys and the tree
+                assert name == "heavy expand" and "leaves" in ph and not any(p.startswith("sk_") for p in ph), (k, name, ph)
+                continue
+            if name == "exact pair":
+                assert "sk_sample0" not in ph and "sk_hist0" in ph, (k, name, ph)
+            if name in ("slabs", "slab overflow"):
+                assert "sk_sample0" in ph, (k, name, ph)
+            if name == "slab overflow":
+                assert "sk_hist0" in ph, (k, name, ph)
+            if name == "exact level 1":
+                assert "sk_spec1" not in ph and "sk_hist1" in ph, (k, name, ph)
+            if name == "level 1 overflow":
+                assert "sk_spec1" in ph and "sk_hist1" in ph, (k, name, ph)
+            if name == "sampled regions":
+                assert "sk_sample1" in ph, (k, name, ph)
+            if name == "forced":
+                assert {"sk_spec1", "sk_hist1", "sk_heavy_split", "sk_count_big"} <= ph, (k, name, ph)
+            if name == "heavy expand":
+                assert "sk_expand_flat" in ph and "sk_heavy_split" not in ph, (k, name, ph)
+    routes = {(k, name): ph for (k, name), both in seen.items() for _, ph in both}
+    assert any("sk_heavy_split" in ph and "sk_count_big" in ph for ph in routes.values()), routes
+    skewed = {key for key, both in seen.items() if any(srt for srt, _ in both)}
+    assert skewed == ({(k, "heavy expand") for k in (31, 22, 21)} if table == "microsatellites" else set()), skewed
+
+
+def test_count_table_repeat_rich_default_engine_at_scale(ctx, pkg):
+    """a mixed table of 3 x 10^5 reads of ~150 bases (~45 Mbase: above SK_MIN_ROWS = 2^25 rows, where the super-k-mer
+    engine is the default for k = 31 and 21) with no debug flag, resident: the heavy-bucket limits the product uses"""
+    words, starts = repeat_rich_table(0x5CA1E, 300_000, 140, 160, {x: 1 for x in RR_KINDS})
+    n = int(starts[-1])
+    d = ctx.upload(words, n)
+    d.set_sequences(starts)
+    ctx.set_profiling(True)
+    try:
+        for k in (31, 21):
+            ok, oc = orc.count_keys(orc.generate_kmers_table(words, starts, k))
+            assert int(oc.sum()) >= 1 << 25
+            h = ctx.count_kmers_table(d, k)
+            phases = {a for a, _ in ctx.last_phase_times()}
+            assert not h.is_sorted and "sk_hist0" in phases, phases      # (the engine by itself)
+            assert h.total == int(oc.sum())
+            check_hist_unordered(h, ok, oc, f"45 Mbase repeat-rich table, default engine, k={k}")
+            h.free()
+    finally:
+        ctx.set_profiling(False)
+    d.free()
+
+
+@pytest.mark.parametrize("k", [32, 31, 21])
+def test_hist_merge_of_repeat_rich_batches(ctx, pkg, k):
+    """a repeat-rich table counted in three batches and merged: the oracle over the whole table (the all-A and all-G keys'
+    counts summed across the batches); histograms of different k do not merge"""
+    words, starts = repeat_rich_table(0x3E7C + k, 6_000, 60, 250, dict(random=1, dup=1, tail=1, polyA=1, polyG=1, micro=1))
+    n = int(starts[-1])
+    seqs = orc.dna_decode(words, n)
+    cuts = [0, 1_900, 4_100, 6_000]
+    hs, ds = [], []
+    all_g = np.uint64(0xFFFFFFFFFFFFFFFF) if k == 32 else np.uint64((1 << (2 * k)) - 1)
+    ctx.set_debug(pkg.DEBUG_FORCE_SUPERKMER)
+    try:
+        for a, b in zip(cuts, cuts[1:]):
+            lo, hi = int(starts[a]), int(starts[b])
+            w, nb = orc.dna_encode(seqs[lo:hi])
+            ds.append(ctx.upload(w, nb))
+            hs.append(ctx.count_kmers_batch(ds[-1], starts[a:b + 1] - np.uint64(lo), k))
+            part = orc.generate_kmers_table(w, starts[a:b + 1] - np.uint64(lo), k)
+            assert np.uint64(0) in part and all_g in part        # (all A, all G: a group of every batch, summed by the merge)
+    finally:
+        ctx.set_debug(0)
+    ok, oc = orc.count_keys(orc.generate_kmers_table(words, starts, k))
+    h01 = hs[0].merge(hs[1])
+    hall = h01.merge(hs[2])
+    assert hall.total == int(oc.sum())
+    check_hist_unordered(hall, ok, oc, f"three batches of a repeat-rich table merged, k={k}")
+    # histograms of another k: refused, no histogram
+    other = ctx.count_kmers_batch(ds[0], starts[:cuts[1] + 1], 20 if k != 20 else 21)
+    for x, y in ((hs[0], other), (other, hall)):
+        with pytest.raises(pkg.DnaGpuError) as ei:
+            x.merge(y)
+        assert ei.value.code == 5                    # DNAGPU_ERR_BAD_ARG
+    for h in hs + [h01, hall, other]:
+        h.free()
+    for dd in ds:
+        dd.free()
+
+
+def test_table_count_leaves_no_state_on_the_context(pkg):
+    """on one context, a table count and a plain unordered count of one sequence in both orders, the engine forced and not:
+    each the oracle's groups (nothing of the table -- its marks -- is left to the next call)"""
+    words, starts = repeat_rich_table(0x57A7E, 9_000, 60, 250, {x: 1 for x in RR_KINDS})
+    n = int(starts[-1])
+    n1 = 1_000_003
+    w1 = orc.synth_words_repeat(0x0DE, n1, 1000)
+    with pkg.Context(0) as c:
+        d = c.upload(words, n)
+        d.set_sequences(starts)
+        d1 = c.upload(w1, n1)
+        for k in (31, 21):
+            tk, tc = orc.count_keys(orc.generate_kmers_table(words, starts, k))
+            pk, pc = orc.count_kmers(w1, n1, k)
+            for flags in (pkg.DEBUG_FORCE_SUPERKMER, 0):
+                c.set_debug(flags)
+                try:
+                    for order in (("table", "plain", "batch", "plain"), ("plain", "batch", "plain", "table")):
+                        for what in order:
+                            if what == "plain":
+                                h = c.count_kmers_unordered(d1, k)
+                                want = (pk, pc)
+                            else:
+                                h = c.count_kmers_table(d, k) if what == "table" else c.count_kmers_batch(d, starts, k)
+                                want = (tk, tc)
+                            w = f"{what} after {order}, k={k}, flags {flags}"
+                            check_hist(h, *want, w) if h.is_sorted else check_hist_unordered(h, *want, w)
+                            h.free()
+                finally:
+                    c.set_debug(0)
+        d.free()
+        d1.free()
 
 
 def test_count_kmers_batch_is_the_plain_count_for_one_sequence_and_checks_its_arguments(ctx, pkg):
