@@ -20,6 +20,7 @@ from .binding import (  # noqa: F401
     DEBUG_SLAB0_OVERFLOW,
     DEBUG_SAMPLE1,
     DEBUG_SPEC1_OVERFLOW,
+    Accumulator,
     Context,
     Dna,
     DnaGpuError,

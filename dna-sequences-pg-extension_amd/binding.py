@@ -154,6 +154,16 @@ def lib():
     L.dnagpu_hist_merge.argtypes = [vp, vp, vp, C.POINTER(vp)]
     L.dnagpu_hist_free.argtypes = [vp, vp]
     L.dnagpu_hist_free.restype = None
+    L.dnagpu_acc_create.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    L.dnagpu_acc_add.argtypes = [vp, vp, vp]
+    L.dnagpu_acc_distinct.argtypes = [vp]
+    L.dnagpu_acc_distinct.restype = C.c_uint64
+    L.dnagpu_acc_total.argtypes = [vp]
+    L.dnagpu_acc_total.restype = C.c_uint64
+    L.dnagpu_acc_summary.argtypes = [vp, vp, u64p, u64p, u64p]
+    L.dnagpu_acc_download.argtypes = [vp, vp, C.c_uint64, C.c_uint64, u64p, u64p]
+    L.dnagpu_acc_free.argtypes = [vp, vp]
+    L.dnagpu_acc_free.restype = None
     L.dnagpu_partition_kmers.argtypes = [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(vp), u64p]
     L.dnagpu_buffer_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
     L.dnagpu_buffer_free.argtypes = [vp, vp]
@@ -376,6 +386,54 @@ class Hist:
             self.h = None
 
 
+class Accumulator:
+    """dnagpu_acc: histograms added up on the device into 64-bit counts (no 2^32 limit); Context.accumulator(k)"""
+
+    def __init__(self, ctx, k):
+        self.ctx, self.h = ctx, C.c_void_p()
+        _chk(lib().dnagpu_acc_create(ctx.h, k, C.byref(self.h)))
+
+    def add(self, hist):
+        _chk(lib().dnagpu_acc_add(self.ctx.h, self.h, hist.h))
+
+    @property
+    def distinct(self):
+        return int(lib().dnagpu_acc_distinct(self.h))
+
+    @property
+    def total(self):
+        return int(lib().dnagpu_acc_total(self.h))
+
+    def summary(self):
+        """(total, distinct, unique, checksum) -- same tuple as Hist.summary and the oracle's hist_summary"""
+        t, u, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _chk(lib().dnagpu_acc_summary(self.ctx.h, self.h, C.byref(t), C.byref(u), C.byref(c)))
+        return t.value, self.distinct, u.value, c.value
+
+    def download(self, first=0, count=None):
+        """groups [first, first+count) as (keys, counts) uint64 arrays; order unspecified but fixed until the next add"""
+        if count is None:
+            count = self.distinct - first
+        keys = np.empty(max(count, 1), dtype=np.uint64)
+        counts = np.empty(max(count, 1), dtype=np.uint64)
+        _chk(lib().dnagpu_acc_download(self.ctx.h, self.h, first, count, keys.ctypes.data_as(u64p),
+                                       counts.ctypes.data_as(u64p)))
+        return keys[:count], counts[:count]
+
+    def free(self):
+        if self.h:
+            if self.ctx._base_debug & DEBUG_GUARD_POOL:
+                self.ctx.synchronize()          # raises if a kernel wrote past the end of a work buffer
+            lib().dnagpu_acc_free(self.ctx.h, self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
 class Context:
     def __init__(self, device=0):
         self.h = C.c_void_p()
@@ -551,6 +609,10 @@ class Context:
         h = C.c_void_p()
         _chk(lib().dnagpu_count_kmers_table(self.h, dna.h, k, C.byref(h)))
         return Hist(self, h)
+
+    def accumulator(self, k):
+        """an empty k-mer accumulator on this context (dnagpu_acc_create): add histograms batch by batch, 64-bit counts"""
+        return Accumulator(self, k)
 
     # ---- the unordered count in two halves (rows on several GPUs: sharded.count_sharded_exchange_records)
     def sk_buckets(self, global_rows, k):

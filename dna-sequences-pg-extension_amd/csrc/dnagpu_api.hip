@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -3033,6 +3034,306 @@ extern "C" void dnagpu_hist_free(dnagpu_ctx *ctx, dnagpu_hist *h)
         pool_free(ctx, h->seg_pre);
     }
     delete h;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the k-mer accumulator (acc_kernels.hip; DESIGN.md "accumulator"): 2^pbits partitions of ACC_SLOTS 16-byte slots.  A table
+// grows -- every partition split on the next hash bits, into new buffers -- when its mean load would pass 3/4; a merge runs
+// only when no partition can end above ACC_BOUND.
+constexpr int ACC_MIN_BITS = 4;
+constexpr u32 ACC_BOUND = ACC_SLOTS / 8 * 7;
+
+struct AccTable {
+    u64 *table = nullptr;     // 2^pbits * ACC_SLOTS * {key, count}
+    u32 *occ = nullptr;       // 2^pbits occupied-slot counts
+    int pbits = 0;            // 0: no table yet
+};
+
+struct dnagpu_acc {
+    int k;
+    AccTable t;
+    u64 distinct = 0, total = 0;
+    std::vector<u64> pre;     // groups before each partition (+ the total): the download order, built after an add
+    u64 *dev_pre = nullptr;
+};
+
+static void acc_table_free(dnagpu_ctx *ctx, AccTable &t)
+{
+    pool_free(ctx, t.table);
+    pool_free(ctx, t.occ);
+    t = AccTable{};
+}
+
+static int acc_table_alloc(dnagpu_ctx *ctx, int pbits, AccTable &t)
+{
+    const u64 P = (u64)1 << pbits;
+    t.pbits = pbits;
+    int rc = pool_alloc_t(ctx, (size_t)(P * ACC_SLOTS * 2), &t.table);
+    if (rc == DNAGPU_OK)
+        rc = pool_alloc_t(ctx, (size_t)P, &t.occ);
+    if (rc != DNAGPU_OK)
+        acc_table_free(ctx, t);
+    return rc;
+}
+
+// the fewest partitions (at least 2^at_least) that hold `groups` at a mean load of 3/4
+static int acc_bits_for(u64 groups, int at_least)
+{
+    int b = std::max(at_least, ACC_MIN_BITS);
+    while (b < 40 && groups > (((u64)ACC_SLOTS << b) / 4) * 3)
+        b++;
+    return b;
+}
+
+static void acc_drop_view(dnagpu_ctx *ctx, dnagpu_acc *acc)
+{
+    acc->pre.clear();
+    pool_free(ctx, acc->dev_pre);
+    acc->dev_pre = nullptr;
+}
+
+extern "C" int dnagpu_acc_create(dnagpu_ctx *ctx, int k, dnagpu_acc **out)
+{
+    return guarded([&]() -> int {
+    if (k < 1 || k > 32)
+        return DNAGPU_ERR_INVALID_K;
+    if (!ctx || !out)
+        return DNAGPU_ERR_BAD_ARG;
+    *out = nullptr;
+    dnagpu_acc *a = new (std::nothrow) dnagpu_acc;
+    if (!a)
+        return DNAGPU_ERR_OOM;
+    a->k = k;
+    *out = a;
+    return DNAGPU_OK;
+    });
+}
+
+extern "C" uint64_t dnagpu_acc_distinct(const dnagpu_acc *acc) { return acc ? acc->distinct : 0; }
+extern "C" uint64_t dnagpu_acc_total(const dnagpu_acc *acc) { return acc ? acc->total : 0; }
+
+extern "C" int dnagpu_acc_add(dnagpu_ctx *ctx, dnagpu_acc *acc, const dnagpu_hist *h)
+{
+    return guarded([&]() -> int {
+    if (!ctx || !acc || !h)
+        return DNAGPU_ERR_BAD_ARG;
+    if (h->k && h->k != acc->k)
+        return DNAGPU_ERR_BAD_ARG;                 // (keys of different k: equal values would be different k-mers)
+    const u64 n_in = h->n_distinct;
+    if (n_in == 0)
+        return DNAGPU_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    PoolScope ps(ctx);
+    // the table the add goes into: the accumulator's own, or a larger one in new buffers that takes over on success
+    AccTable cur = acc->t;
+    struct Fresh {
+        dnagpu_ctx *ctx;
+        AccTable *t;
+        bool on = false;
+        ~Fresh()
+        {
+            if (on)
+                acc_table_free(ctx, *t);
+        }
+    } fresh{ctx, &cur};
+    u32 *stats = nullptr;
+    RC_TRY(ps.alloc(4, &stats));
+    if (acc->distinct == 0) {                      // an empty accumulator is sized from the histogram: no growth later
+        const int b = acc_bits_for(n_in, acc->t.pbits);
+        if (b != acc->t.pbits) {
+            RC_TRY(acc_table_alloc(ctx, b, cur));
+            fresh.on = true;
+            HIP_TRY(hipMemsetAsync(cur.occ, 0, ((size_t)1 << b) * 4, st));
+        }
+    }
+    const dnagpu_hist *const one[1] = {h};
+    const dnagpu_hist *const *parts = h->parts.empty() ? one : h->parts.data();
+    const size_t n_parts = h->parts.empty() ? 1 : h->parts.size();
+    u64 want_cap = 0, n_new = 0;
+    for (int round = 0;; round++) {
+        if (round > 64) {
+            set_err("accumulator: no table size fits the add");
+            return DNAGPU_ERR_INTERNAL;
+        }
+        const u64 P = (u64)1 << cur.pbits;
+        // bins: the expected arrivals per partition + 8 standard deviations (grown to what a round saw if that overflowed)
+        const u64 mean = (n_in + P - 1) / P;
+        u64 cap = mean + 8 * (u64)std::sqrt((double)mean) + 32;
+        cap = std::min<u64>(ACC_SLOTS, (std::max(cap, want_cap) + 31) & ~(u64)31);
+        u32 *cursor = nullptr;
+        u64 *bins = nullptr;
+        RC_TRY(ps.alloc((size_t)P, &cursor));
+        RC_TRY(ps.alloc((size_t)(P * cap * 2), &bins));
+        HIP_TRY(hipMemsetAsync(cursor, 0, (size_t)P * 4, st));
+        HIP_TRY(hipMemsetAsync(stats, 0, 16, st));
+        for (size_t i = 0; i < n_parts; i++) {
+            const dnagpu_hist *q = parts[i];
+            HIP_TRY(launch_acc_bin(q->keys, q->counts, q->extent ? q->extent : q->n_distinct, cur.pbits, cursor, bins, (u32)cap, st));
+        }
+        HIP_TRY(launch_acc_bin_stats(cur.occ, cursor, P, stats, st));
+        u32 m[4] = {0, 0, 0, 0};
+        RC_TRY(read_back(ctx, m, stats, 8));
+        bool commit = m[1] <= cap && m[0] <= ACC_BOUND;
+        u64 grow_for = acc->distinct + n_in;       // (an upper bound of the groups after the add)
+        if (!commit && m[1] > cap && m[1] <= ACC_SLOTS && m[0] <= ACC_BOUND) {
+            want_cap = m[1];                       // a bin overflowed, the table has room: bin again, wider
+            ps.free_now(cursor);
+            ps.free_now(bins);
+            continue;
+        }
+        if (!commit && m[1] <= cap) {              // dry run: how many arrivals are new keys (the rest only add counts)
+            HIP_TRY(hipMemsetAsync(stats, 0, 16, st));
+            HIP_TRY(launch_acc_merge(cur.table, cur.occ, P, cursor, bins, (u32)cap, 0, stats, st));
+            RC_TRY(read_back(ctx, m, stats, 16));
+            commit = m[0] <= ACC_BOUND;
+            grow_for = acc->distinct + ((u64)m[2] | (u64)m[3] << 32);
+        }
+        if (!commit) {                             // grow: every partition split on the next hash bits, into new buffers
+            AccTable next;
+            RC_TRY(acc_table_alloc(ctx, acc_bits_for(grow_for, cur.pbits + 1), next));
+            hipError_t e = hipMemsetAsync(stats, 0, 16, st);
+            if (e == hipSuccess)
+                e = launch_acc_split(cur.table, cur.occ, cur.pbits, next.table, next.occ, next.pbits, stats, st);
+            int rc = DNAGPU_OK;
+            if (e != hipSuccess) {
+                set_err("accumulator split: %s", hipGetErrorString(e));
+                rc = e == hipErrorOutOfMemory ? DNAGPU_ERR_OOM : DNAGPU_ERR_HIP;
+            } else {
+                rc = read_back(ctx, m, stats, 8);
+                if (rc == DNAGPU_OK && m[1]) {
+                    set_err("accumulator split: a partition ran full");
+                    rc = DNAGPU_ERR_INTERNAL;
+                }
+            }
+            if (rc != DNAGPU_OK) {
+                acc_table_free(ctx, next);
+                return rc;
+            }
+            if (fresh.on)
+                acc_table_free(ctx, cur);          // (a grown copy of an earlier round)
+            cur = next;
+            fresh.on = true;
+            want_cap = 0;
+            ps.free_now(cursor);
+            ps.free_now(bins);
+            continue;
+        }
+        HIP_TRY(hipMemsetAsync(stats, 0, 16, st));
+        HIP_TRY(launch_acc_merge(cur.table, cur.occ, P, cursor, bins, (u32)cap, 1, stats, st));
+        RC_TRY(read_back(ctx, m, stats, 16));
+        if (m[1]) {
+            set_err("accumulator merge: a partition ran full");
+            return DNAGPU_ERR_INTERNAL;
+        }
+        n_new = (u64)m[2] | (u64)m[3] << 32;
+        break;
+    }
+    if (fresh.on) {                                // the new table takes over
+        acc_table_free(ctx, acc->t);
+        acc->t = cur;
+        fresh.on = false;
+    }
+    acc->distinct += n_new;
+    acc->total += h->total;
+    acc_drop_view(ctx, acc);
+    return DNAGPU_OK;
+    });
+}
+
+extern "C" int dnagpu_acc_summary(dnagpu_ctx *ctx, const dnagpu_acc *acc, uint64_t *total, uint64_t *unique, uint64_t *checksum)
+{
+    return guarded([&]() -> int {
+    if (!ctx || !acc)
+        return DNAGPU_ERR_BAD_ARG;
+    u64 r[3] = {0, 0, 0};
+    if (acc->distinct) {
+        HIP_TRY(hipSetDevice(ctx->device));
+        PoolScope ps(ctx);
+        u64 *res = nullptr;
+        RC_TRY(ps.alloc(4, &res));
+        HIP_TRY(hipMemsetAsync(res, 0, 32, ctx->stream));
+        HIP_TRY(launch_acc_summary(acc->t.table, acc->t.occ, (u64)1 << acc->t.pbits, res, ctx->stream));
+        RC_TRY(read_back(ctx, r, res, 24));
+    }
+    if (total) *total = r[0];
+    if (unique) *unique = r[1];
+    if (checksum) *checksum = r[2];
+    return DNAGPU_OK;
+    });
+}
+
+extern "C" int dnagpu_acc_download(dnagpu_ctx *ctx, dnagpu_acc *acc, uint64_t first, uint64_t count, uint64_t *keys,
+                                   uint64_t *counts)
+{
+    return guarded([&]() -> int {
+    if (!ctx || !acc)
+        return DNAGPU_ERR_BAD_ARG;
+    if (first > acc->distinct || count > acc->distinct - first)
+        return DNAGPU_ERR_BAD_ARG;
+    if (count == 0 || (!keys && !counts))
+        return DNAGPU_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const u64 P = (u64)1 << acc->t.pbits;
+    if (acc->pre.empty()) {                        // the partitions' group offsets: the order of every window until the next add
+        std::vector<u32> occ((size_t)P);
+        HIP_TRY(hipMemcpyAsync(occ.data(), acc->t.occ, (size_t)P * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::vector<u64> pre((size_t)P + 1);
+        pre[0] = 0;
+        for (u64 p = 0; p < P; p++)
+            pre[p + 1] = pre[p] + occ[p];
+        if (pre[P] != acc->distinct) {
+            set_err("accumulator: %llu groups in the partitions, %llu counted", (unsigned long long)pre[P],
+                    (unsigned long long)acc->distinct);
+            return DNAGPU_ERR_INTERNAL;
+        }
+        u64 *dp = nullptr;
+        RC_TRY(pool_alloc_t(ctx, (size_t)P, &dp));
+        hipError_t e = hipMemcpyAsync(dp, pre.data(), (size_t)P * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            pool_free(ctx, dp);
+            set_err("accumulator download: %s", hipGetErrorString(e));
+            return DNAGPU_ERR_HIP;
+        }
+        acc->pre.swap(pre);
+        acc->dev_pre = dp;
+    }
+    PoolScope ps(ctx);
+    const u64 BATCH = (u64)1 << 25;
+    u64 *sk = nullptr, *sc = nullptr;
+    if (keys)
+        RC_TRY(ps.alloc((size_t)std::min(count, BATCH), &sk));
+    if (counts)
+        RC_TRY(ps.alloc((size_t)std::min(count, BATCH), &sc));
+    for (u64 done = 0; done < count; done += BATCH) {
+        const u64 nb = std::min(BATCH, count - done), f = first + done;
+        // partitions [p_lo, p_hi) hold groups [f, f + nb): pre[p_lo] <= f < pre[p_lo + 1], pre[p_hi] >= f + nb
+        const u64 p_lo = (u64)(std::upper_bound(acc->pre.begin(), acc->pre.end(), f) - acc->pre.begin()) - 1;
+        const u64 p_hi = (u64)(std::lower_bound(acc->pre.begin(), acc->pre.end(), f + nb) - acc->pre.begin());
+        HIP_TRY(launch_acc_gather(acc->t.table, acc->t.occ, acc->dev_pre, p_lo, p_hi - p_lo, f, nb, sk, sc, st));
+        if (keys)
+            HIP_TRY(hipMemcpyAsync(keys + done, sk, nb * 8, hipMemcpyDeviceToHost, st));
+        if (counts)
+            HIP_TRY(hipMemcpyAsync(counts + done, sc, nb * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return DNAGPU_OK;
+    });
+}
+
+extern "C" void dnagpu_acc_free(dnagpu_ctx *ctx, dnagpu_acc *acc)
+{
+    if (!acc)
+        return;
+    if (ctx) {
+        acc_table_free(ctx, acc->t);
+        pool_free(ctx, acc->dev_pre);
+    }
+    delete acc;
 }
 
 // ------------------------------------------------------------------------------------------------

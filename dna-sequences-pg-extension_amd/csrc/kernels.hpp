@@ -167,6 +167,27 @@ hipError_t launch_merge_insert(const u64 *keys, const u32 *counts, u64 n, u64 *t
 hipError_t launch_merge_compact(const u64 *tkeys, const u32 *tcnt, u64 t_slots, u64 *out_keys, u32 *out_counts,
                                 unsigned long long *cursor, hipStream_t s);
 
+// ---- the k-mer accumulator (acc_kernels.hip): P = 2^pbits partitions of ACC_SLOTS 16-byte {key, u64 count} slots (count 0 =
+// empty), occ[p] = occupied slots of partition p.  bin: every group of a histogram (count-0 padding skipped) into bins[p] of
+// bin_cap 16-byte entries, cursor[p] (zeroed by the caller) = arrivals (entries past bin_cap are dropped, counted).
+// bin_stats: stats[0] = max(occ + cursor), stats[1] = max(cursor) (stats zeroed by the caller).  merge: one workgroup per
+// partition with arrivals; commit = 0 only counts the new keys (stats[0] = max(occ + new), stats[2..3] = sum of new as
+// u64), commit = 1 adds the bins in LDS and writes the partitions back (stats[2..3] = new keys; stats[1] != 0: a partition
+// ran full).  split: the table of 2^old_bits partitions into one of 2^new_bits.  gather: groups [first, first + count) of
+// the partition-order view (pre[p] = groups before partition p) of partitions p_lo .. p_lo + n_parts - 1.
+constexpr int ACC_SLOTS = 4096;
+hipError_t launch_acc_bin(const u64 *keys, const u32 *counts, u64 n, int pbits, u32 *cursor, u64 *bins, u32 bin_cap,
+                          hipStream_t s);
+hipError_t launch_acc_bin_stats(const u32 *occ, const u32 *cursor, u64 P, u32 *stats, hipStream_t s);
+hipError_t launch_acc_merge(u64 *table, u32 *occ, u64 P, const u32 *cursor, const u64 *bins, u32 bin_cap, int commit, u32 *stats,
+                            hipStream_t s);
+hipError_t launch_acc_split(const u64 *old_table, const u32 *old_occ, int old_bits, u64 *new_table, u32 *new_occ, int new_bits,
+                            u32 *stats, hipStream_t s);
+// res3[0] += sum(count), res3[1] += #(count == 1), res3[2] += sum(pair_mix(key, count)); zero it first
+hipError_t launch_acc_summary(const u64 *table, const u32 *occ, u64 P, u64 *res3, hipStream_t s);
+hipError_t launch_acc_gather(const u64 *table, const u32 *occ, const u64 *pre, u64 p_lo, u64 n_parts, u64 first, u64 count,
+                             u64 *out_keys, u64 *out_counts, hipStream_t s);
+
 // ---- a table of sequences in one packed stream (extract_kernels.hip)
 // marks: bit b set where a sequence starts at base b (starts[1 .. n_seqs - 1]; the buffer is zeroed here)
 hipError_t launch_batch_marks(const u64 *starts, u64 n_seqs, u32 *marks, u64 n_mark_words, hipStream_t s);

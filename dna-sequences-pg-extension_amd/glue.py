@@ -75,6 +75,20 @@ def lib():
         L.dna_glue_shutdown.restype = None
         L.dna_glue_set_gpus.restype = None
         L.dna_glue_set_gpus.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_int]
+        L.count_kmers_agg_begin.restype = vp
+        L.count_kmers_agg_begin.argtypes = [C.c_int]
+        L.count_kmers_agg_add.restype = C.c_bool
+        L.count_kmers_agg_add.argtypes = [vp, vp]
+        L.count_kmers_agg_next.restype = C.c_bool
+        L.count_kmers_agg_next.argtypes = [vp, C.POINTER(_Kmer), C.POINTER(C.c_int64)]
+        L.count_kmers_agg_failed.restype = C.c_bool
+        L.count_kmers_agg_failed.argtypes = [vp]
+        L.count_kmers_agg_totals.restype = None
+        L.count_kmers_agg_totals.argtypes = [vp] + [C.POINTER(C.c_int64)] * 3
+        L.count_kmers_agg_end.restype = None
+        L.count_kmers_agg_end.argtypes = [vp]
+        L.dna_glue_set_agg_flush_bases.restype = None
+        L.dna_glue_set_agg_flush_bases.argtypes = [C.c_uint64]
         _LIB = L
     return _LIB
 
@@ -243,3 +257,33 @@ def count_kmers(d, k):
     lib().count_kmers_totals(c, C.byref(t), C.byref(dd), C.byref(u))
     lib().count_kmers_end(c)
     return rows, (t.value, dd.value, u.value)
+
+
+def set_agg_flush_bases(n):
+    """bases per batch of count_kmers_agg (dna_glue_set_agg_flush_bases; default 2^30)"""
+    lib().dna_glue_set_agg_flush_bases(int(n))
+
+
+def count_kmers_agg(rows, k):
+    """SELECT k.kmer, count(*) FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS k(kmer) GROUP BY k.kmer
+    (test.sql:140-150) through the aggregate: rows = the table's `dna` values (or their text)
+    -> ([(kmer, count)...], (total, distinct, unique))"""
+    a = lib().count_kmers_agg_begin(k)
+    if not a:
+        raise _err()
+    try:
+        for r in rows:
+            if isinstance(r, str):
+                r = dna(r)
+            if not lib().count_kmers_agg_add(a, r.p):
+                raise _err()
+        out, km, cnt = [], _Kmer(), C.c_int64()
+        while lib().count_kmers_agg_next(a, C.byref(km), C.byref(cnt)):
+            out.append((kmer(c=_Kmer(km.length, km.bit_sequence)), cnt.value))
+        if lib().count_kmers_agg_failed(a):
+            raise _err()
+        t, dd, u = C.c_int64(), C.c_int64(), C.c_int64()
+        lib().count_kmers_agg_totals(a, C.byref(t), C.byref(dd), C.byref(u))
+        return out, (t.value, dd.value, u.value)
+    finally:
+        lib().count_kmers_agg_end(a)

@@ -637,3 +637,193 @@ void count_kmers_end(CountKmers *c)
     free(c->counts);
     free(c);
 }
+
+/* ------------------------------------------------------------------ the count over a TABLE of rows as an aggregate */
+
+static uint64_t g_agg_flush_bases = (uint64_t)1 << 30;
+
+void dna_glue_set_agg_flush_bases(uint64_t n) { g_agg_flush_bases = n ? n : 1; }
+
+struct CountKmersAgg {
+    int k;
+    dnagpu_acc *acc;                             /* created on the first flush (the GPU context is lazy) */
+    uint64_t *words, n_bases, cap_words;         /* the batch: rows back to back as one packed stream */
+    uint64_t *starts, n_seqs, cap_seqs;          /* starts[0 .. n_seqs] */
+    bool finished, failed;
+    uint64_t distinct, total, unique;
+    uint64_t next, win_first, win_count;
+    uint64_t *keys, *counts;
+};
+
+CountKmersAgg *count_kmers_agg_begin(int k)
+{
+    if (k < 1 || k > 32) {
+        ereport_error("%s", dnagpu_strerror(DNAGPU_ERR_INVALID_K));          /* dna.c:772-773 */
+        return NULL;
+    }
+    CountKmersAgg *a = (CountKmersAgg *)calloc(1, sizeof *a);
+    if (!a) {
+        ereport_error("out of memory");
+        return NULL;
+    }
+    a->k = k;
+    return a;
+}
+
+/* n bases of src (packed, base 0 at bit 0) onto dst from base `at`; dst's bits from `at` on are zero and dst has room for
+ * ceil((at + n) / 32) + 1 words */
+static void append_bases(uint64_t *dst, uint64_t at, const uint64_t *src, uint64_t n)
+{
+    const unsigned sh = (unsigned)(at & 31) * 2;
+    const uint64_t w = at >> 5, nw = (n + 31) / 32;
+    for (uint64_t i = 0; i < nw; i++) {
+        uint64_t v = src[i];
+        if (i == nw - 1 && (n & 31))
+            v &= ((uint64_t)1 << (2 * (n & 31))) - 1;                      /* nothing behind the row's last base */
+        if (sh == 0) {
+            dst[w + i] = v;
+        } else {
+            dst[w + i] |= v << sh;
+            dst[w + i + 1] = v >> (64 - sh);
+        }
+    }
+}
+
+static bool agg_grow(void **p, uint64_t *cap, uint64_t need)
+{
+    if (need <= *cap)
+        return true;
+    uint64_t c = *cap ? *cap : 1024;
+    while (c < need)
+        c *= 2;
+    void *q = realloc(*p, (size_t)c * sizeof(uint64_t));
+    if (!q) {
+        ereport_error("out of memory");
+        return false;
+    }
+    *p = q;
+    *cap = c;
+    return true;
+}
+
+/* the batch so far: counted, added into the accumulator, emptied */
+static bool agg_flush(CountKmersAgg *a)
+{
+    bool ok = true;
+    if (a->n_bases > 0) {
+        dnagpu_dna *d = NULL;
+        dnagpu_hist *h = NULL;
+        ok = ctx() != NULL && (a->acc || gpu_ok(dnagpu_acc_create(g_ctx, a->k, &a->acc))) &&
+             gpu_ok(dnagpu_dna_upload(g_ctx, a->words, a->n_bases, &d)) &&
+             gpu_ok(dnagpu_count_kmers_batch(g_ctx, d, a->starts, a->n_seqs, a->k, &h)) &&
+             gpu_ok(dnagpu_acc_add(g_ctx, a->acc, h));
+        if (h)
+            dnagpu_hist_free(g_ctx, h);
+        if (d)
+            dnagpu_dna_free(g_ctx, d);
+    }
+    a->n_bases = 0;
+    a->n_seqs = 0;
+    return ok;
+}
+
+bool count_kmers_agg_add(CountKmersAgg *a, const Dna *row)
+{
+    if (a->finished || a->failed) {
+        ereport_error("count_kmers_agg: row added after the aggregate finished or failed");
+        return false;
+    }
+    const uint64_t len = row->length;
+    if (a->n_seqs > 0 && a->n_bases + len > g_agg_flush_bases && !agg_flush(a)) {   /* a long row: a batch of its own */
+        a->failed = true;
+        return false;
+    }
+    if (!agg_grow((void **)&a->words, &a->cap_words, (a->n_bases + len + 31) / 32 + 1) ||
+        !agg_grow((void **)&a->starts, &a->cap_seqs, a->n_seqs + 2)) {
+        a->failed = true;
+        return false;
+    }
+    a->starts[0] = 0;
+    if (len)
+        append_bases(a->words, a->n_bases, row->bit_sequence, len);
+    a->n_bases += len;
+    a->starts[++a->n_seqs] = a->n_bases;
+    if (a->n_bases >= g_agg_flush_bases && !agg_flush(a)) {
+        a->failed = true;
+        return false;
+    }
+    return true;
+}
+
+/* FINALFUNC's first step: the last batch, then the totals over the accumulated groups */
+static bool agg_finish(CountKmersAgg *a)
+{
+    if (a->finished)
+        return true;
+    if (!agg_flush(a))
+        return false;
+    if (a->acc) {
+        uint64_t t = 0, u = 0, checksum;
+        if (!gpu_ok(dnagpu_acc_summary(g_ctx, a->acc, &t, &u, &checksum)))
+            return false;
+        a->total = t;
+        a->unique = u;
+        a->distinct = dnagpu_acc_distinct(a->acc);
+    }
+    a->keys = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)CK_WINDOW);
+    a->counts = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)CK_WINDOW);
+    if (!a->keys || !a->counts) {
+        ereport_error("out of memory");
+        return false;
+    }
+    a->finished = true;
+    return true;
+}
+
+bool count_kmers_agg_next(CountKmersAgg *a, Kmer *kmer, int64_t *count)
+{
+    if (a->failed)
+        return false;
+    if (!agg_finish(a)) {
+        a->failed = true;
+        return false;
+    }
+    if (a->next >= a->distinct)
+        return false;
+    if (a->next >= a->win_first + a->win_count) {
+        uint64_t n = a->distinct - a->next < CK_WINDOW ? a->distinct - a->next : CK_WINDOW;
+        if (!gpu_ok(dnagpu_acc_download(g_ctx, a->acc, a->next, n, a->keys, a->counts))) {
+            a->failed = true;
+            return false;
+        }
+        a->win_first = a->next;
+        a->win_count = n;
+    }
+    kmer->length = a->k;
+    kmer->bit_sequence = a->keys[a->next - a->win_first];
+    *count = (int64_t)a->counts[a->next - a->win_first];
+    a->next++;
+    return true;
+}
+
+bool count_kmers_agg_failed(const CountKmersAgg *a) { return a->failed; }
+
+void count_kmers_agg_totals(const CountKmersAgg *a, int64_t *total, int64_t *distinct, int64_t *unique)
+{
+    if (total) *total = (int64_t)a->total;
+    if (distinct) *distinct = (int64_t)a->distinct;
+    if (unique) *unique = (int64_t)a->unique;
+}
+
+void count_kmers_agg_end(CountKmersAgg *a)
+{
+    if (!a)
+        return;
+    if (a->acc)
+        dnagpu_acc_free(g_ctx, a->acc);
+    free(a->words);
+    free(a->starts);
+    free(a->keys);
+    free(a->counts);
+    free(a);
+}

@@ -104,6 +104,24 @@ bool count_kmers_next(CountKmers *c, Kmer *kmer, int64_t *count);
 void count_kmers_totals(const CountKmers *c, int64_t *total, int64_t *distinct, int64_t *unique);
 void count_kmers_end(CountKmers *c);
 
+/* ---- SELECT k.kmer, count(*) FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS k(kmer) GROUP BY k.kmer
+ * (test.sql:140-150) as an aggregate over the table's rows ----
+ * begin = the aggregate's first call (NULL + dna_glue_errmsg() on a bad k: dna.c:773); add = SFUNC, one call per row: the
+ * row's bases are appended on the host to one packed stream at any 2-bit offset, and a batch is counted on the GPU
+ * (dnagpu_count_kmers_batch) and added into a device-resident accumulator of 64-bit counts (dnagpu_acc_add) whenever it
+ * reaches the flush size -- a row longer than that is a batch of its own; next = FINALFUNC rows (the first call flushes the
+ * rest; false = done, or an ERROR: count_kmers_agg_failed); totals = sum(count), count(*), count(*) FILTER (WHERE count = 1),
+ * valid once next has been called.  No limit on the table's size: 2^32 - 1 bases apply per batch only. */
+typedef struct CountKmersAgg CountKmersAgg;
+CountKmersAgg *count_kmers_agg_begin(int k);
+bool count_kmers_agg_add(CountKmersAgg *a, const Dna *row);
+bool count_kmers_agg_next(CountKmersAgg *a, Kmer *kmer, int64_t *count);
+bool count_kmers_agg_failed(const CountKmersAgg *a);
+void count_kmers_agg_totals(const CountKmersAgg *a, int64_t *total, int64_t *distinct, int64_t *unique);
+void count_kmers_agg_end(CountKmersAgg *a);
+/* bases per batch (default 2^30); tests use small values to force many batches */
+void dna_glue_set_agg_flush_bases(uint64_t n);
+
 #ifdef __cplusplus
 }
 #endif

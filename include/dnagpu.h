@@ -197,7 +197,7 @@ int dnagpu_hist_is_sorted(const dnagpu_hist *h);
  * every sequence's own generate_kmers: no k-mer spans two sequences, a sequence shorter than k has none (the 64-bit
  * restatement of dna.c:781).  Same result object as dnagpu_count_kmers_unordered (group order unspecified;
  * dnagpu_hist_is_sorted tells); dnagpu_hist_total = the rows of the table.  At most 2^32 - 1 bases per call: callers
- * that stream larger tables count batch by batch and add the histograms up (dnagpu_hist_merge). */
+ * that stream larger tables count batch by batch and add the histograms up (dnagpu_acc_add: 64-bit counts, no total limit). */
 int dnagpu_count_kmers_batch(dnagpu_ctx *ctx, const dnagpu_dna *dna, const uint64_t *seq_starts, uint64_t n_seqs,
                              int k, dnagpu_hist **out);
 /* The same table kept RESIDENT: dnagpu_dna_set_sequences validates seq_starts (as above), uploads them and builds the
@@ -258,6 +258,33 @@ int dnagpu_hist_summary(dnagpu_ctx *ctx, const dnagpu_hist *h, uint64_t *total, 
  * any.  A utility (one random probe of a device-memory table per group), not part of the streaming path. */
 int dnagpu_hist_merge(dnagpu_ctx *ctx, const dnagpu_hist *a, const dnagpu_hist *b, dnagpu_hist **out);
 void dnagpu_hist_free(dnagpu_ctx *ctx, dnagpu_hist *h);
+
+/* ---- k-mer accumulator: GROUP BY over a table of any size, batch by batch (the HashAggregate of test.sql:140-150 with
+ * its int8 counts) ---------------------------------------------------------------------------------------------------
+ * An accumulator stays in device memory and adds histograms into 64-bit counts; no total limit.  It belongs to one context
+ * and its buffers come from that context's pool (the stream rule above).
+ * dnagpu_acc_create: DNAGPU_ERR_INVALID_K unless 1 <= k <= 32; an empty accumulator holds no device memory yet.
+ * dnagpu_acc_add adds the groups of h (equal keys: counts summed, 64-bit).  Any histogram: ordered or unordered, one part or
+ *   several, from every count entry point and dnagpu_hist_merge; count-0 padding slots are skipped and the all-ones key
+ *   (32 G's) counts like any other.  h is left as it is and may be freed right after the call; adding the same histogram
+ *   twice doubles every count.  DNAGPU_ERR_BAD_ARG when h records a k other than the accumulator's (a histogram that
+ *   records none -- the multi-GPU counts -- is accepted: dnagpu_hist_merge's rule).  Every error (bad k, OOM while the
+ *   table grows, a HIP error before the merge) leaves the accumulator as it was: a larger table is built in new buffers and
+ *   takes over only when the add succeeds.  Cost: one streaming pass over the histogram and the partitions it touches,
+ *   not a random probe per group (DESIGN.md "accumulator").
+ * dnagpu_acc_distinct = count(*) over groups, dnagpu_acc_total = sum(count) (0 for NULL).
+ * dnagpu_acc_summary: total, unique = groups with count 1, checksum = wrapping sum of the (key, count) digest of
+ *   dnagpu_hist_summary over 64-bit counts -- an accumulator holding one histogram reports exactly that histogram's summary.
+ * dnagpu_acc_download: groups [first, first+count) into host arrays (either may be NULL).  The order is unspecified, as
+ *   GROUP BY's, but fixed until the next add: the windows of one pass tile the groups exactly once. */
+typedef struct dnagpu_acc dnagpu_acc;
+int dnagpu_acc_create(dnagpu_ctx *ctx, int k, dnagpu_acc **out);
+int dnagpu_acc_add(dnagpu_ctx *ctx, dnagpu_acc *acc, const dnagpu_hist *h);
+uint64_t dnagpu_acc_distinct(const dnagpu_acc *acc);
+uint64_t dnagpu_acc_total(const dnagpu_acc *acc);
+int dnagpu_acc_summary(dnagpu_ctx *ctx, const dnagpu_acc *acc, uint64_t *total, uint64_t *unique, uint64_t *checksum);
+int dnagpu_acc_download(dnagpu_ctx *ctx, dnagpu_acc *acc, uint64_t first, uint64_t count, uint64_t *keys, uint64_t *counts);
+void dnagpu_acc_free(dnagpu_ctx *ctx, dnagpu_acc *acc);
 
 /* ---- multi-GPU sharding of the count (one process per GPU; the exchange itself is the
  * caller's collective, e.g. RCCL all-to-all) -------------------------------------------------
