@@ -1,0 +1,259 @@
+// host_common.hpp -- what the host files of the C-ABI (dnagpu_api.hip, count_host.hip, sk_host.hip, multi_host.hip) share
+// (internal, like kernels.hpp): the error macros, the context / dna / histogram objects, the buffer pool, and the few
+// functions one of the files calls in another.  Declarations only, plus the templates and macros that must be visible;
+// the definitions are in dnagpu_api.hip unless a section says otherwise.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <vector>
+
+#include "../../include/dnagpu.h"
+#include "kernels.hpp"
+
+namespace dnagpu {
+void set_err(const char *fmt, ...);
+
+#ifdef DNAGPU_STAMPS
+inline const char *diag_env(const char *name) { return getenv(name); }
+#else
+inline const char *diag_env(const char *) { return nullptr; }
+#endif
+
+#define HIP_TRY(expr)                                                                        \
+    do {                                                                                     \
+        hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess) {                                                              \
+            set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+            return e_ == hipErrorOutOfMemory ? DNAGPU_ERR_OOM : DNAGPU_ERR_HIP;              \
+        }                                                                                    \
+    } while (0)
+
+#define RC_TRY(expr)           \
+    do {                       \
+        int rc_ = (expr);      \
+        if (rc_ != DNAGPU_OK)  \
+            return rc_;        \
+    } while (0)
+
+// No C++ exception may cross the C-ABI (a PostgreSQL backend would die in std::terminate): every
+// extern "C" entry point that can allocate on the host (pool bookkeeping, event lists, node lists) runs its
+// body inside this guard.
+template <typename F>
+int guarded(F &&body) noexcept
+{
+    try {
+        return body();
+    } catch (const std::bad_alloc &) {
+        set_err("host allocation failed");
+        return DNAGPU_ERR_OOM;
+    } catch (...) {
+        set_err("unexpected C++ exception");
+        return DNAGPU_ERR_INTERNAL;
+    }
+}
+
+// ---------------------------------------------------------------- context + device buffer pool
+struct PoolBlock {
+    void *ptr;
+    size_t size;
+    bool in_use;
+    size_t guard_at = 0;      // DNAGPU_DEBUG_GUARD_POOL: offset of the block's guard band (0 = none)
+};
+constexpr size_t POOL_GUARD = 256;               // bytes of 0xA5 behind the bytes a caller asked for
+
+constexpr size_t MAILBOX_BYTES = (size_t)1 << 20;
+
+}  // namespace dnagpu
+using dnagpu::u32;
+using dnagpu::u64;
+
+struct dnagpu_ctx {
+    int device;
+    hipStream_t stream;
+    std::vector<dnagpu::PoolBlock> pool;
+    bool profiling;
+    dnagpu_phase_times last_times;
+    // per-call event list (profiling)
+    std::vector<hipEvent_t> ev;
+    std::vector<const char *> ev_names;
+    // pinned, device-visible host words: small results (totals, per-group counts) land here without a
+    // staging copy; read after hipStreamSynchronize
+    u64 *mailbox;
+    u64 mailbox_seq = 0;      // sequence number of the last flagged read-back (read_back)
+    unsigned debug_flags;     // DNAGPU_DEBUG_*
+};
+
+struct dnagpu_dna {
+    u64 *words;
+    u64 n_words;
+    u64 n_bases;
+    bool owned;
+    // a TABLE of sequences (dnagpu_dna_set_sequences): where every sequence starts, resident beside the packed stream
+    u64 *seq_starts = nullptr;    // n_seqs + 1 offsets (pool memory)
+    u32 *seq_marks = nullptr;     // one bit per base, set where a sequence starts (pool memory)
+    u64 n_seqs = 0, n_mark_words = 0;
+};
+
+struct dnagpu_hist {
+    u64 *keys = nullptr;        // n_distinct groups, dense; stored leaf by leaf in completion order
+    u32 *counts = nullptr;      // a count never exceeds the 2^32 - 1 rows of one call: 4 bytes in HBM, widened on download
+    u64 n_distinct = 0;
+    u64 total = 0;
+    // segment directory: leaf l (leaves are in ascending key order) = seg_cnt[l] groups at seg_off[l]
+    u64 *seg_off = nullptr;
+    u32 *seg_cnt = nullptr;
+    u32 *seg_pre = nullptr;     // exclusive scan of seg_cnt, built on first ordered download
+    u32 n_segs = 0;
+    bool sorted = true;         // the segments are consecutive key ranges (true unless the super-k-mer engine made them)
+    u64 extent = 0;             // slots of keys / counts in use: n_distinct, or more when an unordered histogram holds count-0 padding
+                                // between segments (0 = n_distinct)
+    // A histogram made of several (dnagpu_hist_parts): the pipelined record exchange counts an owner's buckets group by
+    // group, each group into arrays of its own.  The head then owns no arrays (keys == nullptr); n_distinct / total /
+    // extent are the sums over the parts, the groups of part i come before those of part i + 1 in every ordered read.
+    std::vector<dnagpu_hist *> parts;
+    int k = 0;        // the k the rows were counted with (0 = unknown): dnagpu_hist_merge refuses two different ones
+};
+using HistPtr = std::unique_ptr<dnagpu_hist>;
+
+namespace dnagpu {
+// Up to 32 bytes from the host into device memory as a kernel argument: see Poke32 (dnagpu_api.hip)
+hipError_t poke(void *dst, const void *src, size_t bytes, hipStream_t st);
+// `bytes` of device memory to the host through the pinned mailbox; waits for the stream (dnagpu_api.hip: mailbox_kernel)
+int read_back(dnagpu_ctx *ctx, void *host, const void *dev, size_t bytes);
+
+int pool_alloc(dnagpu_ctx *ctx, size_t bytes, void **out);
+// Buffers go back to the pool while kernels that use them may still be queued: every later user is
+// queued on the same stream, behind them.
+void pool_free(dnagpu_ctx *ctx, void *p);
+
+template <typename T>
+int pool_alloc_t(dnagpu_ctx *ctx, size_t n, T **out)
+{
+    void *p = nullptr;
+    int rc = pool_alloc(ctx, n * sizeof(T), &p);
+    *out = static_cast<T *>(p);
+    return rc;
+}
+
+// frees a set of pool buffers at scope exit
+struct PoolScope {
+    dnagpu_ctx *ctx;
+    std::vector<void *> ptrs;
+    explicit PoolScope(dnagpu_ctx *c) : ctx(c) {}
+    ~PoolScope()
+    {
+        for (void *p : ptrs)
+            pool_free(ctx, p);
+    }
+    template <typename T>
+    int alloc(size_t n, T **out)
+    {
+        int rc = pool_alloc_t(ctx, n, out);
+        if (rc == DNAGPU_OK)
+            ptrs.push_back(*out);
+        return rc;
+    }
+    void release(void *p)   // hand ownership to the caller
+    {
+        ptrs.erase(std::remove(ptrs.begin(), ptrs.end(), p), ptrs.end());
+    }
+    void free_now(void *p)
+    {
+        release(p);
+        pool_free(ctx, p);
+    }
+};
+
+// An empty histogram of `total` rows, owned by the caller until it hands it out (release()); null when the host is out
+// of memory.
+HistPtr hist_new(u64 total, bool sorted = true);
+// h takes the groups and their segment directory over from the scope that allocated them.
+void hist_adopt(PoolScope &ps, dnagpu_hist *h, u64 *keys, u32 *counts, u64 *seg_off, u32 *seg_cnt, u32 n_segs, u64 n_distinct,
+                bool sorted, u64 extent);
+// hist_adopt for n_groups groups that are ONE segment: seg_off[0] = 0 and seg_cnt[0] = n_groups, twelve bytes of one pool
+// block written by one poke.  (seg_cnt points into the block of seg_off: freeing it finds no block of its own and does
+// nothing.)  Waits for the stream.
+int hist_adopt_one_segment(dnagpu_ctx *ctx, PoolScope &ps, dnagpu_hist *h, u64 *keys, u32 *counts, u64 n_groups, bool sorted);
+
+// ---------------------------------------------------------------- profiling helpers
+void prof_begin(dnagpu_ctx *ctx);
+void prof_mark(dnagpu_ctx *ctx, const char *name);
+void prof_end(dnagpu_ctx *ctx);      // names[i] labels the interval [mark i, mark i+1)
+
+// ---------------------------------------------------------------- dna
+inline u64 words_for(u64 n_bases) { return (n_bases + 31) / 32; }
+// validates [first, first+count) against the row count of generate_kmers(dna, k)
+int check_range(const dnagpu_dna *dna, int k, u64 first, u64 count);
+
+// ---------------------------------------------------------------- count_host.hip
+struct TreeResult {
+    Node *nodes;      // final node list (leaves, or the children of a forced level)
+    u32 n_nodes;
+    u32 n_big;        // leaves that sort more than LEAF_CAP_SMALL keys among them
+    u32 n_small;      // leaves that sort up to LEAF_CAP_SMALL keys
+    u32 n_tiny;       // leaves that sort at most LEAF_CAP_TINY keys (the rest: single-key or empty nodes)
+    u64 n_keys;       // keys in the tree (== n unless an owner filter dropped some at the dna root)
+    u64 *buf0;
+    u64 *buf1;        // may be null if never needed
+};
+
+// Runs levels until every node is a leaf (force_bits == 0), or exactly one forced level of
+// `force_bits` bits on the root (force_bits > 0).  dna != null: root over the packed sequence
+// (keys land in buf0, allocated here); else root over keys_in (used as buf0).
+// init_nodes != null: the levels start at `start_level` from that node list over keys_in (pool memory of `ps`; the
+// nodes' key ranges need not share key bits: the super-k-mer engine enters here with its bucket nodes)
+int run_tree(dnagpu_ctx *ctx, PoolScope &ps, const dnagpu_dna *dna, u64 first, u64 n, int k,
+             u64 *keys_in, int force_bits, TreeResult *res, int fixed_bits = 0, u64 fixed_prefix = 0,
+             bool single_level = true, u32 flt_lo = 0, u32 flt_span = ~0u, u32 flt_tb = 0,
+             Node *init_nodes = nullptr, u32 init_n = 0, int start_level = 0);
+// short k-mers (2k <= dense_max_bits()) of enough rows to pay for the table passes and for compacting the table: no tree
+bool dense_pays(u64 n, int k);
+
+// ---------------------------------------------------------------- sk_host.hip
+// DNAGPU_SK_SKEWED: a bucket is too heavy (low-complexity input): the caller counts with the ordinary tree
+// instead, which has the skew paths.
+constexpr int DNAGPU_SK_SKEWED = -1;
+// geometry of a count of n rows: final buckets of ~SK_LEAF_MEAN k-mers = 16 per mid bucket; mid buckets = c0n coarse x 2^b1.
+// A multi-GPU count derives it from the GLOBAL row count on every rank (the digits are part of the records).
+struct SkGeom {
+    int b1, r0bits;
+    u32 c0n;
+    u64 mid_limit;
+};
+SkGeom sk_geometry(const dnagpu_ctx *ctx, u64 n, int k);
+
+// The rows a record count sweeps: [first, first + n) of dna's generate_kmers rows.  marks != null: a count over a TABLE
+// of sequences -- one bit per base of the packed stream, set where a sequence starts (n_mark_words words, device memory);
+// level 0 makes no record of rows that reach across a mark.
+struct SkRows {
+    const dnagpu_dna *dna;
+    u64 first, n;
+    const u32 *marks;
+    u64 n_mark_words;
+};
+
+// rows.n = rows swept; n_kmers_expected = the k-mers they hold (fewer over a table of sequences: rows.marks)
+int count_sk(dnagpu_ctx *ctx, const SkRows &rows, int k, dnagpu_hist *h, u64 n_kmers_expected);
+// the records a landing buffer of the buckets blen[] should have room for, so that level 1 can run without its histogram
+u64 sk_received_cap(const std::vector<u64> &blen, u32 n_coarse, const SkGeom &g);
+// rec0 (pool memory; this takes it over and returns it to the pool) = the records of the coarse buckets, bucket after
+// bucket: bucket d = blen[d] records at boff[d] (n_coarse = 2^r0bits entries).  Everything queued on ctx->stream
+// behind whatever filled rec0.
+int count_sk_received(dnagpu_ctx *ctx, void *rec0, const std::vector<u64> &boff, const std::vector<u64> &blen, const SkGeom &g,
+                      int k, dnagpu_hist *h, u64 rec0_cap = 0);
+}  // namespace dnagpu
+
+struct dnagpu_records {
+    void *recs = nullptr;       // pool memory: 16 bytes per record, bucket after bucket
+    std::vector<u64> off;       // n_buckets + 1 offsets (records)
+};

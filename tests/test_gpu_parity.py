@@ -647,7 +647,7 @@ def test_count_unordered_superkmers(ctx, pkg, n, k, first):
     assert h.total == len(keys)
     check_hist_unordered(h, ok, oc, f"unordered n={n} k={k} first={first}")
     h.free()
-    rows = len(keys)                                 # the default choice of engine (dnagpu_api.hip: sk_is_default)
+    rows = len(keys)                                 # the default choice of engine (count_host.hip: sk_is_default)
     if rows >= (1 << 25) and (k >= 23 or (k == 22 and rows <= (1 << 31)) or (k == 21 and rows <= (1 << 29)) or
                               (k == 20 and rows <= (1 << 28))):
         h = ctx.count_kmers_unordered(d, k, first=first)
@@ -1251,7 +1251,7 @@ def sk_lmax(k):
 
 
 def sk_chunk_rows(n_rows):
-    """level 0's chunk length: the exact pair's (4096 chunks) and the slab sweep's (1024) formulas in dnagpu_api.hip"""
+    """level 0's chunk length: the exact pair's (4096 chunks) and the slab sweep's (1024) formulas in sk_host.hip (sk_level0_begin)"""
     return tuple((max(4 * SK_ROUND_ROWS, (n_rows + c - 1) // c) + SK_ROUND_ROWS - 1) // SK_ROUND_ROWS * SK_ROUND_ROWS
                  for c in (4096, 1024))
 
@@ -1706,6 +1706,50 @@ def test_table_count_leaves_no_state_on_the_context(pkg):
                             h.free()
                 finally:
                     c.set_debug(0)
+        d.free()
+        d1.free()
+
+
+def test_refused_table_count_leaves_no_state_on_the_context(pkg):
+    """on one context, in this order: a table count through the forced record engine (several sequences), a table count that
+    is refused (bad seq_starts), then a plain unordered count and the records (dnagpu_sk_records, counted by
+    dnagpu_count_records) of ONE long sequence, the engine still forced: both the oracle's groups -- the marks are an input
+    of the table's own call and of no other"""
+    words, starts = repeat_rich_table(0x57A7F, 9_000, 60, 250, {x: 1 for x in RR_KINDS})
+    n = int(starts[-1])
+    n1 = 1_000_003
+    w1 = orc.synth_words_repeat(0x0DF, n1, 1000)
+    with pkg.Context(0) as c:
+        d = c.upload(words, n)
+        d1 = c.upload(w1, n1)
+        for k in (31, 21):
+            tk, tc = orc.count_keys(orc.generate_kmers_table(words, starts, k))
+            pk, pc = orc.count_kmers(w1, n1, k)
+            rows1 = n1 - k + 1
+            c.set_debug(pkg.DEBUG_FORCE_SUPERKMER)
+            try:
+                h = c.count_kmers_batch(d, starts, k)
+                assert not h.is_sorted                    # (the record engine counted it)
+                check_hist_unordered(h, tk, tc, f"forced table count, k={k}")
+                h.free()
+                bad = starts.copy()
+                bad[len(bad) // 2] = bad[len(bad) // 2 - 1] - np.uint64(1)      # (not ascending)
+                with pytest.raises(pkg.DnaGpuError) as ei:
+                    c.count_kmers_batch(d, bad, k)
+                assert ei.value.code == 5                 # DNAGPU_ERR_BAD_ARG
+                h = c.count_kmers_unordered(d1, k)
+                assert not h.is_sorted
+                check_hist_unordered(h, pk, pc, f"plain count after a refused table count, k={k}")
+                h.free()
+                r = c.sk_records(d1, k, 0, rows1, rows1)
+                pieces = [(r.device_ptr + 16 * int(r.offsets[b]), int(r.offsets[b + 1] - r.offsets[b]), b) for b in range(r.n_buckets)]
+                h = c.count_records(pieces, k, rows1)
+                assert h.total == rows1
+                check_hist_unordered(h, pk, pc, f"records after a refused table count, k={k}")
+                h.free()
+                r.free()
+            finally:
+                c.set_debug(0)
         d.free()
         d1.free()
 
