@@ -16,6 +16,7 @@ from .binding import (  # noqa: F401
     DEBUG_HEAVY_EXPAND,
     DEBUG_NO_SLAB0,
     DEBUG_NO_SPEC1,
+    DEBUG_POISON_POOL,
     DEBUG_SLAB0,
     DEBUG_SLAB0_OVERFLOW,
     DEBUG_SAMPLE1,

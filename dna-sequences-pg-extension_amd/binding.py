@@ -351,14 +351,17 @@ class Hist:
     def is_sorted(self):
         return bool(lib().dnagpu_hist_is_sorted(self.h))
 
-    def download(self, first=0, count=None):
+    def download(self, first=0, count=None, want_keys=True, want_counts=True):
+        """groups [first, first+count) of the read order as (keys, counts) uint64 arrays; an array not wanted is passed as
+        NULL and comes back as None"""
         if count is None:
             count = self.distinct - first
-        keys = np.empty(max(count, 1), dtype=np.uint64)
-        counts = np.empty(max(count, 1), dtype=np.uint64)
-        _chk(lib().dnagpu_hist_download(self.ctx.h, self.h, first, count, keys.ctypes.data_as(u64p),
-                                        counts.ctypes.data_as(u64p)))
-        return keys[:count], counts[:count]
+        keys = np.empty(max(count, 1), dtype=np.uint64) if want_keys else None
+        counts = np.empty(max(count, 1), dtype=np.uint64) if want_counts else None
+        _chk(lib().dnagpu_hist_download(self.ctx.h, self.h, first, count,
+                                        keys.ctypes.data_as(u64p) if want_keys else None,
+                                        counts.ctypes.data_as(u64p) if want_counts else None))
+        return (keys[:count] if want_keys else None, counts[:count] if want_counts else None)
 
     def sorted_view_device(self, dev_keys, dev_counts, first=0, count=None):
         """ascending-key groups [first, first+count) into caller-owned device arrays of uint64"""
@@ -494,20 +497,28 @@ class Context:
         _chk(lib().dnagpu_dna_wrap(self.h, dev_ptr, n_words, n_bases, C.byref(h)))
         return Dna(self, h)
 
-    def pack(self, text):
-        """dna_in on the device: text (str/bytes of A/T/C/G) -> Dna"""
-        b = text.encode() if isinstance(text, str) else bytes(text)
+    def _pack(self, text, n_bases, on_device):
         h = C.c_void_p()
         pos, ch = C.c_uint64(), C.create_string_buffer(1)
-        rc = lib().dnagpu_dna_pack(self.h, b, len(b), 0, C.byref(h), C.byref(pos), ch)
+        rc = lib().dnagpu_dna_pack(self.h, text, n_bases, on_device, C.byref(h), C.byref(pos), ch)
         if rc == ERR_DNA_INVALID_CHAR:
             e = DnaGpuError(rc)
             e.message = f"{e.message}: {ch.raw.decode(errors='replace')}"
             e.bad_pos = pos.value
+            e.bad_char = ch.raw
             e.args = (e.message,)
             raise e
         _chk(rc)
         return Dna(self, h)
+
+    def pack(self, text):
+        """dna_in on the device: text (str/bytes of A/T/C/G) -> Dna"""
+        b = text.encode() if isinstance(text, str) else bytes(text)
+        return self._pack(b, len(b), 0)
+
+    def pack_device(self, dev_text, n_bases):
+        """the same from n_bases characters already in device memory (any byte alignment)"""
+        return self._pack(C.cast(C.c_void_p(dev_text), C.c_char_p), n_bases, 1)
 
     def unpack(self, dna, first=0, count=None):
         if count is None:
@@ -515,6 +526,24 @@ class Context:
         buf = C.create_string_buffer(max(count, 1))
         _chk(lib().dnagpu_dna_unpack(self.h, dna.h, first, count, buf, 0))
         return buf.raw[:count].decode()
+
+    def unpack_device(self, dna, first, count, dev_text):
+        """bases [first, first+count) as `count` characters into device memory (any byte alignment)"""
+        _chk(lib().dnagpu_dna_unpack(self.h, dna.h, first, count, dev_text, 1))
+
+    def from_wire_device(self, dev_wire, wire_bytes):
+        """dna_recv from a wire image in device memory (8-byte aligned) -> Dna"""
+        h = C.c_void_p()
+        _chk(lib().dnagpu_dna_from_wire(self.h, dev_wire, wire_bytes, 1, C.byref(h)))
+        return Dna(self, h)
+
+    def to_wire_device(self, dna, dev_wire, wire_cap):
+        """dna_send into device memory (8-byte aligned, wire_cap bytes of room)"""
+        _chk(lib().dnagpu_dna_to_wire(self.h, dna.h, dev_wire, wire_cap, 1))
+
+    def kmers_to_text_device(self, dev_keys, n, k, dev_text):
+        """n keys in device memory -> n records of k characters + NUL in device memory"""
+        _chk(lib().dnagpu_kmers_to_text(self.h, dev_keys, n, k, dev_text, 1))
 
     def from_wire(self, wire):
         """dna_recv on the device: the binary wire image (bytes) -> Dna"""
@@ -669,6 +698,15 @@ class Context:
     def buffer_free(self, ptr):
         lib().dnagpu_buffer_free(self.h, ptr)
 
+    def download_bytes(self, ptr, n):
+        out = np.empty(max(n, 1), dtype=np.uint8)
+        _chk(lib().dnagpu_buffer_download(self.h, ptr, n, out.ctypes.data))
+        return out[:n]
+
+    def upload_bytes(self, ptr, arr):
+        a = np.ascontiguousarray(arr, dtype=np.uint8)
+        _chk(lib().dnagpu_buffer_upload(self.h, ptr, a.ctypes.data, a.size))
+
     def download_u64(self, ptr, n):
         out = np.empty(max(n, 1), dtype=np.uint64)
         _chk(lib().dnagpu_buffer_download(self.h, ptr, n * 8, out.ctypes.data))
@@ -684,6 +722,14 @@ class Context:
         out = np.empty(max(k.size, 1), dtype=np.uint32)
         _chk(lib().dnagpu_kmer_hash(self.h, k.ctypes.data, k.size, out.ctypes.data, 0))
         return out[:k.size]
+
+    def kmer_hash_device(self, dev_keys, n, dev_out):
+        """n keys in device memory -> n uint32 hashes in device memory"""
+        _chk(lib().dnagpu_kmer_hash(self.h, dev_keys, n, dev_out, 1))
+
+    def kmer_match_device(self, dev_keys, n, k, flt, dev_flags):
+        """n keys in device memory -> n uint8 flags in device memory"""
+        _chk(lib().dnagpu_kmer_match(self.h, dev_keys, n, k, C.byref(flt.c), dev_flags, 1))
 
     def kmer_match(self, keys, k, flt):
         a = np.ascontiguousarray(keys, dtype=np.uint64)

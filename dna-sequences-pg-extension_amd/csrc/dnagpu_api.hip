@@ -728,7 +728,10 @@ extern "C" int dnagpu_dna_to_wire(dnagpu_ctx *ctx, const dnagpu_dna *dna, void *
     } else {
         HIP_TRY(hipMemcpyAsync(wire, hdr, 8, hipMemcpyHostToDevice, ctx->stream));
     }
-    HIP_TRY(launch_wire_swap(dna->words, wire_on_device ? dst : stage, nw, ~(u64)0, ctx->stream));
+    // (a wrapped view's last word may carry the caller's neighbouring data behind the last base: not part of the image)
+    const u64 last_mask = (dna->n_bases % 32) ? (((u64)1 << (2 * (dna->n_bases % 32))) - 1) : ~(u64)0;
+    // (the kernel masks what it stores, i.e. the swapped word: swapped mask)
+    HIP_TRY(launch_wire_swap(dna->words, wire_on_device ? dst : stage, nw, __builtin_bswap64(last_mask), ctx->stream));
     if (!wire_on_device && nw)
         HIP_TRY(hipMemcpyAsync(dst, stage, nw * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -458,7 +458,8 @@ __global__ __launch_bounds__(256) void unpack_kernel(const u64 *__restrict__ wor
     unsigned char buf[16];
 #pragma unroll
     for (int j = 0; j < 16; j++) {
-        u64 p = first + i0 + j;
+        // (positions from first + count on are not read: the word behind the window's last may not be the sequence's)
+        u64 p = first + (i0 + j < count ? i0 + j : count - 1);
         u32 code = (u32)(words[p >> 5] >> ((p & 31) * 2)) & 3;
         buf[j] = (unsigned char)((L >> (8 * code)) & 0xff);
     }

@@ -85,7 +85,10 @@ typedef struct dnagpu_dna dnagpu_dna;
  * itself: it is the hand-off of dna->bit_sequence / dna->length (dna.c:45-46). */
 int dnagpu_dna_upload(dnagpu_ctx *ctx, const uint64_t *words, uint64_t n_bases, dnagpu_dna **out);
 /* Wraps n_words packed words already in device memory (no copy; the caller keeps them alive and
- * unchanged until dnagpu_dna_free).  n_words >= ceil(n_bases/32). */
+ * unchanged until dnagpu_dna_free, which does not release them).  n_words >= ceil(n_bases/32).  The view may lie in the
+ * middle of the caller's own data: results never depend on the bits behind base n_bases - 1 (the rest of the last word,
+ * words [ceil(n_bases/32), n_words)) -- dnagpu_dna_to_wire clears them in the image -- and no word from n_words on is
+ * read. */
 int dnagpu_dna_wrap(dnagpu_ctx *ctx, const uint64_t *dev_words, uint64_t n_words, uint64_t n_bases,
                     dnagpu_dna **out);
 /* Synthetic sequence generated on the device: word w = splitmix64(seed + w) (i.i.d. uniform bases,
