@@ -28,6 +28,8 @@ from .binding import (  # noqa: F401
     Filter,
     Hist,
     Records,
+    SPECTRUM_MAX_BINS,
+    TOP_MAX,
     MULTI_AUTO,
     MULTI_COPY,
     MULTI_RCCL,

@@ -30,6 +30,9 @@ DEBUG_SLAB0 = 64
 DEBUG_NO_SLAB0 = 128
 DEBUG_SLAB0_OVERFLOW = 256
 DEBUG_SAMPLE1 = 512                   # level 1: regions from a sampled histogram whatever the coarse buckets look like
+SPECTRUM_MAX_BINS = 1 << 20
+TOP_MAX = 1 << 20
+U64_MAX = 2 ** 64 - 1
 
 
 def _env_debug():
@@ -164,6 +167,10 @@ def lib():
     L.dnagpu_acc_download.argtypes = [vp, vp, C.c_uint64, C.c_uint64, u64p, u64p]
     L.dnagpu_acc_free.argtypes = [vp, vp]
     L.dnagpu_acc_free.restype = None
+    for obj in ("hist", "acc"):
+        getattr(L, f"dnagpu_{obj}_spectrum").argtypes = [vp, vp, C.c_uint64, u64p]
+        getattr(L, f"dnagpu_{obj}_select").argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, u64p, C.c_int]
+        getattr(L, f"dnagpu_{obj}_top").argtypes = [vp, vp, C.c_uint64, vp, vp, u64p, C.c_int]
     L.dnagpu_partition_kmers.argtypes = [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(vp), u64p]
     L.dnagpu_buffer_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
     L.dnagpu_buffer_free.argtypes = [vp, vp]
@@ -312,7 +319,61 @@ class Records:
             self.h = None
 
 
-class Hist:
+class _CountQueries:
+    """the count-ordered queries Hist and Accumulator share (dnagpu_hist_* / dnagpu_acc_* spectrum, select, top)"""
+
+    _obj = None                       # "hist" / "acc"
+
+    def _q(self, name):
+        return getattr(lib(), f"dnagpu_{self._obj}_{name}")
+
+    def spectrum(self, n_bins):
+        """the k-mer spectrum: bins[c - 1] = groups with count c, bins[n_bins - 1] = groups with count >= n_bins"""
+        bins = np.zeros(max(int(n_bins), 1), dtype=np.uint64)
+        _chk(self._q("spectrum")(self.ctx.h, self.h, n_bins, bins.ctypes.data_as(u64p)))
+        return bins[:n_bins]
+
+    def select(self, min_count, max_count=U64_MAX, cap=None, on_device=False, out=None):
+        """GROUP BY kmer HAVING count(*) BETWEEN min_count AND max_count, order unspecified.
+        host: -> (keys, counts, n_matches): at most cap rows (cap=None: all of them -- two calls, the first with cap 0 sizes
+        the arrays).  on_device: the rows go to device arrays of cap uint64 each -- out=(dev_keys, dev_counts) (either may
+        be None) -> n_matches; without out they are allocated here (Context.buffer_free them) -> (dev_keys, dev_counts,
+        n_matches)"""
+        n = C.c_uint64()
+        fn = self._q("select")
+        if cap is None:
+            _chk(fn(self.ctx.h, self.h, min_count, max_count, None, None, 0, C.byref(n), 0))
+            cap = n.value
+        if on_device:
+            dk, dc = out if out is not None else (self.ctx.buffer_alloc(8 * max(cap, 1)), self.ctx.buffer_alloc(8 * max(cap, 1)))
+            _chk(fn(self.ctx.h, self.h, min_count, max_count, dk, dc, cap, C.byref(n), 1))
+            return n.value if out is not None else (dk, dc, n.value)
+        keys = np.empty(max(cap, 1), dtype=np.uint64)
+        counts = np.empty(max(cap, 1), dtype=np.uint64)
+        _chk(fn(self.ctx.h, self.h, min_count, max_count, keys.ctypes.data, counts.ctypes.data, cap, C.byref(n), 0))
+        m = min(n.value, cap)
+        return keys[:m], counts[:m], n.value
+
+    def top(self, n, on_device=False, out=None):
+        """GROUP BY kmer ORDER BY count(*) DESC LIMIT n: min(n, distinct) rows, counts descending, keys ascending among equal
+        counts.  host: -> (keys, counts).  on_device: into out=(dev_keys, dev_counts) of n uint64 each -> rows written;
+        without out the arrays are allocated here (Context.buffer_free them) -> (dev_keys, dev_counts, rows)"""
+        got = C.c_uint64()
+        fn = self._q("top")
+        if on_device:
+            dk, dc = out if out is not None else (self.ctx.buffer_alloc(8 * max(n, 1)), self.ctx.buffer_alloc(8 * max(n, 1)))
+            _chk(fn(self.ctx.h, self.h, n, dk, dc, C.byref(got), 1))
+            return got.value if out is not None else (dk, dc, got.value)
+        rows = min(n, self.distinct)
+        keys = np.empty(max(rows, 1), dtype=np.uint64)
+        counts = np.empty(max(rows, 1), dtype=np.uint64)
+        _chk(fn(self.ctx.h, self.h, n, keys.ctypes.data, counts.ctypes.data, C.byref(got), 0))
+        return keys[:got.value], counts[:got.value]
+
+
+class Hist(_CountQueries):
+    _obj = "hist"
+
     def __init__(self, ctx, handle):
         self.ctx, self.h = ctx, handle
 
@@ -389,8 +450,10 @@ class Hist:
             self.h = None
 
 
-class Accumulator:
+class Accumulator(_CountQueries):
     """dnagpu_acc: histograms added up on the device into 64-bit counts (no 2^32 limit); Context.accumulator(k)"""
+
+    _obj = "acc"
 
     def __init__(self, ctx, k):
         self.ctx, self.h = ctx, C.c_void_p()

@@ -1329,20 +1329,7 @@ extern "C" void dnagpu_hist_free(dnagpu_ctx *ctx, dnagpu_hist *h)
 constexpr int ACC_MIN_BITS = 4;
 constexpr u32 ACC_BOUND = ACC_SLOTS / 8 * 7;
 
-struct AccTable {
-    u64 *table = nullptr;     // 2^pbits * ACC_SLOTS * {key, count}
-    u32 *occ = nullptr;       // 2^pbits occupied-slot counts
-    int pbits = 0;            // 0: no table yet
-};
-
-struct dnagpu_acc {
-    int k;
-    AccTable t;
-    u64 distinct = 0, total = 0;
-    std::vector<u64> pre;     // groups before each partition (+ the total): the download order, built after an add
-    u64 *dev_pre = nullptr;
-};
-
+// (AccTable and dnagpu_acc: host_common.hpp -- query_host.hip reads the table too)
 static void acc_table_free(dnagpu_ctx *ctx, AccTable &t)
 {
     pool_free(ctx, t.table);

@@ -1,4 +1,4 @@
-// host_common.hpp -- what the host files of the C-ABI (dnagpu_api.hip, count_host.hip, sk_host.hip, multi_host.hip) share
+// host_common.hpp -- what the host files of the C-ABI (dnagpu_api.hip, count_host.hip, sk_host.hip, multi_host.hip, query_host.hip) share
 // (internal, like kernels.hpp): the error macros, the context / dna / histogram objects, the buffer pool, and the few
 // functions one of the files calls in another.  Declarations only, plus the templates and macros that must be visible;
 // the definitions are in dnagpu_api.hip unless a section says otherwise.
@@ -252,6 +252,23 @@ u64 sk_received_cap(const std::vector<u64> &blen, u32 n_coarse, const SkGeom &g)
 int count_sk_received(dnagpu_ctx *ctx, void *rec0, const std::vector<u64> &boff, const std::vector<u64> &blen, const SkGeom &g,
                       int k, dnagpu_hist *h, u64 rec0_cap = 0);
 }  // namespace dnagpu
+
+// the k-mer accumulator (dnagpu_api.hip: dnagpu_acc_*; query_host.hip reads the table)
+namespace dnagpu {
+struct AccTable {
+    u64 *table = nullptr;     // 2^pbits * ACC_SLOTS * {key, count}
+    u32 *occ = nullptr;       // 2^pbits occupied-slot counts
+    int pbits = 0;            // 0: no table yet
+};
+}  // namespace dnagpu
+
+struct dnagpu_acc {
+    int k;
+    dnagpu::AccTable t;
+    u64 distinct = 0, total = 0;
+    std::vector<u64> pre;     // groups before each partition (+ the total): the download order, built after an add
+    u64 *dev_pre = nullptr;
+};
 
 struct dnagpu_records {
     void *recs = nullptr;       // pool memory: 16 bytes per record, bucket after bucket

@@ -188,6 +188,47 @@ hipError_t launch_acc_summary(const u64 *table, const u32 *occ, u64 P, u64 *res3
 hipError_t launch_acc_gather(const u64 *table, const u32 *occ, const u64 *pre, u64 p_lo, u64 n_parts, u64 first, u64 count,
                              u64 *out_keys, u64 *out_counts, hipStream_t s);
 
+// ---- queries over counted groups (query_kernels.hip).  A group source is a histogram part (n slots of
+// keys / 32-bit counts, count 0 = padding) or the accumulator's table (n = P * ACC_SLOTS 16-byte slots, occ[p] == 0: the
+// partition is not read); both are cut into tiles of Q_TILE slots.
+constexpr int Q_TILE = 2048;
+constexpr int Q_DIGITS = 2048;        // bins of one radix-select pass: 11-bit digits of the count
+constexpr u32 Q_LDS_BINS = 8192;      // most bins a workgroup privatises in LDS
+struct QHistSrc {
+    const u64 *keys;
+    const u32 *counts;
+    u64 n;
+};
+struct QAccSrc {
+    const u64 *table;
+    const u32 *occ;
+    u64 n;
+};
+// which bin a group's count c goes to: spectrum != 0: min(c, n_bins) - 1; else the digit (c >> shift) & (Q_DIGITS - 1) of
+// the groups with c >> prefix_shift == prefix (has_prefix != 0; prefix_shift < 64).  lds_bins: 4 .. Q_LDS_BINS.
+struct QDigit {
+    int spectrum;
+    u64 n_bins;
+    int shift;
+    int has_prefix;
+    int prefix_shift;
+    u64 prefix;
+    u32 lds_bins;
+    int want_max;
+};
+// bins[b] += the groups of bin b (bins: at least max(lds_bins, n_bins) words, zeroed by the caller; several sources add
+// into the same bins); want_max: *maxc = max(*maxc, largest count)
+hipError_t launch_query_digits(const QHistSrc &s, const QDigit &a, u64 *bins, u64 *maxc, hipStream_t st);
+hipError_t launch_query_digits(const QAccSrc &s, const QDigit &a, u64 *bins, u64 *maxc, hipStream_t st);
+// the groups with lo <= count <= hi (lo >= 1) to out_keys / out_counts (either may be null) at *cursor + their rank, rows
+// from `cap` on not stored; *cursor += all matches (so several sources, or several ranges, append to one output)
+hipError_t launch_query_select(const QHistSrc &s, u64 lo, u64 hi, u64 *out_keys, u64 *out_counts, u64 cap, u64 *cursor,
+                               hipStream_t st);
+hipError_t launch_query_select(const QAccSrc &s, u64 lo, u64 hi, u64 *out_keys, u64 *out_counts, u64 cap, u64 *cursor,
+                               hipStream_t st);
+// m = 2^x >= 2 rows sorted by (count descending, key ascending)
+hipError_t launch_query_sort(u64 *keys, u64 *counts, u32 m, hipStream_t st);
+
 // ---- a table of sequences in one packed stream (extract_kernels.hip)
 // marks: bit b set where a sequence starts at base b (starts[1 .. n_seqs - 1]; the buffer is zeroed here)
 hipError_t launch_batch_marks(const u64 *starts, u64 n_seqs, u32 *marks, u64 n_mark_words, hipStream_t s);

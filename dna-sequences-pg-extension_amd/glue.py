@@ -89,6 +89,12 @@ def lib():
         L.count_kmers_agg_end.argtypes = [vp]
         L.dna_glue_set_agg_flush_bases.restype = None
         L.dna_glue_set_agg_flush_bases.argtypes = [C.c_uint64]
+        L.count_kmers_top_begin.restype = vp
+        L.count_kmers_top_begin.argtypes = [vp, C.c_int, C.c_int64]
+        L.count_kmers_spectrum.restype = C.c_bool
+        L.count_kmers_spectrum.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
+        L.count_kmers_agg_top.restype = C.c_bool
+        L.count_kmers_agg_top.argtypes = [vp, C.c_int64]
         _LIB = L
     return _LIB
 
@@ -242,12 +248,12 @@ def set_gpus(devices, transport=0):
     lib().dna_glue_set_gpus(n, (C.c_int * n)(*devices), transport)
 
 
-def count_kmers(d, k):
+def count_kmers(d, k, _begin=None):
     """SELECT k.kmer, count(*) FROM generate_kmers(d, k) AS k(kmer) GROUP BY k.kmer
     -> ([(kmer, count)...], (total, distinct, unique))"""
     if isinstance(d, str):
         d = dna(d)
-    c = lib().count_kmers_begin(d.p, k)
+    c = _begin(d) if _begin else lib().count_kmers_begin(d.p, k)
     if not c:
         raise _err()
     rows, km, cnt = [], _Kmer(), C.c_int64()
@@ -259,12 +265,39 @@ def count_kmers(d, k):
     return rows, (t.value, dd.value, u.value)
 
 
+def count_kmers_top(d, k, n):
+    """SELECT k.kmer, count(*) FROM generate_kmers(d, k) AS k(kmer) GROUP BY k.kmer ORDER BY count(*) DESC LIMIT n
+    (test.sql:95; sorted and cut on the device) -> ([(kmer, count)...] in that order, (total, distinct, unique) of all groups)"""
+    return count_kmers(d, k, _begin=lambda dd: lib().count_kmers_top_begin(dd.p, k, n))
+
+
+def count_kmers_spectrum(d, k, n_bins):
+    """the k-mer spectrum of generate_kmers(d, k): [groups with count 1, with count 2, ..., with count >= n_bins]"""
+    if isinstance(d, str):
+        d = dna(d)
+    c = lib().count_kmers_begin(d.p, k)
+    if not c:
+        raise _err()
+    try:
+        bins = (C.c_int64 * max(n_bins, 1))()
+        if not lib().count_kmers_spectrum(c, bins, n_bins):
+            raise _err()
+        return [int(b) for b in bins[:n_bins]]
+    finally:
+        lib().count_kmers_end(c)
+
+
 def set_agg_flush_bases(n):
     """bases per batch of count_kmers_agg (dna_glue_set_agg_flush_bases; default 2^30)"""
     lib().dna_glue_set_agg_flush_bases(int(n))
 
 
-def count_kmers_agg(rows, k):
+def count_kmers_agg_top(rows, k, n):
+    """count_kmers_agg ... ORDER BY count(*) DESC LIMIT n: the rows in that order, the totals over all groups"""
+    return count_kmers_agg(rows, k, _top=n)
+
+
+def count_kmers_agg(rows, k, _top=None):
     """SELECT k.kmer, count(*) FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS k(kmer) GROUP BY k.kmer
     (test.sql:140-150) through the aggregate: rows = the table's `dna` values (or their text)
     -> ([(kmer, count)...], (total, distinct, unique))"""
@@ -272,6 +305,8 @@ def count_kmers_agg(rows, k):
     if not a:
         raise _err()
     try:
+        if _top is not None and not lib().count_kmers_agg_top(a, _top):
+            raise _err()
         for r in rows:
             if isinstance(r, str):
                 r = dna(r)

@@ -539,7 +539,8 @@ static dnagpu_multi *multi(void)
     return g_multi;
 }
 
-CountKmers *count_kmers_begin(Dna *dna, int k)
+/* single: one histogram on this backend's device whatever dna_glue_set_gpus asked for (count_kmers_top_begin) */
+static CountKmers *ck_begin(Dna *dna, int k, bool single)
 {
     uint64_t n_rows = 0;
     if (!gpu_ok(dnagpu_kmer_count(dna->length, k, &n_rows)))
@@ -551,7 +552,7 @@ CountKmers *count_kmers_begin(Dna *dna, int k)
     }
     c->k = k;
     bool ok;
-    if (g_n_gpus > 1) {
+    if (g_n_gpus > 1 && !single) {
         /* the sequence goes to the ranks as contiguous word chunks; one all-gather + per-rank owner counts */
         dnagpu_multi *m = multi();
         dnagpu_multi_dna *md = NULL;
@@ -594,6 +595,58 @@ CountKmers *count_kmers_begin(Dna *dna, int k)
         return NULL;
     }
     return c;
+}
+
+CountKmers *count_kmers_begin(Dna *dna, int k) { return ck_begin(dna, k, false); }
+
+static bool top_limit_ok(const char *who, int64_t limit)
+{
+    if (limit >= 1 && limit <= (int64_t)DNAGPU_TOP_MAX)
+        return true;
+    ereport_error("%s: limit must be between 1 and %u", who, (unsigned)DNAGPU_TOP_MAX);
+    return false;
+}
+
+/* ... GROUP BY k.kmer ORDER BY count(*) DESC LIMIT limit (test.sql:95): the rows are chosen and sorted on the device
+ * (dnagpu_hist_top) and served from the window buffers, which hold DNAGPU_TOP_MAX rows */
+CountKmers *count_kmers_top_begin(Dna *dna, int k, int64_t limit)
+{
+    if (!top_limit_ok("count_kmers_top", limit))
+        return NULL;
+    CountKmers *c = ck_begin(dna, k, true);
+    if (!c)
+        return NULL;
+    uint64_t n = 0;
+    if (!gpu_ok(dnagpu_hist_top(c->hctx[0], c->hist[0], (uint64_t)limit, c->keys, c->counts, &n, 0))) {
+        count_kmers_end(c);
+        return NULL;
+    }
+    c->rank_distinct = n;                        /* _next serves rows [0, n) of the one window */
+    c->win_first = 0;
+    c->win_count = n;
+    return c;
+}
+
+bool count_kmers_spectrum(const CountKmers *c, int64_t *bins, int n_bins)
+{
+    if (!c || !bins || n_bins < 1 || (uint64_t)n_bins > DNAGPU_SPECTRUM_MAX_BINS) {
+        ereport_error("count_kmers_spectrum: n_bins must be between 1 and %u", (unsigned)DNAGPU_SPECTRUM_MAX_BINS);
+        return false;
+    }
+    uint64_t *part = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)n_bins);
+    if (!part) {
+        ereport_error("out of memory");
+        return false;
+    }
+    bool ok = true;
+    memset(bins, 0, sizeof(int64_t) * (size_t)n_bins);
+    for (int r = 0; ok && r < c->n_ranks; r++) {     /* the ranks' groups are disjoint: their spectra add up */
+        ok = gpu_ok(dnagpu_hist_spectrum(c->hctx[r], c->hist[r], (uint64_t)n_bins, part));
+        for (int b = 0; ok && b < n_bins; b++)
+            bins[b] += (int64_t)part[b];
+    }
+    free(part);
+    return ok;
 }
 
 bool count_kmers_next(CountKmers *c, Kmer *kmer, int64_t *count)
@@ -650,6 +703,8 @@ struct CountKmersAgg {
     uint64_t *words, n_bases, cap_words;         /* the batch: rows back to back as one packed stream */
     uint64_t *starts, n_seqs, cap_seqs;          /* starts[0 .. n_seqs] */
     bool finished, failed;
+    uint64_t top_limit;                          /* count_kmers_agg_top: serve only the first rows of ORDER BY count(*) DESC */
+    uint64_t serve_n;                            /* rows _next serves: distinct, or the rows of the top */
     uint64_t distinct, total, unique;
     uint64_t next, win_first, win_count;
     uint64_t *keys, *counts;
@@ -776,7 +831,28 @@ static bool agg_finish(CountKmersAgg *a)
         ereport_error("out of memory");
         return false;
     }
+    a->serve_n = a->distinct;
+    if (a->top_limit && a->acc) {                /* chosen and sorted on the device; the window buffers hold DNAGPU_TOP_MAX rows */
+        uint64_t n = 0;
+        if (!gpu_ok(dnagpu_acc_top(g_ctx, a->acc, a->top_limit, a->keys, a->counts, &n, 0)))
+            return false;
+        a->serve_n = n;
+        a->win_first = 0;
+        a->win_count = n;
+    }
     a->finished = true;
+    return true;
+}
+
+bool count_kmers_agg_top(CountKmersAgg *a, int64_t limit)
+{
+    if (!top_limit_ok("count_kmers_agg_top", limit))
+        return false;
+    if (a->finished || a->failed) {
+        ereport_error("count_kmers_agg_top: called after the first row was served or the aggregate failed");
+        return false;
+    }
+    a->top_limit = (uint64_t)limit;
     return true;
 }
 
@@ -788,10 +864,10 @@ bool count_kmers_agg_next(CountKmersAgg *a, Kmer *kmer, int64_t *count)
         a->failed = true;
         return false;
     }
-    if (a->next >= a->distinct)
+    if (a->next >= a->serve_n)
         return false;
     if (a->next >= a->win_first + a->win_count) {
-        uint64_t n = a->distinct - a->next < CK_WINDOW ? a->distinct - a->next : CK_WINDOW;
+        uint64_t n = a->serve_n - a->next < CK_WINDOW ? a->serve_n - a->next : CK_WINDOW;
         if (!gpu_ok(dnagpu_acc_download(g_ctx, a->acc, a->next, n, a->keys, a->counts))) {
             a->failed = true;
             return false;

@@ -103,6 +103,14 @@ bool count_kmers_next(CountKmers *c, Kmer *kmer, int64_t *count);
 /* sum(count), count(*), count(*) FILTER (WHERE count = 1) over the groups (test.sql:112-114) */
 void count_kmers_totals(const CountKmers *c, int64_t *total, int64_t *distinct, int64_t *unique);
 void count_kmers_end(CountKmers *c);
+/* ... GROUP BY k.kmer ORDER BY count(*) DESC LIMIT limit -- the reference's own first counting statement (test.sql:95) with
+ * the sort and the cut done on the device (dnagpu_hist_top): count_kmers_next then serves min(limit, distinct) rows, counts
+ * descending, kmers ascending among equal counts; count_kmers_totals still covers every group.  limit < 1 or >
+ * DNAGPU_TOP_MAX: NULL and dna_glue_errmsg().  One device (dna_glue_set_device) whatever dna_glue_set_gpus asked for. */
+CountKmers *count_kmers_top_begin(Dna *dna, int k, int64_t limit);
+/* the k-mer spectrum of a count: bins[c - 1] = groups with count c, bins[n_bins - 1] = groups with count >= n_bins
+ * (test.sql:112-114 is bins[0]); dnagpu_hist_spectrum.  false + dna_glue_errmsg() on an ERROR. */
+bool count_kmers_spectrum(const CountKmers *c, int64_t *bins, int n_bins);
 
 /* ---- SELECT k.kmer, count(*) FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS k(kmer) GROUP BY k.kmer
  * (test.sql:140-150) as an aggregate over the table's rows ----
@@ -119,6 +127,9 @@ bool count_kmers_agg_next(CountKmersAgg *a, Kmer *kmer, int64_t *count);
 bool count_kmers_agg_failed(const CountKmersAgg *a);
 void count_kmers_agg_totals(const CountKmersAgg *a, int64_t *total, int64_t *distinct, int64_t *unique);
 void count_kmers_agg_end(CountKmersAgg *a);
+/* ... ORDER BY count(*) DESC LIMIT limit over the aggregate (dnagpu_acc_top): called before the first count_kmers_agg_next,
+ * which then serves those rows only; false + dna_glue_errmsg() for a bad limit (as count_kmers_top_begin) or a late call */
+bool count_kmers_agg_top(CountKmersAgg *a, int64_t limit);
 /* bases per batch (default 2^30); tests use small values to force many batches */
 void dna_glue_set_agg_flush_bases(uint64_t n);
 

@@ -289,6 +289,44 @@ int dnagpu_acc_summary(dnagpu_ctx *ctx, const dnagpu_acc *acc, uint64_t *total, 
 int dnagpu_acc_download(dnagpu_ctx *ctx, dnagpu_acc *acc, uint64_t first, uint64_t count, uint64_t *keys, uint64_t *counts);
 void dnagpu_acc_free(dnagpu_ctx *ctx, dnagpu_acc *acc);
 
+/* ---- count-ordered queries over counted groups: the reference's first counting statement is not a bare GROUP BY but
+ *   SELECT k.kmer, count(*) FROM generate_kmers(...) AS k(kmer) GROUP BY k.kmer ORDER BY count(*) DESC   (test.sql:95)
+ * and its second summarises the distribution of the counts (count(*) FILTER (WHERE count = 1), test.sql:112-114) -----------
+ * Three read-only queries, each over a histogram (dnagpu_hist_*) and over an accumulator (dnagpu_acc_*: a table past 2^32
+ * rows only ever exists as one).  They run on the device and hand out only the answer, not every group.
+ * Every histogram is accepted, under dnagpu_acc_add's rule: ordered or unordered, one part or several, results of
+ * dnagpu_hist_merge, borrowed dnagpu_hist_part views.  Count-0 padding slots, empty accumulator slots and unoccupied
+ * partitions are never a group; the all-ones key is a key like any other.  The object is left as it is (the accumulator's
+ * download order too).  A NULL ctx, object, bins or n_out is DNAGPU_ERR_BAD_ARG; the range of n_bins / n is checked first
+ * (dnagpu_acc_create's order).
+ *
+ * spectrum: the k-mer spectrum.  bins[c - 1] = the groups with count == c for 1 <= c < n_bins, bins[n_bins - 1] = the groups
+ *   with count >= n_bins (bins: n_bins words of host memory).  sum(bins) = distinct; with n_bins >= 2, bins[0] is the
+ *   `unique` of dnagpu_hist_summary; n_bins == 1 gives [distinct].  n_bins outside 1 .. DNAGPU_SPECTRUM_MAX_BINS:
+ *   DNAGPU_ERR_BAD_ARG.
+ * select: GROUP BY kmer HAVING count(*) BETWEEN min_count AND max_count.  The groups with min_count <= count <= max_count, in
+ *   unspecified order, counts as uint64 (dnagpu_hist_download's widening), at most `cap` rows to each of out_keys /
+ *   out_counts (either may be NULL; host memory, or device memory when out_on_device != 0).  *n_out = ALL matching groups
+ *   even when that exceeds cap (dnagpu_generate_kmers_filtered's rule); which cap of them are written is then unspecified.
+ *   min_count > max_count matches nothing (DNAGPU_OK); min_count == 0 means 1.
+ * top: GROUP BY kmer ORDER BY count(*) DESC LIMIT n.  *n_out = min(n, distinct) rows sorted by count descending, keys
+ *   ascending (as uint64) among rows of equal count.  With T the count of the last row, every group with count > T is
+ *   returned; which groups of count == T fill the remaining places is unspecified (PostgreSQL's LIMIT over ties promises no
+ *   more).  n >= distinct (with distinct <= DNAGPU_TOP_MAX) is the whole ORDER BY count(*) DESC of test.sql:95.  n == 0 or
+ *   an empty object: *n_out = 0, DNAGPU_OK.  n > DNAGPU_TOP_MAX: DNAGPU_ERR_TOO_LARGE. */
+#define DNAGPU_SPECTRUM_MAX_BINS (1u << 20)
+#define DNAGPU_TOP_MAX           (1u << 20)
+int dnagpu_hist_spectrum(dnagpu_ctx *ctx, const dnagpu_hist *h, uint64_t n_bins, uint64_t *bins);
+int dnagpu_acc_spectrum(dnagpu_ctx *ctx, const dnagpu_acc *acc, uint64_t n_bins, uint64_t *bins);
+int dnagpu_hist_select(dnagpu_ctx *ctx, const dnagpu_hist *h, uint64_t min_count, uint64_t max_count,
+                       uint64_t *out_keys, uint64_t *out_counts, uint64_t cap, uint64_t *n_out, int out_on_device);
+int dnagpu_acc_select(dnagpu_ctx *ctx, const dnagpu_acc *acc, uint64_t min_count, uint64_t max_count,
+                      uint64_t *out_keys, uint64_t *out_counts, uint64_t cap, uint64_t *n_out, int out_on_device);
+int dnagpu_hist_top(dnagpu_ctx *ctx, const dnagpu_hist *h, uint64_t n,
+                    uint64_t *out_keys, uint64_t *out_counts, uint64_t *n_out, int out_on_device);
+int dnagpu_acc_top(dnagpu_ctx *ctx, const dnagpu_acc *acc, uint64_t n,
+                   uint64_t *out_keys, uint64_t *out_counts, uint64_t *n_out, int out_on_device);
+
 /* ---- multi-GPU sharding of the count (one process per GPU; the exchange itself is the
  * caller's collective, e.g. RCCL all-to-all) -------------------------------------------------
  * Step 1 on every rank: the keys of rows [first, first+count) partitioned by owner.  Owner o of
