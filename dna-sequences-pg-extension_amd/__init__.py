@@ -17,6 +17,7 @@ from .binding import (  # noqa: F401
     DEBUG_NO_SLAB0,
     DEBUG_NO_SPEC1,
     DEBUG_POISON_POOL,
+    DEBUG_RANK_SMALL,
     DEBUG_SLAB0,
     DEBUG_SLAB0_OVERFLOW,
     DEBUG_SAMPLE1,
@@ -34,6 +35,9 @@ from .binding import (  # noqa: F401
     MULTI_COPY,
     MULTI_RCCL,
     Multi,
+    ORDER_COUNT_ASC,
+    ORDER_COUNT_DESC,
+    Ranking,
     abi_version,
     device_count,
     kmer_count,

@@ -30,8 +30,11 @@ DEBUG_SLAB0 = 64
 DEBUG_NO_SLAB0 = 128
 DEBUG_SLAB0_OVERFLOW = 256
 DEBUG_SAMPLE1 = 512                   # level 1: regions from a sampled histogram whatever the coarse buckets look like
+DEBUG_RANK_SMALL = 1024               # rank: a class limit of 4 counts and sort chunks of 2048 rows (the tail path at small sizes)
 SPECTRUM_MAX_BINS = 1 << 20
 TOP_MAX = 1 << 20
+ORDER_COUNT_DESC = 0                  # ORDER BY count(*) DESC (test.sql:95)
+ORDER_COUNT_ASC = 1                   # ORDER BY count(*): the rarest first
 U64_MAX = 2 ** 64 - 1
 
 
@@ -171,6 +174,17 @@ def lib():
         getattr(L, f"dnagpu_{obj}_spectrum").argtypes = [vp, vp, C.c_uint64, u64p]
         getattr(L, f"dnagpu_{obj}_select").argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, u64p, C.c_int]
         getattr(L, f"dnagpu_{obj}_top").argtypes = [vp, vp, C.c_uint64, vp, vp, u64p, C.c_int]
+        getattr(L, f"dnagpu_{obj}_rank").argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
+    L.dnagpu_ranking_rows.argtypes = [vp]
+    L.dnagpu_ranking_rows.restype = C.c_uint64
+    L.dnagpu_ranking_order.argtypes = [vp]
+    L.dnagpu_ranking_device_keys.argtypes = [vp]
+    L.dnagpu_ranking_device_keys.restype = vp
+    L.dnagpu_ranking_device_counts.argtypes = [vp]
+    L.dnagpu_ranking_device_counts.restype = vp
+    L.dnagpu_ranking_read.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_int]
+    L.dnagpu_ranking_free.argtypes = [vp, vp]
+    L.dnagpu_ranking_free.restype = None
     L.dnagpu_partition_kmers.argtypes = [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(vp), u64p]
     L.dnagpu_buffer_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
     L.dnagpu_buffer_free.argtypes = [vp, vp]
@@ -319,8 +333,62 @@ class Records:
             self.h = None
 
 
+class Ranking:
+    """dnagpu_ranking: every group of a Hist / an Accumulator in count order, a snapshot in device memory (Hist.rank,
+    Accumulator.rank)"""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+
+    @property
+    def rows(self):
+        return int(lib().dnagpu_ranking_rows(self.h))
+
+    @property
+    def order(self):
+        return int(lib().dnagpu_ranking_order(self.h))
+
+    @property
+    def device_keys(self):
+        """device pointer of `rows` uint64 keys in rank order (None for an empty ranking)"""
+        return lib().dnagpu_ranking_device_keys(self.h)
+
+    @property
+    def device_counts(self):
+        return lib().dnagpu_ranking_device_counts(self.h)
+
+    def read(self, first=0, count=None, on_device=False, out=None):
+        """rows [first, first + count) of the order (count=None: all from first on).  host: -> (keys, counts).  on_device:
+        into out=(dev_keys, dev_counts) of count uint64 each (either may be None) -> count; without out the arrays are
+        allocated here (Context.buffer_free them) -> (dev_keys, dev_counts, count)"""
+        if count is None:
+            count = self.rows - first
+        fn = lib().dnagpu_ranking_read
+        if on_device:
+            dk, dc = out if out is not None else (self.ctx.buffer_alloc(8 * max(count, 1)), self.ctx.buffer_alloc(8 * max(count, 1)))
+            _chk(fn(self.ctx.h, self.h, first, count, dk, dc, 1))
+            return count if out is not None else (dk, dc, count)
+        keys = np.empty(max(count, 1), dtype=np.uint64)
+        counts = np.empty(max(count, 1), dtype=np.uint64)
+        _chk(fn(self.ctx.h, self.h, first, count, keys.ctypes.data, counts.ctypes.data, 0))
+        return keys[:count], counts[:count]
+
+    def free(self):
+        if self.h:
+            if self.ctx._base_debug & DEBUG_GUARD_POOL:
+                self.ctx.synchronize()          # raises if a kernel wrote past the end of a work buffer
+            lib().dnagpu_ranking_free(self.ctx.h, self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
 class _CountQueries:
-    """the count-ordered queries Hist and Accumulator share (dnagpu_hist_* / dnagpu_acc_* spectrum, select, top)"""
+    """the count-ordered queries Hist and Accumulator share (dnagpu_hist_* / dnagpu_acc_* spectrum, select, top, rank)"""
 
     _obj = None                       # "hist" / "acc"
 
@@ -369,6 +437,13 @@ class _CountQueries:
         counts = np.empty(max(rows, 1), dtype=np.uint64)
         _chk(fn(self.ctx.h, self.h, n, keys.ctypes.data, counts.ctypes.data, C.byref(got), 0))
         return keys[:got.value], counts[:got.value]
+
+
+    def rank(self, order=ORDER_COUNT_DESC):
+        """GROUP BY kmer ORDER BY count(*) [DESC] without a LIMIT: every group in count order -> Ranking (free it)"""
+        r = C.c_void_p()
+        _chk(self._q("rank")(self.ctx.h, self.h, order, C.byref(r)))
+        return Ranking(self.ctx, r)
 
 
 class Hist(_CountQueries):

@@ -204,6 +204,11 @@ struct QAccSrc {
     const u32 *occ;
     u64 n;
 };
+struct QDenseSrc {                    // dense rows with 64-bit counts (the tail of a ranking): a third, trivial source
+    const u64 *keys;
+    const u64 *counts;
+    u64 n;
+};
 // which bin a group's count c goes to: spectrum != 0: min(c, n_bins) - 1; else the digit (c >> shift) & (Q_DIGITS - 1) of
 // the groups with c >> prefix_shift == prefix (has_prefix != 0; prefix_shift < 64).  lds_bins: 4 .. Q_LDS_BINS.
 struct QDigit {
@@ -226,8 +231,21 @@ hipError_t launch_query_select(const QHistSrc &s, u64 lo, u64 hi, u64 *out_keys,
                                hipStream_t st);
 hipError_t launch_query_select(const QAccSrc &s, u64 lo, u64 hi, u64 *out_keys, u64 *out_counts, u64 cap, u64 *cursor,
                                hipStream_t st);
+hipError_t launch_query_digits(const QDenseSrc &s, const QDigit &a, u64 *bins, u64 *maxc, hipStream_t st);
+hipError_t launch_query_select(const QDenseSrc &s, u64 lo, u64 hi, u64 *out_keys, u64 *out_counts, u64 cap, u64 *cursor,
+                               hipStream_t st);
 // m = 2^x >= 2 rows sorted by (count descending, key ascending)
 hipError_t launch_query_sort(u64 *keys, u64 *counts, u32 m, hipStream_t st);
+// rank (dnagpu_*_rank): a counting sort by count class.  A group of count c belongs to class min(c, n_classes); cursors[cls]
+// (n_classes + 1 words, [0] unused) holds the next free row of class cls -- the caller sets them to the classes' first rows.
+// Every tile takes one returning atomic per class it holds rows of and stores (key, 64-bit count) at the rows it got; rows
+// from `rows` on are never stored.  3 <= n_classes <= Q_DIGITS.  Several sources go on from the same cursors.
+hipError_t launch_query_rank_scatter(const QHistSrc &s, u32 n_classes, u64 *cursors, u64 *out_keys, u64 *out_counts, u64 rows,
+                                     hipStream_t st);
+hipError_t launch_query_rank_scatter(const QAccSrc &s, u32 n_classes, u64 *cursors, u64 *out_keys, u64 *out_counts, u64 rows,
+                                     hipStream_t st);
+// rows [0, n) of the two arrays reversed in place
+hipError_t launch_query_reverse(u64 *keys, u64 *counts, u64 n, hipStream_t st);
 
 // ---- a table of sequences in one packed stream (extract_kernels.hip)
 // marks: bit b set where a sequence starts at base b (starts[1 .. n_seqs - 1]; the buffer is zeroed here)

@@ -1,6 +1,6 @@
-// query_kernels.hip -- read-only queries over counted groups (dnagpu_hist_* / dnagpu_acc_* spectrum, select, top;
-// DESIGN.md 4.10): a digit histogram of the counts, a compaction of the groups whose count lies in a range, and the
-// sort of at most 2^20 selected rows.
+// query_kernels.hip -- read-only queries over counted groups (dnagpu_hist_* / dnagpu_acc_* spectrum, select, top, rank;
+// DESIGN.md 4.10): a digit histogram of the counts, a compaction of the groups whose count lies in a range, the
+// sort of at most 2^20 selected rows, and the scatter of every group to the rows of its count class (rank).
 //
 // One abstraction feeds every kernel, a GROUP SOURCE cut into tiles of Q_TILE slots, eight per thread of a 256-thread
 // workgroup:
@@ -9,7 +9,8 @@
 //   QAccSrc   the accumulator's table: 16-byte {key, u64 count} slots read one dwordx4 at a time, count 0 = empty; a tile
 //             lies inside one partition (Q_TILE divides ACC_SLOTS) and the tiles of a partition with occ == 0 are never
 //             read (its slots hold nothing defined).
-// Neither kernel writes to its source.
+//   QDenseSrc dense rows u64 keys[], u64 counts[] (the tail of a ranking, compacted): the digit and select kernels only.
+// No kernel writes to its source.
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
@@ -53,6 +54,26 @@ struct HistTile {
         }
     }
     __device__ __forceinline__ u64 key(u64 t, int tid, int j, const u64 (&)[Q_PER_T]) const { return s.keys[slot(t, tid, j)]; }
+    // every slot's key beside its count (rank): two dwordx4 per four slots where the tile is whole; a padding slot's key is
+    // read (it lies inside the extent) and never used
+    __device__ __forceinline__ void load_keys(u64 t, int tid, u64 (&k)[Q_PER_T]) const
+    {
+        const bool whole = (t + 1) * Q_TILE <= s.n && (reinterpret_cast<uintptr_t>(s.keys) & 15) == 0;
+        if (whole) {
+#pragma unroll
+            for (int h = 0; h < Q_PER_T / 2; h++) {
+                const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(s.keys + slot(t, tid, 2 * h));
+                k[2 * h] = v.x;
+                k[2 * h + 1] = v.y;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < Q_PER_T; j++) {
+                const u64 i = slot(t, tid, j);
+                k[j] = i < s.n ? s.keys[i] : 0;
+            }
+        }
+    }
 };
 
 struct AccTile {
@@ -74,6 +95,22 @@ struct AccTile {
         }
     }
     __device__ __forceinline__ u64 key(u64, int, int j, const u64 (&k)[Q_PER_T]) const { return k[j]; }
+    __device__ __forceinline__ void load_keys(u64, int, u64 (&)[Q_PER_T]) const {}       // (load brought them)
+};
+
+struct DenseTile {
+    QDenseSrc s;
+    __device__ __forceinline__ bool live(u64) const { return true; }
+    __device__ __forceinline__ u64 slot(u64 t, int tid, int j) const { return t * Q_TILE + (u64)j * Q_NT + (u64)tid; }
+    __device__ __forceinline__ void load(u64 t, int tid, u64 (&c)[Q_PER_T], u64 (&)[Q_PER_T]) const
+    {
+#pragma unroll
+        for (int j = 0; j < Q_PER_T; j++) {
+            const u64 i = slot(t, tid, j);
+            c[j] = i < s.n ? s.counts[i] : 0;
+        }
+    }
+    __device__ __forceinline__ u64 key(u64 t, int tid, int j, const u64 (&)[Q_PER_T]) const { return s.keys[slot(t, tid, j)]; }
 };
 
 __device__ __forceinline__ u64 tiles_of(u64 n) { return (n + Q_TILE - 1) / Q_TILE; }
@@ -187,6 +224,93 @@ __global__ __launch_bounds__(Q_NT) void query_select_kernel(Src src, u64 lo, u64
     }
 }
 
+// ---- rank: every group to the rows of its count class, class = min(count, n_classes) (the last class is the tail: every
+// count from n_classes on, still to be sorted).  One workgroup per tile.  It ranks its rows inside every class, reserves the
+// rows of a class with ONE returning global atomic per class the tile holds (cursors[class], which starts at the class's
+// first row), and stores (key, 64-bit count) at the reserved base + rank: the rows one tile adds to a class are contiguous.
+// Classes 1 .. R_FAST are ranked with a block scan of per-thread counts, two 16-bit fields in one word (on uniform data
+// every group has count 1: 64 lanes taking a returning LDS atomic on one address would serialise); the other classes
+// take a returning LDS atomic on the class's counter, and the lane that drew rank 0 makes the class's reservation.
+constexpr int R_FAST = 2;
+
+template <class Src>
+__global__ __launch_bounds__(Q_NT) void query_rank_scatter_kernel(Src src, u32 n_classes, unsigned long long *__restrict__ cursors,
+                                                                  u64 *__restrict__ out_keys, u64 *__restrict__ out_counts, u64 rows)
+{
+    __shared__ u32 cnt[Q_DIGITS + 1];
+    __shared__ u64 base[Q_DIGITS + 1];
+    __shared__ u32 arr[Q_NT];
+    __shared__ u32 wtmp[Q_NT / 64];
+    const int tid = threadIdx.x;
+    const u64 t = blockIdx.x;
+    if (!src.live(t))
+        return;
+    for (u32 b = tid; b <= n_classes; b += Q_NT)
+        cnt[b] = 0;
+    u64 c[Q_PER_T], k[Q_PER_T];
+    src.load(t, tid, c, k);
+    src.load_keys(t, tid, k);
+    __syncthreads();
+    u32 rank[Q_PER_T];
+    u32 fast = 0;                                    // this thread's rows of class 1 (bits 0-15) and class 2 (bits 16-31)
+#pragma unroll
+    for (int j = 0; j < Q_PER_T; j++) {
+        const u64 v = c[j];
+        rank[j] = 0;
+        if (v == 0)
+            continue;
+        if (v <= (u64)R_FAST) {
+            const int sh = 16 * ((int)v - 1);
+            rank[j] = (fast >> sh) & 0xFFFFu;
+            fast += 1u << sh;
+        } else {
+            rank[j] = atomicAdd(&cnt[v < n_classes ? (u32)v : n_classes], 1u);
+        }
+    }
+    const u32 total = block_scan_value<Q_NT>(fast, arr, Q_NT, wtmp, tid);      // (its barriers also end the LDS atomics)
+    if (tid < R_FAST) {
+        const u32 n = (total >> (16 * tid)) & 0xFFFFu;
+        if (n)
+            base[tid + 1] = atomicAdd(&cursors[tid + 1], (unsigned long long)n);
+    }
+#pragma unroll
+    for (int j = 0; j < Q_PER_T; j++) {
+        if (c[j] > (u64)R_FAST && rank[j] == 0) {
+            const u32 cls = c[j] < n_classes ? (u32)c[j] : n_classes;
+            base[cls] = atomicAdd(&cursors[cls], (unsigned long long)cnt[cls]);
+        }
+    }
+    __syncthreads();
+    const u32 before = arr[tid];
+#pragma unroll
+    for (int j = 0; j < Q_PER_T; j++) {
+        const u64 v = c[j];
+        if (v == 0)
+            continue;
+        const u32 cls = v < n_classes ? (u32)v : n_classes;
+        u64 at = base[cls] + rank[j];
+        if (v <= (u64)R_FAST)
+            at += (before >> (16 * ((int)v - 1))) & 0xFFFFu;
+        if (at < rows) {                             // (always, while the cursors were set from this source's spectrum)
+            out_keys[at] = k[j];
+            out_counts[at] = v;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void query_reverse_kernel(u64 *__restrict__ keys, u64 *__restrict__ cnts, u64 n)
+{
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n / 2)
+        return;
+    const u64 p = n - 1 - i;
+    const u64 ka = keys[i], ca = cnts[i], kb = keys[p], cb = cnts[p];
+    keys[i] = kb;
+    cnts[i] = cb;
+    keys[p] = ka;
+    cnts[p] = ca;
+}
+
 // ---- the sort of top's rows: a bitonic network over m = 2^x rows by (count descending, key ascending).  Steps whose
 // partners are less than SORT_TILE apart run in LDS, a whole tile's steps per launch; the others are one launch each over
 // global memory.  Not a hot path: at most 2^20 rows.
@@ -260,6 +384,19 @@ hipError_t run_digits(const S &s, const QDigit &a, u64 *bins, u64 *maxc, hipStre
 }
 
 template <class Src, class S>
+hipError_t run_rank(const S &s, u32 n_classes, u64 *cursors, u64 *out_keys, u64 *out_counts, u64 rows, hipStream_t st)
+{
+    const u64 n_tiles = (s.n + Q_TILE - 1) / Q_TILE;
+    if (n_tiles == 0)
+        return hipSuccess;
+    if (n_tiles > 0x7FFFFFFFull || n_classes < R_FAST + 1 || n_classes > (u32)Q_DIGITS)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(query_rank_scatter_kernel<Src>, dim3((unsigned)n_tiles), dim3(Q_NT), 0, st, Src{s}, n_classes,
+                       reinterpret_cast<unsigned long long *>(cursors), out_keys, out_counts, rows);
+    return hipGetLastError();
+}
+
+template <class Src, class S>
 hipError_t run_select(const S &s, u64 lo, u64 hi, u64 *out_keys, u64 *out_counts, u64 cap, u64 *cursor, hipStream_t st)
 {
     const u64 n_tiles = (s.n + Q_TILE - 1) / Q_TILE;
@@ -291,6 +428,38 @@ hipError_t launch_query_select(const QAccSrc &s, u64 lo, u64 hi, u64 *out_keys, 
                                hipStream_t st)
 {
     return run_select<AccTile>(s, lo, hi, out_keys, out_counts, cap, cursor, st);
+}
+
+hipError_t launch_query_digits(const QDenseSrc &s, const QDigit &a, u64 *bins, u64 *maxc, hipStream_t st)
+{
+    return run_digits<DenseTile>(s, a, bins, maxc, st);
+}
+hipError_t launch_query_select(const QDenseSrc &s, u64 lo, u64 hi, u64 *out_keys, u64 *out_counts, u64 cap, u64 *cursor,
+                               hipStream_t st)
+{
+    return run_select<DenseTile>(s, lo, hi, out_keys, out_counts, cap, cursor, st);
+}
+
+hipError_t launch_query_rank_scatter(const QHistSrc &s, u32 n_classes, u64 *cursors, u64 *out_keys, u64 *out_counts, u64 rows,
+                                     hipStream_t st)
+{
+    return run_rank<HistTile>(s, n_classes, cursors, out_keys, out_counts, rows, st);
+}
+hipError_t launch_query_rank_scatter(const QAccSrc &s, u32 n_classes, u64 *cursors, u64 *out_keys, u64 *out_counts, u64 rows,
+                                     hipStream_t st)
+{
+    return run_rank<AccTile>(s, n_classes, cursors, out_keys, out_counts, rows, st);
+}
+
+hipError_t launch_query_reverse(u64 *keys, u64 *counts, u64 n, hipStream_t st)
+{
+    if (n < 2)
+        return hipSuccess;
+    const u64 blocks = (n / 2 + 255) / 256;
+    if (blocks > 0x7FFFFFFFull)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(query_reverse_kernel, dim3((unsigned)blocks), dim3(256), 0, st, keys, counts, n);
+    return hipGetLastError();
 }
 
 hipError_t launch_query_sort(u64 *keys, u64 *counts, u32 m, hipStream_t st)

@@ -95,6 +95,10 @@ def lib():
         L.count_kmers_spectrum.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
         L.count_kmers_agg_top.restype = C.c_bool
         L.count_kmers_agg_top.argtypes = [vp, C.c_int64]
+        L.count_kmers_ordered_begin.restype = vp
+        L.count_kmers_ordered_begin.argtypes = [vp, C.c_int, C.c_bool]
+        L.count_kmers_agg_order.restype = C.c_bool
+        L.count_kmers_agg_order.argtypes = [vp, C.c_bool]
         _LIB = L
     return _LIB
 
@@ -271,6 +275,12 @@ def count_kmers_top(d, k, n):
     return count_kmers(d, k, _begin=lambda dd: lib().count_kmers_top_begin(dd.p, k, n))
 
 
+def count_kmers_ordered(d, k, descending=True):
+    """SELECT k.kmer, count(*) FROM generate_kmers(d, k) AS k(kmer) GROUP BY k.kmer ORDER BY count(*) [DESC] -- no LIMIT
+    (test.sql:95 as written; ranked on the device) -> ([(kmer, count)...] every group in that order, (total, distinct, unique))"""
+    return count_kmers(d, k, _begin=lambda dd: lib().count_kmers_ordered_begin(dd.p, k, descending))
+
+
 def count_kmers_spectrum(d, k, n_bins):
     """the k-mer spectrum of generate_kmers(d, k): [groups with count 1, with count 2, ..., with count >= n_bins]"""
     if isinstance(d, str):
@@ -297,7 +307,12 @@ def count_kmers_agg_top(rows, k, n):
     return count_kmers_agg(rows, k, _top=n)
 
 
-def count_kmers_agg(rows, k, _top=None):
+def count_kmers_agg_ordered(rows, k, descending=True):
+    """count_kmers_agg ... ORDER BY count(*) [DESC] without a LIMIT: every group in that order, the totals"""
+    return count_kmers_agg(rows, k, _order=descending)
+
+
+def count_kmers_agg(rows, k, _top=None, _order=None):
     """SELECT k.kmer, count(*) FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS k(kmer) GROUP BY k.kmer
     (test.sql:140-150) through the aggregate: rows = the table's `dna` values (or their text)
     -> ([(kmer, count)...], (total, distinct, unique))"""
@@ -306,6 +321,8 @@ def count_kmers_agg(rows, k, _top=None):
         raise _err()
     try:
         if _top is not None and not lib().count_kmers_agg_top(a, _top):
+            raise _err()
+        if _order is not None and not lib().count_kmers_agg_order(a, bool(_order)):
             raise _err()
         for r in rows:
             if isinstance(r, str):

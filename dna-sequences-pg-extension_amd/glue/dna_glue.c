@@ -501,6 +501,7 @@ struct CountKmers {
     int n_ranks, rank;                       /* rank = the histogram rows are being served from */
     dnagpu_hist *hist[CK_MAX_RANKS];
     dnagpu_ctx *hctx[CK_MAX_RANKS];
+    dnagpu_ranking *ranking;                 /* count_kmers_ordered_begin: the rows come from it, the histogram is gone */
     uint64_t rank_distinct, next, win_first, win_count;   /* cursor inside hist[rank] */
     uint64_t distinct;
     uint64_t *keys, *counts;
@@ -627,6 +628,25 @@ CountKmers *count_kmers_top_begin(Dna *dna, int k, int64_t limit)
     return c;
 }
 
+/* ... GROUP BY k.kmer ORDER BY count(*) [DESC] with no LIMIT: every group ranked on the device (dnagpu_hist_rank); the
+ * histogram is freed, count_kmers_next reads the ranking window by window */
+#define CK_RANK_WINDOW ((uint64_t)1 << 20)
+CountKmers *count_kmers_ordered_begin(Dna *dna, int k, bool descending)
+{
+    CountKmers *c = ck_begin(dna, k, true);
+    if (!c)
+        return NULL;
+    if (!gpu_ok(dnagpu_hist_rank(c->hctx[0], c->hist[0], descending ? DNAGPU_ORDER_COUNT_DESC : DNAGPU_ORDER_COUNT_ASC,
+                                 &c->ranking))) {
+        count_kmers_end(c);
+        return NULL;
+    }
+    dnagpu_hist_free(c->hctx[0], c->hist[0]);
+    c->hist[0] = NULL;
+    c->rank_distinct = dnagpu_ranking_rows(c->ranking);
+    return c;
+}
+
 bool count_kmers_spectrum(const CountKmers *c, int64_t *bins, int n_bins)
 {
     if (!c || !bins || n_bins < 1 || (uint64_t)n_bins > DNAGPU_SPECTRUM_MAX_BINS) {
@@ -660,7 +680,10 @@ bool count_kmers_next(CountKmers *c, Kmer *kmer, int64_t *count)
     }
     if (c->next >= c->win_first + c->win_count) {
         uint64_t n = c->rank_distinct - c->next < CK_WINDOW ? c->rank_distinct - c->next : CK_WINDOW;
-        if (!gpu_ok(dnagpu_hist_download(c->hctx[c->rank], c->hist[c->rank], c->next, n, c->keys, c->counts)))
+        if (c->ranking && n > CK_RANK_WINDOW)
+            n = CK_RANK_WINDOW;
+        if (!gpu_ok(c->ranking ? dnagpu_ranking_read(c->hctx[0], c->ranking, c->next, n, c->keys, c->counts, 0)
+                               : dnagpu_hist_download(c->hctx[c->rank], c->hist[c->rank], c->next, n, c->keys, c->counts)))
             return false;
         c->win_first = c->next;
         c->win_count = n;
@@ -686,6 +709,8 @@ void count_kmers_end(CountKmers *c)
     for (int r = 0; r < c->n_ranks; r++)
         if (c->hist[r])
             dnagpu_hist_free(c->hctx[r], c->hist[r]);
+    if (c->ranking)
+        dnagpu_ranking_free(c->hctx[0], c->ranking);
     free(c->keys);
     free(c->counts);
     free(c);
@@ -704,6 +729,8 @@ struct CountKmersAgg {
     uint64_t *starts, n_seqs, cap_seqs;          /* starts[0 .. n_seqs] */
     bool finished, failed;
     uint64_t top_limit;                          /* count_kmers_agg_top: serve only the first rows of ORDER BY count(*) DESC */
+    int order;                                   /* count_kmers_agg_order: 0 = none, 1 = count descending, 2 = ascending */
+    dnagpu_ranking *ranking;                     /* ... every group in that order, made when the aggregate finishes */
     uint64_t serve_n;                            /* rows _next serves: distinct, or the rows of the top */
     uint64_t distinct, total, unique;
     uint64_t next, win_first, win_count;
@@ -840,7 +867,21 @@ static bool agg_finish(CountKmersAgg *a)
         a->win_first = 0;
         a->win_count = n;
     }
+    if (a->order && a->acc &&
+        !gpu_ok(dnagpu_acc_rank(g_ctx, a->acc, a->order == 1 ? DNAGPU_ORDER_COUNT_DESC : DNAGPU_ORDER_COUNT_ASC, &a->ranking)))
+        return false;
     a->finished = true;
+    return true;
+}
+
+bool count_kmers_agg_order(CountKmersAgg *a, bool descending)
+{
+    if (a->finished || a->failed) {
+        ereport_error("count_kmers_agg_order: called after the first row was served or the aggregate failed");
+        return false;
+    }
+    a->order = descending ? 1 : 2;
+    a->top_limit = 0;
     return true;
 }
 
@@ -853,6 +894,7 @@ bool count_kmers_agg_top(CountKmersAgg *a, int64_t limit)
         return false;
     }
     a->top_limit = (uint64_t)limit;
+    a->order = 0;
     return true;
 }
 
@@ -868,7 +910,10 @@ bool count_kmers_agg_next(CountKmersAgg *a, Kmer *kmer, int64_t *count)
         return false;
     if (a->next >= a->win_first + a->win_count) {
         uint64_t n = a->serve_n - a->next < CK_WINDOW ? a->serve_n - a->next : CK_WINDOW;
-        if (!gpu_ok(dnagpu_acc_download(g_ctx, a->acc, a->next, n, a->keys, a->counts))) {
+        if (a->ranking && n > CK_RANK_WINDOW)
+            n = CK_RANK_WINDOW;
+        if (!gpu_ok(a->ranking ? dnagpu_ranking_read(g_ctx, a->ranking, a->next, n, a->keys, a->counts, 0)
+                               : dnagpu_acc_download(g_ctx, a->acc, a->next, n, a->keys, a->counts))) {
             a->failed = true;
             return false;
         }
@@ -895,6 +940,8 @@ void count_kmers_agg_end(CountKmersAgg *a)
 {
     if (!a)
         return;
+    if (a->ranking)
+        dnagpu_ranking_free(g_ctx, a->ranking);
     if (a->acc)
         dnagpu_acc_free(g_ctx, a->acc);
     free(a->words);

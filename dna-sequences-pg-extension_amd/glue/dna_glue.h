@@ -108,6 +108,12 @@ void count_kmers_end(CountKmers *c);
  * descending, kmers ascending among equal counts; count_kmers_totals still covers every group.  limit < 1 or >
  * DNAGPU_TOP_MAX: NULL and dna_glue_errmsg().  One device (dna_glue_set_device) whatever dna_glue_set_gpus asked for. */
 CountKmers *count_kmers_top_begin(Dna *dna, int k, int64_t limit);
+/* ... GROUP BY k.kmer ORDER BY count(*) DESC (descending) or ORDER BY count(*) (the rarest first) with NO LIMIT -- test.sql:95
+ * as written: count_kmers_ordered(dna, int, bool) RETURNS SETOF (kmer, bigint), which replaces the planner's Sort node above
+ * count_kmers.  The groups are counted, ranked on the device (dnagpu_hist_rank) and the histogram is freed; count_kmers_next
+ * then serves EVERY group in count order, read from the ranking in windows of at most 2^20 rows (dnagpu_ranking_read); the
+ * order among equal counts is unspecified.  count_kmers_totals still covers every group.  One device, as count_kmers_top_begin. */
+CountKmers *count_kmers_ordered_begin(Dna *dna, int k, bool descending);
 /* the k-mer spectrum of a count: bins[c - 1] = groups with count c, bins[n_bins - 1] = groups with count >= n_bins
  * (test.sql:112-114 is bins[0]); dnagpu_hist_spectrum.  false + dna_glue_errmsg() on an ERROR. */
 bool count_kmers_spectrum(const CountKmers *c, int64_t *bins, int n_bins);
@@ -130,6 +136,10 @@ void count_kmers_agg_end(CountKmersAgg *a);
 /* ... ORDER BY count(*) DESC LIMIT limit over the aggregate (dnagpu_acc_top): called before the first count_kmers_agg_next,
  * which then serves those rows only; false + dna_glue_errmsg() for a bad limit (as count_kmers_top_begin) or a late call */
 bool count_kmers_agg_top(CountKmersAgg *a, int64_t limit);
+/* ... ORDER BY count(*) [DESC] with no LIMIT over the aggregate (dnagpu_acc_rank): called before the first
+ * count_kmers_agg_next, which then serves every group in count order; false + dna_glue_errmsg() for a late call.  The later
+ * of count_kmers_agg_top and count_kmers_agg_order holds. */
+bool count_kmers_agg_order(CountKmersAgg *a, bool descending);
 /* bases per batch (default 2^30); tests use small values to force many batches */
 void dna_glue_set_agg_flush_bases(uint64_t n);
 

@@ -327,6 +327,42 @@ int dnagpu_hist_top(dnagpu_ctx *ctx, const dnagpu_hist *h, uint64_t n,
 int dnagpu_acc_top(dnagpu_ctx *ctx, const dnagpu_acc *acc, uint64_t n,
                    uint64_t *out_keys, uint64_t *out_counts, uint64_t *n_out, int out_on_device);
 
+/* ---- rank: GROUP BY kmer ORDER BY count(*) [DESC] with NO LIMIT -- every group in count order (test.sql:95 as written),
+ * for any number of groups: top stops at DNAGPU_TOP_MAX rows, and before this the whole order meant downloading every
+ * group and sorting on the host.  The order is made on the device (a counting sort by count class, DESIGN.md 4.10 "Rank").
+ * Snapshot: a dnagpu_ranking owns two dense device arrays of `rows` uint64 each (keys, counts; rows = distinct of the
+ *   source), taken from the context's pool (the stream rule above).  It does not depend on its source afterwards: the
+ *   histogram may be freed, the accumulator may take further adds.  The source is left exactly as it was (its summary, the
+ *   accumulator's download order).
+ * Row order: counts non-increasing (DNAGPU_ORDER_COUNT_DESC) or non-decreasing (DNAGPU_ORDER_COUNT_ASC: the rarest first).
+ *   The order among rows of EQUAL count is unspecified (PostgreSQL promises none) but fixed for the ranking's life, so the
+ *   windows of dnagpu_ranking_read tile the rows exactly once.  This is deliberately weaker than top's key-ascending ties: a
+ *   key sort of a class that holds 10^8 keys is not what this pass is for.
+ * Sources: every source dnagpu_acc_add accepts -- ordered and unordered histograms, histograms of several parts and borrowed
+ *   dnagpu_hist_part views, dnagpu_hist_merge results -- and accumulators with their 64-bit counts.  Count-0 padding slots,
+ *   empty accumulator slots and partitions that hold nothing are never a row; the all-ones key is a key.
+ * An empty source gives a ranking of 0 rows (DNAGPU_OK) whose device arrays are NULL; it holds no device memory.
+ * Errors: an `order` other than the two values is DNAGPU_ERR_BAD_ARG and is checked first (range before missing object); a
+ *   NULL ctx, source or out is DNAGPU_ERR_BAD_ARG; an allocation failure is DNAGPU_ERR_OOM with nothing leaked and *out = NULL.
+ * dnagpu_ranking_rows / _order: 0 for NULL.  dnagpu_ranking_device_keys / _counts: the rows dense, in rank order; counts are
+ *   uint64 (dnagpu_hist_download's widening).
+ * dnagpu_ranking_read: rows [first, first + count) to out_keys / out_counts (either may be NULL; host memory, or device
+ *   memory when out_on_device != 0), by dnagpu_hist_download's window rule: first > rows or count > rows - first is
+ *   DNAGPU_ERR_BAD_ARG; count == 0 or both outputs NULL is DNAGPU_OK; a NULL ctx or r is DNAGPU_ERR_BAD_ARG.  Waits for the copy.
+ * dnagpu_ranking_free returns the arrays to ctx's pool (NULL r: nothing). */
+typedef struct dnagpu_ranking dnagpu_ranking;
+#define DNAGPU_ORDER_COUNT_DESC 0   /* ORDER BY count(*) DESC  (test.sql:95) */
+#define DNAGPU_ORDER_COUNT_ASC  1   /* ORDER BY count(*)       (rarest first) */
+int dnagpu_hist_rank(dnagpu_ctx *ctx, const dnagpu_hist *h, int order, dnagpu_ranking **out);
+int dnagpu_acc_rank(dnagpu_ctx *ctx, const dnagpu_acc *acc, int order, dnagpu_ranking **out);
+uint64_t dnagpu_ranking_rows(const dnagpu_ranking *r);
+int dnagpu_ranking_order(const dnagpu_ranking *r);
+const uint64_t *dnagpu_ranking_device_keys(const dnagpu_ranking *r);
+const uint64_t *dnagpu_ranking_device_counts(const dnagpu_ranking *r);
+int dnagpu_ranking_read(dnagpu_ctx *ctx, const dnagpu_ranking *r, uint64_t first, uint64_t count,
+                        uint64_t *out_keys, uint64_t *out_counts, int out_on_device);
+void dnagpu_ranking_free(dnagpu_ctx *ctx, dnagpu_ranking *r);
+
 /* ---- multi-GPU sharding of the count (one process per GPU; the exchange itself is the
  * caller's collective, e.g. RCCL all-to-all) -------------------------------------------------
  * Step 1 on every rank: the keys of rows [first, first+count) partitioned by owner.  Owner o of
@@ -526,6 +562,11 @@ int dnagpu_kmer_match(dnagpu_ctx *ctx, const uint64_t *keys, uint64_t n, int k,
  * speculative sweep come from a sampled histogram -- one piece of 1024 records in every eight -- instead of the parents' sizes.
  * DNAGPU_DEBUG_SAMPLE1 takes the sampled regions whatever the coarse buckets look like (tests on short sequences). */
 #define DNAGPU_DEBUG_SAMPLE1 512u
+/* dnagpu_*_rank sorts by count class: the groups with a count below the class limit (2048) go straight to their class's
+ * rows, the others (the tail) are sorted in chunks of up to 2^20 rows, peeled off the tail from the largest counts down.
+ * DNAGPU_DEBUG_RANK_SMALL shrinks both limits -- a class limit of 4 counts, a sort chunk of 2048 rows -- so that small inputs
+ * take the tail path and several peels (tests). */
+#define DNAGPU_DEBUG_RANK_SMALL 1024u
 int dnagpu_set_debug(dnagpu_ctx *ctx, unsigned flags);
 
 /* ---- instrumentation ------------------------------------------------------------------------
