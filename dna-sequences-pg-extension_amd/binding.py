@@ -126,6 +126,8 @@ def lib():
     L.dnagpu_count_kmers_unordered.argtypes = [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(vp)]
     L.dnagpu_hist_is_sorted.argtypes = [vp]
     L.dnagpu_count_kmers_batch.argtypes = [vp, vp, u64p, C.c_uint64, C.c_int, C.POINTER(vp)]
+    L.dnagpu_generate_kmers_table.argtypes = [vp, vp, C.c_int, C.POINTER(_FilterC), C.c_uint64, C.c_uint64, vp, vp, vp,
+                                              C.c_uint64, u64p, C.c_int]
     L.dnagpu_dna_set_sequences.argtypes = [vp, vp, u64p, C.c_uint64]
     L.dnagpu_dna_sequences.argtypes = [vp]
     L.dnagpu_dna_sequences.restype = C.c_uint64
@@ -743,6 +745,30 @@ class Context:
         n = C.c_uint64()
         _chk(lib().dnagpu_generate_kmers_filtered(self.h, dna.h, k, C.byref(flt.c), first, count,
                                                   dev_keys, dev_pos, cap, C.byref(n), 1))
+        return n.value
+
+    def generate_kmers_table(self, dna, k, flt=None, first=0, count=None, cap=None, want_keys=True, want_seq=True,
+                             want_pos=True):
+        """rows of a table made resident with Dna.set_sequences (FROM table, LATERAL generate_kmers(sequence, k) [WHERE flt])
+        among stream rows [first, first + count), in table order -> (keys, seq, pos, n_total)"""
+        total = kmer_count(dna.n_bases, k)
+        if count is None:
+            count = max(total - first, 0)
+        if cap is None:
+            cap = count
+        arrs = [np.empty(max(cap, 1), dtype=np.uint64) if w else None for w in (want_keys, want_seq, want_pos)]
+        n = C.c_uint64()
+        _chk(lib().dnagpu_generate_kmers_table(
+            self.h, dna.h, k, C.byref(flt.c) if flt is not None else None, first, count,
+            *[a.ctypes.data if a is not None else None for a in arrs], cap, C.byref(n), 0))
+        m = min(n.value, cap)
+        return tuple(a[:m] if a is not None else None for a in arrs) + (n.value,)
+
+    def generate_kmers_table_device(self, dna, k, flt, first, count, dev_keys=None, dev_seq=None, dev_pos=None, cap=0):
+        """the same into device memory (8-byte aligned addresses or None) -> n_total"""
+        n = C.c_uint64()
+        _chk(lib().dnagpu_generate_kmers_table(self.h, dna.h, k, C.byref(flt.c) if flt is not None else None, first, count,
+                                               dev_keys, dev_seq, dev_pos, cap, C.byref(n), 1))
         return n.value
 
     # ---- GROUP BY

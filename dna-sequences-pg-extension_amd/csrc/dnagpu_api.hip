@@ -1044,6 +1044,101 @@ extern "C" int dnagpu_generate_kmers_filtered(dnagpu_ctx *ctx, const dnagpu_dna 
     });
 }
 
+// The rows of a TABLE of sequences (FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS k(kmer) [WHERE ...],
+// test.sql:140-150, 172-176): the same two sweeps with the in-one-sequence mask, every row labelled with its sequence and
+// its ordinal inside it (filter_kernels.hip: fbt_*).
+extern "C" int dnagpu_generate_kmers_table(dnagpu_ctx *ctx, const dnagpu_dna *dna, int k, const dnagpu_filter *filter,
+                                           uint64_t first, uint64_t count, uint64_t *out_keys, uint64_t *out_seq,
+                                           uint64_t *out_pos, uint64_t cap, uint64_t *n_out, int out_on_device)
+{
+    return guarded([&]() -> int {
+    if (!ctx || !dna || !n_out)
+        return DNAGPU_ERR_BAD_ARG;
+    RC_TRY(check_range(dna, k, first, count));
+    if (dna->n_seqs == 0 && dna->n_bases != 0)
+        return DNAGPU_ERR_BAD_ARG;                 // (no dnagpu_dna_set_sequences before)
+    FilterBits fb;
+    for (int q = 0; q < 4; q++)
+        fb.sets[q] = 0xFFFFFFFFu;                  // no WHERE: N everywhere
+    fb.k = k;
+    bool none = false;
+    int op_error = DNAGPU_OK;                      // the operator's own ERROR, raised only if a table row evaluates it
+    if (filter) {
+        RC_TRY(build_filter_bits(filter, k, false, &fb, &none));          // a malformed filter is always an error
+        FilterBits unused;
+        bool unused_none;
+        op_error = build_filter_bits(filter, k, true, &unused, &unused_none);
+    }
+    *n_out = 0;
+    if (count == 0)
+        return DNAGPU_OK;
+    if (count > 0xFFFFFFFFull)
+        return DNAGPU_ERR_TOO_LARGE;
+    if (none && op_error == DNAGPU_OK)
+        return DNAGPU_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    PoolScope ps(ctx);
+    u32 n_groups = 0, tpg = 0;
+    filter_bits_geometry(count, &n_groups, &tpg);
+    u32 *group_counts = nullptr;
+    RC_TRY(ps.alloc((size_t)n_groups, &group_counts));
+    u32 *hc = reinterpret_cast<u32 *>(ctx->mailbox);
+    auto sum_groups = [&](u64 *total) -> int {
+        HIP_TRY(hipMemcpyAsync(hc, group_counts, (size_t)n_groups * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        *total = 0;
+        for (u32 g = 0; g < n_groups; g++)
+            *total += hc[g];
+        return DNAGPU_OK;
+    };
+    if (op_error != DNAGPU_OK) {
+        // the reference raises the ERROR when the operator is first evaluated: on the window's first table row, if any
+        FilterBits all = fb;
+        for (int q = 0; q < 4; q++)
+            all.sets[q] = 0xFFFFFFFFu;
+        HIP_TRY(launch_table_bits_count(dna->words, dna->n_words, dna->seq_marks, dna->n_mark_words, first, count, all,
+                                        group_counts, ctx->stream));
+        u64 rows = 0;
+        RC_TRY(sum_groups(&rows));
+        return rows ? op_error : DNAGPU_OK;
+    }
+    prof_begin(ctx);
+    prof_mark(ctx, "filter_count");
+    HIP_TRY(launch_table_bits_count(dna->words, dna->n_words, dna->seq_marks, dna->n_mark_words, first, count, fb,
+                                    group_counts, ctx->stream));
+    const bool want = cap > 0 && (out_keys || out_seq || out_pos);
+    if (want && out_on_device) {
+        // both sweeps queued back to back; the total arrives in the pinned mailbox
+        prof_mark(ctx, "filter_write");
+        HIP_TRY(launch_table_bits_write(dna->words, dna->n_words, dna->seq_marks, dna->n_mark_words, dna->seq_starts,
+                                        dna->n_seqs, first, count, fb, group_counts, out_keys, out_seq, out_pos, cap,
+                                        ctx->mailbox, ctx->stream));
+        prof_mark(ctx, "end");
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        prof_end(ctx);
+        *n_out = ctx->mailbox[0];
+        return DNAGPU_OK;
+    }
+    u64 total = 0;
+    RC_TRY(sum_groups(&total));
+    *n_out = total;
+    const u64 nwrite = std::min<u64>(total, cap);
+    if (nwrite == 0 || !want)
+        return DNAGPU_OK;
+    u64 *host[3] = {out_keys, out_seq, out_pos}, *dev[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < 3; i++)
+        if (host[i])
+            RC_TRY(ps.alloc((size_t)nwrite, &dev[i]));
+    HIP_TRY(launch_table_bits_write(dna->words, dna->n_words, dna->seq_marks, dna->n_mark_words, dna->seq_starts, dna->n_seqs,
+                                    first, count, fb, group_counts, dev[0], dev[1], dev[2], nwrite, nullptr, ctx->stream));
+    for (int i = 0; i < 3; i++)
+        if (host[i])
+            HIP_TRY(hipMemcpyAsync(host[i], dev[i], nwrite * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DNAGPU_OK;
+    });
+}
+
 // ------------------------------------------------------------------------------------------------
 // batched operators
 extern "C" int dnagpu_kmer_hash(dnagpu_ctx *ctx, const uint64_t *keys, uint64_t n, uint32_t *out, int on_device)

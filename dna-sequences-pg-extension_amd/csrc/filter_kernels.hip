@@ -327,6 +327,354 @@ __global__ __launch_bounds__(FB_THREADS) void fb_write_kernel(const u64 *__restr
         *total_out = off;
 }
 
+// ================================================================================================
+// The same two sweeps over a TABLE of sequences (dnagpu_generate_kmers_table): the rows of every sequence's own
+// generate_kmers (FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k), test.sql:140-150, 172-176), each with the
+// sequence it came from and its ordinal inside that sequence, in table order.  Kernels of their own, so that the
+// single-sequence kernels above compile to what they were.
+//
+// A stream row is a table row when no sequence starts among the k - 1 bases behind its first base (batch_keys_kernel's
+// rule).  For a thread's 32 rows that is one bit-sliced mask from the resident marks; it is ANDed into the match mask, so
+// a row that reaches across a boundary is never counted, listed or looked up.
+
+// the mark words under the 62 bases behind a thread's first row (mw = the word of that row's base)
+struct Marks3 {
+    u32 m0, m1, m2;
+};
+
+__device__ __forceinline__ Marks3 marks_load(const u32 *__restrict__ marks, u64 n_mark_words, u64 mw, u32 fo)
+{
+    Marks3 r;
+    r.m0 = mw < n_mark_words ? marks[mw] : 0u;
+    r.m1 = mw + 1 < n_mark_words ? marks[mw + 1] : 0u;
+    r.m2 = (fo && mw + 2 < n_mark_words) ? marks[mw + 2] : 0u;      // bits fo + 1 .. fo + 62 end in the third word
+    return r;
+}
+
+// bit j = row j of the thread's 32 reaches across a sequence start.  M = the marks of bases p0 + 1 .. p0 + 62 (p0 = the
+// thread's first row); row j is spoiled when any of M's bits j .. j + span - 1 is set (span = k - 1 <= 31): M ORed with
+// shifted copies of itself, the covered width doubling, then one shift for the rest.
+__device__ __forceinline__ u32 spoiled_rows(const Marks3 &r, u32 fo, u32 span)
+{
+    if (span == 0)                                   // k = 1: a row is one base
+        return 0u;
+    const unsigned sh = fo + 1u;                     // 1 .. 32
+    u64 M = ((((u64)r.m1 << 32) | r.m0) >> sh) | ((u64)r.m2 << (64u - sh));
+    u32 c = 1;
+    for (; 2u * c <= span; c *= 2u)                  // wave-uniform, at most four rounds
+        M |= M >> c;
+    M |= M >> (span - c);                            // span - c < c: no gap
+    return (u32)M;
+}
+
+// Index of the first entry of a[lo .. hi) that is > p (hi when there is none), a ascending; by the whole workgroup, every
+// thread gets the answer.  256-ary: every round the threads test the last entries of 256 equal chunks and the answer's
+// chunk becomes the range.  wc: FB_WAVES words of LDS that nothing else uses during the call.
+__device__ __forceinline__ u64 block_upper_bound(const u64 *__restrict__ a, u64 lo, u64 hi, u64 p, u32 *wc)
+{
+    const int tid = threadIdx.x;
+    while (hi > lo) {                                // uniform
+        const u64 step = (hi - lo + FB_THREADS - 1) / FB_THREADS;
+        const u64 c0 = lo + (u64)tid * step;
+        bool le = false;
+        if (c0 < hi) {
+            const u64 c1 = c0 + step < hi ? c0 + step : hi;
+            le = a[c1 - 1] <= p;
+        }
+        const u32 wcnt = (u32)__popcll(__ballot(le));
+        if ((tid & 63) == 0)
+            wc[tid >> 6] = wcnt;
+        __syncthreads();
+        u32 cnt = 0;
+#pragma unroll
+        for (int w = 0; w < FB_WAVES; w++)
+            cnt += wc[w];
+        __syncthreads();
+        // chunks [0, cnt) lie at or below p; chunk cnt, if it has entries, ends above p
+        u64 nlo = lo + (u64)cnt * step;
+        if (nlo > hi)
+            nlo = hi;
+        u64 nhi = nlo + step < hi ? nlo + step : hi;
+        if (nhi > nlo)
+            nhi--;
+        lo = nlo;
+        hi = nhi;
+    }
+    return lo;
+}
+
+// ---- sweep 1 over a table: matching table rows per workgroup range
+__global__ __launch_bounds__(FB_THREADS) void fbt_count_kernel(const u64 *__restrict__ words, u64 n_words,
+                                                               const u32 *__restrict__ marks, u64 n_mark_words, u64 first,
+                                                               u64 count, FilterBits fb, u32 tiles_per_group,
+                                                               u32 *__restrict__ group_counts)
+{
+    __shared__ u32 wsum[FB_WAVES];
+    const u32 s0 = fb.sets[0], s1 = fb.sets[1], s2 = fb.sets[2], s3 = fb.sets[3];
+    const u32 fo = (u32)(first & 31), span = (u32)fb.k - 1u;
+    const unsigned sh = fo * 2;
+    const u64 w_first = first >> 5;
+    const u64 n_tiles = (count + FB_TILE - 1) / FB_TILE;
+    u64 t0 = (u64)blockIdx.x * tiles_per_group, t1 = t0 + tiles_per_group;
+    if (t1 > n_tiles)
+        t1 = n_tiles;
+    u32 c = 0;
+    u64 w = w_first + t0 * (FB_TILE / 32) + threadIdx.x;
+    Words3 nxt = words_load(words, n_words, w, sh);
+    Marks3 mnxt = marks_load(marks, n_mark_words, w, fo);
+    for (u64 t = t0; t < t1; t++) {
+        const Words3 cur = nxt;
+        const Marks3 mcur = mnxt;
+        if (t + 1 < t1) {
+            w = w_first + (t + 1) * (FB_TILE / 32) + threadIdx.x;
+            nxt = words_load(words, n_words, w, sh);
+            mnxt = marks_load(marks, n_mark_words, w, fo);
+        }
+        const u64 row0 = t * FB_TILE + (u64)threadIdx.x * FB_ROWS;
+        const u64 m = match_rows(stream_of(cur, sh), s0, s1, s2, s3) & valid_rows(row0 < count ? (long long)(count - row0) : 0);
+        c += (u32)__popc(compact_even(m) & ~spoiled_rows(mcur, fo, span));
+    }
+    c = wave_sum(c);
+    if ((threadIdx.x & 63) == 0)
+        wsum[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u32 g = 0;
+        for (int wv = 0; wv < FB_WAVES; wv++)
+            g += wsum[wv];
+        group_counts[blockIdx.x] = g;
+    }
+}
+
+// ---- sweep 2 over a table: keys, sequences and ordinals in table order
+// The sequence of a row at stream position p is the LAST sequence that starts at or before p (an upper bound over
+// seq_starts, minus one: of a run of equal starts -- empty sequences -- only the last one has bases).  Nothing searches
+// all n_seqs + 1 starts per row: the workgroup finds the bound of its first position once (block_upper_bound); every tile
+// then reads the 256 starts from its lower bound on into LDS, counts those at or below its last position -- that is its
+// upper bound, unless all 256 are, which takes another block_upper_bound (sequences shorter than 32 bases on average) --
+// and every LISTED row searches between the tile's two bounds: in LDS, or in global memory when they are more than 256
+// apart.  One long sequence gives equal bounds and no search.
+// WIDE: the arrays asked for are 16-byte aligned at the same index parity `par`.
+constexpr u32 FBT_STARTS = FB_THREADS;               // starts of a tile held in LDS
+template <bool WIDE>
+__global__ __launch_bounds__(FB_THREADS) void fbt_write_kernel(const u64 *__restrict__ words, u64 n_words,
+                                                               const u32 *__restrict__ marks, u64 n_mark_words,
+                                                               const u64 *__restrict__ seq_starts, u64 n_seqs, u64 first,
+                                                               u64 count, u64 mask, FilterBits fb, u32 tiles_per_group,
+                                                               const u32 *__restrict__ group_counts,
+                                                               u64 *__restrict__ out_keys, u64 *__restrict__ out_seq,
+                                                               u64 *__restrict__ out_pos, u64 cap, u32 par,
+                                                               u64 *__restrict__ total_out)
+{
+    __shared__ unsigned short list[FB_TILE];         // tile-local rows of the listed table rows, in row order
+    __shared__ u64 wsh[FB_THREADS + 2];              // the tile's packed words: keys are cut from here
+    __shared__ u64 sst[FBT_STARTS + 1];              // seq_starts[lo - 1 .. lo + 256) of the tile's lower bound lo
+    __shared__ u32 wtot[FB_WAVES], wle[FB_WAVES], wub[FB_WAVES];
+    __shared__ u64 base_sh;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+    // listed rows before this workgroup's range
+    {
+        u32 part = 0;
+        for (u32 g = tid; g < blockIdx.x; g += FB_THREADS)
+            part += group_counts[g];
+        part = wave_sum(part);
+        if (lane == 0)
+            wtot[wave] = part;
+        __syncthreads();
+        if (tid == 0) {
+            u64 b = 0;
+            for (int w = 0; w < FB_WAVES; w++)
+                b += wtot[w];
+            base_sh = b;
+        }
+        __syncthreads();
+    }
+    u64 off = base_sh;
+
+    const u32 s0 = fb.sets[0], s1 = fb.sets[1], s2 = fb.sets[2], s3 = fb.sets[3];
+    const u32 fo = (u32)(first & 31), span = (u32)fb.k - 1u;
+    const unsigned sh = fo * 2;
+    const u64 w_first = first >> 5;
+    const u64 n_tiles = (count + FB_TILE - 1) / FB_TILE;
+    u64 t0 = (u64)blockIdx.x * tiles_per_group, t1 = t0 + tiles_per_group;
+    if (t1 > n_tiles)
+        t1 = n_tiles;
+    const bool locate = out_seq || out_pos;          // uniform
+    // seq_starts[0 .. ub_lo) lie at or below every position of the tile: entry 0 is 0, entry n_seqs is above every row
+    u64 ub_lo = 1;
+    if (locate && t0 < t1)
+        ub_lo = block_upper_bound(seq_starts, 1, n_seqs, first + t0 * FB_TILE, wub);
+
+    u64 w = w_first + t0 * (FB_TILE / 32) + tid;
+    Words3 nxt = words_load(words, n_words, w, sh);
+    Marks3 mnxt = marks_load(marks, n_mark_words, w, fo);
+    for (u64 t = t0; t < t1; t++) {
+        const u64 tile_row0 = t * FB_TILE;
+        const u64 row0 = tile_row0 + (u64)tid * FB_ROWS;
+        const Words3 cur = nxt;
+        const Marks3 mcur = mnxt;
+        if (t + 1 < t1) {
+            w = w_first + (t + 1) * (FB_TILE / 32) + tid;
+            nxt = words_load(words, n_words, w, sh);
+            mnxt = marks_load(marks, n_mark_words, w, fo);
+        }
+        // the starts from the lower bound on, and how many of them the tile's last position has reached
+        const u64 p_last = first + (tile_row0 + FB_TILE < count ? tile_row0 + FB_TILE : count) - 1;
+        u64 sv = ~(u64)0, sv_lo = 0;
+        if (locate) {
+            if (ub_lo + (u64)tid <= n_seqs)
+                sv = seq_starts[ub_lo + tid];
+            sv_lo = seq_starts[ub_lo - 1];
+        }
+        const u32 nle = (u32)__popcll(__ballot(sv <= p_last));
+        u32 m = compact_even(match_rows(stream_of(cur, sh), s0, s1, s2, s3) &
+                             valid_rows(row0 < count ? (long long)(count - row0) : 0)) &
+                ~spoiled_rows(mcur, fo, span);
+        const u32 c = (u32)__popc(m);
+        const u32 inc = wave_incl_scan(c);
+        if (lane == 63)
+            wtot[wave] = inc;
+        if (lane == 0)
+            wle[wave] = nle;
+        __syncthreads();                             // also: the previous tile's list, words and starts have been read
+        u32 wbase = 0, tile_cnt = 0, n_le = 0;
+#pragma unroll
+        for (int wv = 0; wv < FB_WAVES; wv++) {
+            const u32 v = wtot[wv];
+            wbase += wv < wave ? v : 0u;
+            tile_cnt += v;
+            n_le += wle[wv];
+        }
+        wsh[tid] = cur.w0;
+        if (tid == FB_THREADS - 1) {
+            wsh[FB_THREADS] = cur.w1;
+            wsh[FB_THREADS + 1] = cur.w2;
+        }
+        sst[1 + tid] = sv;
+        if (tid == 0)
+            sst[0] = sv_lo;
+        u64 ub_hi = ub_lo + n_le;
+        if (locate && n_le == FBT_STARTS && ub_hi <= n_seqs)     // uniform
+            ub_hi = block_upper_bound(seq_starts, ub_hi, n_seqs, p_last, wub);
+        const u64 n_between = ub_hi - ub_lo;
+        u32 r = wbase + inc - c;
+        const u32 row_in_tile = (u32)tid * FB_ROWS;
+        while (m) {
+            const u32 j = (u32)__builtin_ctz(m);
+            m &= m - 1;
+            list[r++] = (unsigned short)(row_in_tile + j);
+        }
+        __syncthreads();
+
+        // key of tile-local row r: bits [2q, 2q + 2k) of the tile's words, q = r + first % 32
+        auto key_of = [&](u32 row) -> u64 {
+            const u32 q = row + fo;
+            return funnel(wsh[q >> 5], wsh[(q >> 5) + 1], (q & 31u) * 2u) & mask;
+        };
+        // sequence and ordinal of the row at stream position p
+        auto locate_row = [&](u64 p, u64 &sq, u64 &ord) {
+            if (n_between <= FBT_STARTS) {
+                u32 lo = 0, n = (u32)n_between;
+                while (n) {
+                    const u32 half = n >> 1;
+                    if (sst[1 + lo + half] <= p) {
+                        lo += half + 1;
+                        n -= half + 1;
+                    } else {
+                        n = half;
+                    }
+                }
+                sq = ub_lo - 1 + lo;
+                ord = p - sst[lo];
+            } else {
+                u64 lo = ub_lo, n = n_between;
+                while (n) {
+                    const u64 half = n >> 1;
+                    if (seq_starts[lo + half] <= p) {
+                        lo += half + 1;
+                        n -= half + 1;
+                    } else {
+                        n = half;
+                    }
+                }
+                sq = lo - 1;
+                ord = p - seq_starts[lo - 1];
+            }
+        };
+        if (WIDE) {
+            // slot pairs (s, s+1) with (off + s + par) even: 16-byte aligned in every array
+            const int lead = (int)((off + par) & 1);
+            for (int s = 2 * tid - lead; s < (int)tile_cnt; s += 2 * FB_THREADS) {
+                const bool v0 = s >= 0, v1 = s + 1 < (int)tile_cnt;
+                const u32 r0 = v0 ? list[s] : 0u, r1 = v1 ? list[s + 1] : 0u;
+                const u64 p0 = first + tile_row0 + r0, p1 = first + tile_row0 + r1;
+                const u64 i0 = off + (u64)(long long)s;
+                ull2_t kv = {0, 0}, qv = {0, 0}, ov = {0, 0};
+                if (out_keys) {
+                    kv.x = key_of(r0);
+                    kv.y = key_of(r1);
+                }
+                if (locate) {
+                    u64 a, b;
+                    locate_row(p0, a, b);
+                    qv.x = a;
+                    ov.x = b;
+                    locate_row(p1, a, b);
+                    qv.y = a;
+                    ov.y = b;
+                }
+                if (v0 && v1 && i0 + 1 < cap) {
+                    if (out_keys)
+                        __builtin_nontemporal_store(kv, reinterpret_cast<ull2_t *>(out_keys + i0));
+                    if (out_seq)
+                        __builtin_nontemporal_store(qv, reinterpret_cast<ull2_t *>(out_seq + i0));
+                    if (out_pos)
+                        __builtin_nontemporal_store(ov, reinterpret_cast<ull2_t *>(out_pos + i0));
+                } else {
+                    if (v0 && i0 < cap) {
+                        if (out_keys)
+                            __builtin_nontemporal_store(kv.x, &out_keys[i0]);
+                        if (out_seq)
+                            __builtin_nontemporal_store(qv.x, &out_seq[i0]);
+                        if (out_pos)
+                            __builtin_nontemporal_store(ov.x, &out_pos[i0]);
+                    }
+                    if (v1 && i0 + 1 < cap) {
+                        if (out_keys)
+                            __builtin_nontemporal_store(kv.y, &out_keys[i0 + 1]);
+                        if (out_seq)
+                            __builtin_nontemporal_store(qv.y, &out_seq[i0 + 1]);
+                        if (out_pos)
+                            __builtin_nontemporal_store(ov.y, &out_pos[i0 + 1]);
+                    }
+                }
+            }
+        } else {
+            for (u32 s = tid; s < tile_cnt; s += FB_THREADS) {
+                const u32 r0 = list[s];
+                const u64 i0 = off + s;
+                if (i0 < cap) {
+                    if (out_keys)
+                        __builtin_nontemporal_store(key_of(r0), &out_keys[i0]);
+                    if (locate) {
+                        u64 a, b;
+                        locate_row(first + tile_row0 + r0, a, b);
+                        if (out_seq)
+                            __builtin_nontemporal_store(a, &out_seq[i0]);
+                        if (out_pos)
+                            __builtin_nontemporal_store(b, &out_pos[i0]);
+                    }
+                }
+            }
+        }
+        off += tile_cnt;
+        ub_lo = ub_hi;                               // at or below the next tile's first position
+    }
+    if (total_out && blockIdx.x == gridDim.x - 1 && tid == 0)
+        *total_out = off;
+}
+
 // groups of the two sweeps for `count` rows: every group takes the same number of consecutive tiles
 void filter_bits_geometry(u64 count, u32 *n_groups, u32 *tiles_per_group)
 {
@@ -387,6 +735,51 @@ hipError_t launch_filter_bits_write(const u64 *words, u64 n_words, u64 first, u6
     else
         launch_write_variant<false, true>(wide, grid, s, words, n_words, first, count, mask, fb, tpw, group_counts,
                                           out_keys, out_pos, cap, par, total_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_table_bits_count(const u64 *words, u64 n_words, const u32 *marks, u64 n_mark_words, u64 first, u64 count,
+                                   const FilterBits &fb, u32 *group_counts, hipStream_t s)
+{
+    if (count == 0)
+        return hipSuccess;
+    u32 groups, tpg;
+    filter_bits_geometry(count, &groups, &tpg);
+    hipLaunchKernelGGL(fbt_count_kernel, dim3(groups), dim3(FB_THREADS), 0, s, words, n_words, marks, n_mark_words, first, count,
+                       fb, tpg, group_counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_table_bits_write(const u64 *words, u64 n_words, const u32 *marks, u64 n_mark_words, const u64 *seq_starts,
+                                   u64 n_seqs, u64 first, u64 count, const FilterBits &fb, const u32 *group_counts,
+                                   u64 *out_keys, u64 *out_seq, u64 *out_pos, u64 cap, u64 *total_out, hipStream_t s)
+{
+    if (count == 0)
+        return hipSuccess;
+    u32 groups, tpg;
+    filter_bits_geometry(count, &groups, &tpg);
+    // 16-byte stores need every array asked for 8-byte aligned, all at the same index parity at 16-byte boundaries
+    const uintptr_t a[3] = {reinterpret_cast<uintptr_t>(out_keys), reinterpret_cast<uintptr_t>(out_seq),
+                            reinterpret_cast<uintptr_t>(out_pos)};
+    uintptr_t ref = 0;
+    bool wide = true;
+    for (uintptr_t x : a) {
+        if (!x)
+            continue;
+        if (!ref)
+            ref = x;
+        wide = wide && (x & 7) == 0 && ((x ^ ref) & 15) == 0;
+    }
+    const u32 par = (u32)((ref >> 3) & 1);
+    const u64 mask = kmer_mask(fb.k);
+    if (wide)
+        hipLaunchKernelGGL((fbt_write_kernel<true>), dim3(groups), dim3(FB_THREADS), 0, s, words, n_words, marks, n_mark_words,
+                           seq_starts, n_seqs, first, count, mask, fb, tpg, group_counts, out_keys, out_seq, out_pos, cap, par,
+                           total_out);
+    else
+        hipLaunchKernelGGL((fbt_write_kernel<false>), dim3(groups), dim3(FB_THREADS), 0, s, words, n_words, marks, n_mark_words,
+                           seq_starts, n_seqs, first, count, mask, fb, tpg, group_counts, out_keys, out_seq, out_pos, cap, par,
+                           total_out);
     return hipGetLastError();
 }
 

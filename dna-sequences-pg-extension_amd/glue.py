@@ -99,6 +99,16 @@ def lib():
         L.count_kmers_ordered_begin.argtypes = [vp, C.c_int, C.c_bool]
         L.count_kmers_agg_order.restype = C.c_bool
         L.count_kmers_agg_order.argtypes = [vp, C.c_bool]
+        L.table_kmers_begin.restype = vp
+        L.table_kmers_begin.argtypes = [C.c_int, C.c_char, C.POINTER(_Kmer), C.POINTER(_Qkmer)]
+        L.table_kmers_add.restype = C.c_bool
+        L.table_kmers_add.argtypes = [vp, vp]
+        L.table_kmers_next.restype = C.c_bool
+        L.table_kmers_next.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_Kmer)]
+        L.table_kmers_failed.restype = C.c_bool
+        L.table_kmers_failed.argtypes = [vp]
+        L.table_kmers_end.restype = None
+        L.table_kmers_end.argtypes = [vp]
         _LIB = L
     return _LIB
 
@@ -339,3 +349,35 @@ def count_kmers_agg(rows, k, _top=None, _order=None):
         return out, (t.value, dd.value, u.value)
     finally:
         lib().count_kmers_agg_end(a)
+
+
+def table_kmers(rows, k, op=None, rhs=None):
+    """SELECT <row ordinal>, k.kmer FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS k(kmer) [WHERE <op>]
+    (test.sql:172-176; op in None, '=', '^@', '@>' as generate_kmers_where): rows = the table's `dna` values (or their text)
+    -> (seq int64[], pos int64[], keys uint64[]) in table order"""
+    import numpy as np
+    if op is None:
+        t = lib().table_kmers_begin(k, b"\0", None, None)
+    elif op == "@>":
+        t = lib().table_kmers_begin(k, b"@", None, C.byref(rhs.c))
+    else:
+        t = lib().table_kmers_begin(k, b"=" if op == "=" else b"^", C.byref(rhs.c), None)
+    if not t:
+        raise _err()
+    try:
+        for r in rows:
+            if isinstance(r, str):
+                r = dna(r)
+            if not lib().table_kmers_add(t, r.p):
+                raise _err()
+        seq, pos, keys = [], [], []
+        sq, ps, km = C.c_int64(), C.c_int64(), _Kmer()
+        while lib().table_kmers_next(t, C.byref(sq), C.byref(ps), C.byref(km)):
+            seq.append(sq.value)
+            pos.append(ps.value)
+            keys.append(km.bit_sequence)
+        if lib().table_kmers_failed(t):
+            raise _err()
+        return np.array(seq, dtype=np.int64), np.array(pos, dtype=np.int64), np.array(keys, dtype=np.uint64)
+    finally:
+        lib().table_kmers_end(t)

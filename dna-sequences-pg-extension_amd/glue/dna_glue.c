@@ -809,6 +809,21 @@ static bool agg_flush(CountKmersAgg *a)
     return ok;
 }
 
+/* one more row behind the batch's rows: its bases onto the packed stream, its end as the next start */
+static bool batch_append(uint64_t **words, uint64_t *n_bases, uint64_t *cap_words, uint64_t **starts, uint64_t *n_seqs,
+                         uint64_t *cap_seqs, const Dna *row)
+{
+    const uint64_t len = row->length;
+    if (!agg_grow((void **)words, cap_words, (*n_bases + len + 31) / 32 + 1) || !agg_grow((void **)starts, cap_seqs, *n_seqs + 2))
+        return false;
+    (*starts)[0] = 0;
+    if (len)
+        append_bases(*words, *n_bases, row->bit_sequence, len);
+    *n_bases += len;
+    (*starts)[++*n_seqs] = *n_bases;
+    return true;
+}
+
 bool count_kmers_agg_add(CountKmersAgg *a, const Dna *row)
 {
     if (a->finished || a->failed) {
@@ -820,16 +835,10 @@ bool count_kmers_agg_add(CountKmersAgg *a, const Dna *row)
         a->failed = true;
         return false;
     }
-    if (!agg_grow((void **)&a->words, &a->cap_words, (a->n_bases + len + 31) / 32 + 1) ||
-        !agg_grow((void **)&a->starts, &a->cap_seqs, a->n_seqs + 2)) {
+    if (!batch_append(&a->words, &a->n_bases, &a->cap_words, &a->starts, &a->n_seqs, &a->cap_seqs, row)) {
         a->failed = true;
         return false;
     }
-    a->starts[0] = 0;
-    if (len)
-        append_bases(a->words, a->n_bases, row->bit_sequence, len);
-    a->n_bases += len;
-    a->starts[++a->n_seqs] = a->n_bases;
     if (a->n_bases >= g_agg_flush_bases && !agg_flush(a)) {
         a->failed = true;
         return false;
@@ -949,4 +958,185 @@ void count_kmers_agg_end(CountKmersAgg *a)
     free(a->keys);
     free(a->counts);
     free(a);
+}
+
+/* ------------------------------------------------------------------ the ROWS of a table: kmers_of_table */
+
+#define TK_WINDOW ((uint64_t)1 << 20)     /* stream rows per refill: a window never holds more table rows than stream rows */
+
+typedef struct TableBatch {
+    uint64_t *words, n_bases, cap_words;         /* rows back to back as one packed stream, as the aggregate packs them */
+    uint64_t *starts, n_seqs, cap_seqs;
+    uint64_t first_seq;                          /* ordinal of the batch's first row in the table */
+} TableBatch;
+
+struct TableKmers {
+    int k;
+    bool filtered, started, failed, open;        /* open: the last batch still takes rows */
+    dnagpu_filter filter;
+    TableBatch *batches;
+    uint64_t n_batches, cap_batches, n_rows;     /* n_rows: add calls so far */
+    /* the scan */
+    uint64_t cur;                                /* batch being read */
+    dnagpu_dna *dev;                             /* ... resident, with its sequence set */
+    uint64_t scan_pos, scan_total;               /* stream rows of the batch: next unscanned, all */
+    uint64_t *keys, *seq, *pos, win_count, win_used;
+};
+
+TableKmers *table_kmers_begin(int k, char op, const Kmer *rhs, const Qkmer *rhs_pattern)
+{
+    if (k < 1 || k > 32) {
+        ereport_error("%s", dnagpu_strerror(DNAGPU_ERR_INVALID_K));          /* dna.c:772-773 */
+        return NULL;
+    }
+    TableKmers *t = (TableKmers *)calloc(1, sizeof *t);
+    if (!t) {
+        ereport_error("out of memory");
+        return NULL;
+    }
+    t->k = k;
+    t->filtered = op != 0;
+    switch (op) {
+    case 0:
+        break;
+    case '=':
+    case '^':
+        t->filter.kind = op == '=' ? DNAGPU_FILTER_EQUALS : DNAGPU_FILTER_STARTS_WITH;
+        t->filter.length = rhs->length;
+        t->filter.bits = rhs->bit_sequence;
+        break;
+    case '@':
+        t->filter.kind = DNAGPU_FILTER_CONTAINS;
+        strncpy(t->filter.pattern, rhs_pattern->sequence, sizeof t->filter.pattern - 1);
+        break;
+    default:
+        ereport_error("unknown operator");
+        free(t);
+        return NULL;
+    }
+    return t;
+}
+
+bool table_kmers_add(TableKmers *t, const Dna *row)
+{
+    if (t->started || t->failed) {
+        ereport_error("table_kmers: row added after the first row was served or the scan failed");
+        return false;
+    }
+    TableBatch *b = t->open ? &t->batches[t->n_batches - 1] : NULL;
+    if (b && b->n_seqs > 0 && b->n_bases + row->length > g_agg_flush_bases)      /* a long row: a batch of its own */
+        b = NULL;
+    if (!b) {
+        if (t->n_batches == t->cap_batches) {
+            const uint64_t c = t->cap_batches ? 2 * t->cap_batches : 16;
+            TableBatch *q = (TableBatch *)realloc(t->batches, (size_t)c * sizeof *q);
+            if (!q) {
+                ereport_error("out of memory");
+                t->failed = true;
+                return false;
+            }
+            t->batches = q;
+            t->cap_batches = c;
+        }
+        b = &t->batches[t->n_batches++];
+        memset(b, 0, sizeof *b);
+        b->first_seq = t->n_rows;
+    }
+    if (!batch_append(&b->words, &b->n_bases, &b->cap_words, &b->starts, &b->n_seqs, &b->cap_seqs, row)) {
+        t->failed = true;
+        return false;
+    }
+    t->n_rows++;
+    t->open = b->n_bases < g_agg_flush_bases;
+    return true;
+}
+
+static void tk_drop_device(TableKmers *t)
+{
+    if (t->dev)
+        dnagpu_dna_free(g_ctx, t->dev);
+    t->dev = NULL;
+}
+
+/* batch t->cur onto the device with its boundaries; false = ERROR */
+static bool tk_open_batch(TableKmers *t)
+{
+    const TableBatch *b = &t->batches[t->cur];
+    t->scan_pos = 0;
+    t->scan_total = b->n_bases >= (uint64_t)t->k ? b->n_bases - (uint64_t)t->k + 1 : 0;
+    if (t->scan_total == 0)
+        return true;
+    return ctx() != NULL && gpu_ok(dnagpu_dna_upload(g_ctx, b->words, b->n_bases, &t->dev)) &&
+           gpu_ok(dnagpu_dna_set_sequences(g_ctx, t->dev, b->starts, b->n_seqs));
+}
+
+bool table_kmers_next(TableKmers *t, int64_t *seq, int64_t *pos, Kmer *out)
+{
+    if (t->failed)
+        return false;
+    if (!t->started) {
+        t->started = true;
+        t->keys = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)TK_WINDOW);
+        t->seq = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)TK_WINDOW);
+        t->pos = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)TK_WINDOW);
+        if (!t->keys || !t->seq || !t->pos) {
+            ereport_error("out of memory");
+            t->failed = true;
+            return false;
+        }
+        if (t->n_batches && !tk_open_batch(t)) {
+            t->failed = true;
+            return false;
+        }
+    }
+    while (t->win_used >= t->win_count) {                                 /* the next window with rows */
+        if (t->cur >= t->n_batches)
+            return false;
+        if (t->scan_pos >= t->scan_total) {                               /* the next batch */
+            tk_drop_device(t);
+            if (++t->cur >= t->n_batches)
+                return false;
+            if (!tk_open_batch(t)) {
+                t->failed = true;
+                return false;
+            }
+            continue;
+        }
+        const uint64_t n = t->scan_total - t->scan_pos < TK_WINDOW ? t->scan_total - t->scan_pos : TK_WINDOW;
+        uint64_t n_out = 0;
+        if (!gpu_ok(dnagpu_generate_kmers_table(g_ctx, t->dev, t->k, t->filtered ? &t->filter : NULL, t->scan_pos, n, t->keys,
+                                                t->seq, t->pos, TK_WINDOW, &n_out, 0))) {
+            t->failed = true;                                             /* the ERROR aborts the statement */
+            return false;
+        }
+        t->scan_pos += n;
+        t->win_count = n_out;
+        t->win_used = 0;
+    }
+    const uint64_t i = t->win_used++;
+    if (seq)
+        *seq = (int64_t)(t->batches[t->cur].first_seq + t->seq[i]);
+    if (pos)
+        *pos = (int64_t)t->pos[i];
+    out->length = t->k;
+    out->bit_sequence = t->keys[i];
+    return true;
+}
+
+bool table_kmers_failed(const TableKmers *t) { return t->failed; }
+
+void table_kmers_end(TableKmers *t)
+{
+    if (!t)
+        return;
+    tk_drop_device(t);
+    for (uint64_t i = 0; i < t->n_batches; i++) {
+        free(t->batches[i].words);
+        free(t->batches[i].starts);
+    }
+    free(t->batches);
+    free(t->keys);
+    free(t->seq);
+    free(t->pos);
+    free(t);
 }

@@ -143,6 +143,25 @@ bool count_kmers_agg_order(CountKmersAgg *a, bool descending);
 /* bases per batch (default 2^30); tests use small values to force many batches */
 void dna_glue_set_agg_flush_bases(uint64_t n);
 
+
+/* ---- SELECT d.id, k.kmer FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS k(kmer) [WHERE <op>]: the ROWS of
+ * a table (what test.sql:172-176 inserts into kmer_data_t, and the WHERE forms test.sql:187-262 asks of that column) as one
+ * set-returning scan, kmers_of_table ----
+ * begin: op 0 = no WHERE; '=', '^', '@' as generate_kmers_where_begin (NULL + dna_glue_errmsg() on a bad k: dna.c:773);
+ * add = one call per row of the table, in order (packed on the host as count_kmers_agg_add packs them); next = one row:
+ * seq = the 0-based ordinal of the add call the k-mer came from, pos = its ordinal inside that row's generate_kmers, in table
+ * order.  At the first next the table goes to the device in batches of at most the aggregate's flush size
+ * (dna_glue_set_agg_flush_bases; a row longer than that is a batch of its own), each made resident
+ * (dnagpu_dna_upload + dnagpu_dna_set_sequences) and read in windows of at most 2^20 stream rows
+ * (dnagpu_generate_kmers_table).  The operator ERRORs (dna.c:854-856, 1106-1108) come at the first next, if the table has a
+ * row at all; false from next = done, or an ERROR: table_kmers_failed. */
+typedef struct TableKmers TableKmers;
+TableKmers *table_kmers_begin(int k, char op, const Kmer *rhs, const Qkmer *rhs_pattern);
+bool table_kmers_add(TableKmers *t, const Dna *row);
+bool table_kmers_next(TableKmers *t, int64_t *seq, int64_t *pos, Kmer *out);
+bool table_kmers_failed(const TableKmers *t);
+void table_kmers_end(TableKmers *t);
+
 #ifdef __cplusplus
 }
 #endif

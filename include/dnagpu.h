@@ -34,7 +34,7 @@ extern "C" {
 /* 2: histograms of several parts (dnagpu_hist_parts: what dnagpu_count_multi_unordered returns with its default of three
  * bucket groups per owner -- dnagpu_hist_device_keys / _counts are NULL for those), the dnagpu_multi_* options, the
  * table-of-sequences count (dnagpu_count_kmers_batch, dnagpu_dna_set_sequences + dnagpu_count_kmers_table,
- * dnagpu_hist_merge) */
+ * dnagpu_hist_merge), the rows of a table of sequences with the fused WHERE forms (dnagpu_generate_kmers_table) */
 #define DNAGPU_ABI_VERSION 2
 
 /* ---- status codes ------------------------------------------------------------------------
@@ -212,6 +212,36 @@ int dnagpu_count_kmers_batch(dnagpu_ctx *ctx, const dnagpu_dna *dna, const uint6
 int dnagpu_dna_set_sequences(dnagpu_ctx *ctx, dnagpu_dna *dna, const uint64_t *seq_starts, uint64_t n_seqs);
 uint64_t dnagpu_dna_sequences(const dnagpu_dna *dna);
 int dnagpu_count_kmers_table(dnagpu_ctx *ctx, const dnagpu_dna *dna, int k, dnagpu_hist **out);
+/* The ROWS of the same table -- FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS k(kmer) [WHERE <op>]: the
+ * k-mers of every sequence, each with the sequence it came from (what test.sql:172-176 inserts into kmer_data_t), and the
+ * three WHERE forms over them (test.sql:187-262 asks them of that stored column, whose row ids are this order).
+ * Input: a table made resident with dnagpu_dna_set_sequences; a non-empty stream without a set is DNAGPU_ERR_BAD_ARG
+ *   (dnagpu_count_kmers_table's rule).
+ * Window: [first, first + count) are rows of the STREAM, under dnagpu_generate_kmers_filtered's range rule: stream row p is
+ *   the window of k bases at base p of the packed stream.  More than 2^32 - 1 stream rows in one call: DNAGPU_ERR_TOO_LARGE.
+ *   A caller with buffers of cap rows pages with windows of cap stream rows (a window never holds more table rows than
+ *   stream rows).
+ * Table rows: stream row p is a table row when it lies inside one sequence: with s the sequence for which
+ *   seq_starts[s] <= p < seq_starts[s+1], p + k <= seq_starts[s+1].  These are exactly the rows of every sequence's own
+ *   generate_kmers (dna.c:781, in 64 bits): a sequence shorter than k has none; empty sequences, runs of them included, have
+ *   none and are never an s.
+ * Output: the table rows of the window that satisfy `filter`, in ascending p -- table order: sequence by sequence, position
+ *   order inside a sequence (test.sql:86-92 per sequence).  out_keys[i] = the key, out_seq[i] = s (0-based, global, not
+ *   relative to the window), out_pos[i] = p - seq_starts[s] (the row's ordinal inside its sequence's generate_kmers).  Any
+ *   of the three arrays may be NULL; at most cap rows go to each; *n_out = all matching rows, even beyond cap.  The arrays
+ *   are host memory, or device memory when out_on_device != 0 (8-byte aligned, at any parity relative to each other).
+ * Filter: NULL = no WHERE, every table row matches.  Otherwise the operators of dnagpu_generate_kmers_filtered with its
+ *   rules (EQUALS of another length matches nothing, a 32-base prefix compares 64 bits, 'U' matches nothing, a malformed
+ *   filter -- bad kind, invalid qkmer text -- is always an error), except that the two operator ERRORs,
+ *   DNAGPU_ERR_QKMER_LEN_MISMATCH (dna.c:1106-1108) and DNAGPU_ERR_PREFIX_TOO_LONG (dna.c:854-856), are raised exactly when
+ *   the window holds at least one TABLE row: the reference raises them when the operator is first evaluated, and a window
+ *   whose stream rows all span boundaries evaluates nothing (0 rows, DNAGPU_OK).
+ * Checks, in order: NULL ctx / dna / n_out (DNAGPU_ERR_BAD_ARG), k (DNAGPU_ERR_INVALID_K, dna.c:772-773), the range, the
+ *   missing set, the filter.  count == 0: *n_out = 0, DNAGPU_OK.  The table, its sequence set and the stream are untouched. */
+int dnagpu_generate_kmers_table(dnagpu_ctx *ctx, const dnagpu_dna *dna, int k, const dnagpu_filter *filter,
+                                uint64_t first, uint64_t count,
+                                uint64_t *out_keys, uint64_t *out_seq, uint64_t *out_pos,
+                                uint64_t cap, uint64_t *n_out, int out_on_device);
 /* Same over an arbitrary array of n keys of k bases already in device memory.  dev_keys is used as
  * scratch and its contents are unspecified afterwards. */
 int dnagpu_count_keys(dnagpu_ctx *ctx, uint64_t *dev_keys, uint64_t n, int k, dnagpu_hist **out);
