@@ -542,7 +542,7 @@ extern "C" int dnagpu_count_keys_in_range(dnagpu_ctx *ctx, uint64_t *dev_keys, u
     while (free_bits < nbits && (diff >> free_bits) != 0)
         free_bits++;
     const int fixed = nbits - free_bits;
-    const u64 prefix = free_bits >= 64 ? 0 : (key_min >> free_bits) << free_bits;
+    const u64 prefix = free_bits >= 64 ? 0 : ((key_min & kmer_mask(k)) >> free_bits) << free_bits;
     // a single possible key (fixed == 2k) still runs through the generic path: rem = 0 leaf
     return count_core(ctx, nullptr, 0, n, k, dev_keys, out, fixed, prefix);
     }), out, k);

@@ -1713,16 +1713,22 @@ extern "C" int dnagpu_partition_kmers(dnagpu_ctx *ctx, const dnagpu_dna *dna, in
     return guarded([&]() -> int {
     if (!ctx || !dna || !dev_keys || !owner_offsets || n_owners < 1 || n_owners > (1 << MAX_SPLIT_BITS))
         return DNAGPU_ERR_BAD_ARG;
+    *dev_keys = nullptr;
     RC_TRY(check_range(dna, k, first, count));
+    const int bits = std::min(2 * k, MAX_SPLIT_BITS);
+    if (2 * k == bits) {
+        // the forced level would be terminal: nothing is scattered (children carry key = prefix, count = len); expanding
+        // them is not needed by any caller today: k <= 5 counts run on one GPU.  Refused before any device work
+        set_err("partition: k too small to shard (2k <= %d bits)", MAX_SPLIT_BITS);
+        return DNAGPU_ERR_BAD_ARG;
+    }
     if (count > 0xFFFFFFFFull)
         return DNAGPU_ERR_TOO_LARGE;
     HIP_TRY(hipSetDevice(ctx->device));
-    *dev_keys = nullptr;
     for (int o = 0; o <= n_owners; o++)
         owner_offsets[o] = 0;
     if (count == 0)
         return DNAGPU_OK;
-    const int bits = std::min(2 * k, MAX_SPLIT_BITS);
     const u32 R = 1u << bits;
     prof_begin(ctx);
     PoolScope ps(ctx);
@@ -1739,12 +1745,6 @@ extern "C" int dnagpu_partition_kmers(dnagpu_ctx *ctx, const dnagpu_dna *dna, in
     for (int o = 0; o <= n_owners; o++) {
         u64 d0 = ((u64)o * R + n_owners - 1) / n_owners;
         owner_offsets[o] = d0 >= R ? count : kids[d0].start;
-    }
-    if (2 * k == bits) {
-        // terminal level: nothing was scattered (children carry key = prefix, count = len); expand
-        // is not needed by any caller today: k <= 5 counts run on one GPU
-        set_err("partition: k too small to shard (2k <= %d bits)", MAX_SPLIT_BITS);
-        return DNAGPU_ERR_BAD_ARG;
     }
     ps.release(tr.buf0);
     *dev_keys = tr.buf0;

@@ -246,7 +246,11 @@ int dnagpu_generate_kmers_table(dnagpu_ctx *ctx, const dnagpu_dna *dna, int k, c
  * scratch and its contents are unspecified afterwards. */
 int dnagpu_count_keys(dnagpu_ctx *ctx, uint64_t *dev_keys, uint64_t n, int k, dnagpu_hist **out);
 /* Same, when the caller knows that every key lies in [key_min, key_max] (an owner's key range after
- * the multi-GPU exchange): the bits the two bounds share are not partitioned on again. */
+ * the multi-GPU exchange): the bits the two bounds share are not partitioned on again.  Any range with
+ * key_min <= key_max is valid, aligned to a power of two or not; key_min == key_max is the one-key range (every
+ * key equals it: one group of n rows).  Bits of the two bounds above the 2k key bits are ignored.  A wider range
+ * than the keys need gives the same histogram.  key_min > key_max: DNAGPU_ERR_BAD_ARG; a key outside the range
+ * breaks the promise and the result is then unspecified. */
 int dnagpu_count_keys_in_range(dnagpu_ctx *ctx, uint64_t *dev_keys, uint64_t n, int k,
                                uint64_t key_min, uint64_t key_max, dnagpu_hist **out);
 
@@ -399,6 +403,8 @@ void dnagpu_ranking_free(dnagpu_ctx *ctx, dnagpu_ranking *r);
  * n_owners owns the keys whose top `owner_bits` bits d satisfy (d * n_owners) >> owner_bits == o
  * (contiguous, ascending key ranges).  *dev_keys receives a device buffer of `count` keys grouped
  * by owner, owner_offsets[0..n_owners] the group boundaries.  Free with dnagpu_buffer_free.
+ * 1 <= n_owners <= 1024, else DNAGPU_ERR_BAD_ARG.  k <= 5 is DNAGPU_ERR_BAD_ARG too (the whole key is the owner
+ * digit: such counts run on one GPU); the call is refused before any device work and *dev_keys is NULL.
  * Step 2 (caller): exchange the groups.  Step 3: dnagpu_count_keys on what was received; the
  * concatenation of the owners' downloads in owner order is the global result, keys ascending. */
 /* Alternative without moving keys (the default of sharded.py): every rank holds the whole packed
