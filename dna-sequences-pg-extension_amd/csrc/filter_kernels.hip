@@ -150,196 +150,14 @@ __device__ __forceinline__ u32 compact_even(u64 m)
     return lo | (hi << 16);
 }
 
-// ---- sweep 1: matches per workgroup range ----------------------------------------------------
-__global__ __launch_bounds__(FB_THREADS) void fb_count_kernel(const u64 *__restrict__ words, u64 n_words, u64 first,
-                                                              u64 count, FilterBits fb, u32 tiles_per_group,
-                                                              u32 *__restrict__ group_counts)
-{
-    __shared__ u32 wsum[FB_WAVES];
-    const u32 s0 = fb.sets[0], s1 = fb.sets[1], s2 = fb.sets[2], s3 = fb.sets[3];
-    const unsigned sh = (unsigned)(first & 31) * 2;
-    const u64 w_first = first >> 5;
-    const u64 n_tiles = (count + FB_TILE - 1) / FB_TILE;
-    u64 t0 = (u64)blockIdx.x * tiles_per_group, t1 = t0 + tiles_per_group;
-    if (t1 > n_tiles)
-        t1 = n_tiles;
-    u32 c = 0;
-    // the next tile's words are requested before the current tile is tested
-    Words3 nxt = words_load(words, n_words, w_first + t0 * (FB_TILE / 32) + threadIdx.x, sh);
-    for (u64 t = t0; t < t1; t++) {
-        const Words3 cur = nxt;
-        if (t + 1 < t1)
-            nxt = words_load(words, n_words, w_first + (t + 1) * (FB_TILE / 32) + threadIdx.x, sh);
-        const u64 row0 = t * FB_TILE + (u64)threadIdx.x * FB_ROWS;
-        const u64 m = match_rows(stream_of(cur, sh), s0, s1, s2, s3);
-        c += (u32)__popcll(m & valid_rows(row0 < count ? (long long)(count - row0) : 0));
-    }
-    c = wave_sum(c);
-    if ((threadIdx.x & 63) == 0)
-        wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u32 g = 0;
-        for (int w = 0; w < FB_WAVES; w++)
-            g += wsum[w];
-        group_counts[blockIdx.x] = g;
-    }
-}
-
-// ---- sweep 2: position-ordered keys and positions ---------------------------------------------
-// WIDE: out_keys / out_pos are 16-byte aligned at the same index parity `par`, so two consecutive
-// slots go out as one 16-byte store.
-// (A wave-granular variant -- every wave lists and writes its own 2048 rows, no workgroup barrier -- was
-// measured 8-10 % slower at selectivity 1/4: four times as many, four times shorter output bursts.)
-template <bool HAS_KEYS, bool HAS_POS, bool WIDE>
-__global__ __launch_bounds__(FB_THREADS) void fb_write_kernel(const u64 *__restrict__ words, u64 n_words, u64 first,
-                                                              u64 count, u64 mask, FilterBits fb, u32 tiles_per_group,
-                                                              const u32 *__restrict__ group_counts,
-                                                              u64 *__restrict__ out_keys, u64 *__restrict__ out_pos,
-                                                              u64 cap, u32 par, u64 *__restrict__ total_out)
-{
-    __shared__ unsigned short list[FB_TILE];         // tile-local rows of the matches, in row order
-    __shared__ u64 wsh[FB_THREADS + 2];              // the tile's packed words: keys are cut from here
-    __shared__ u32 wtot[FB_WAVES];
-    __shared__ u64 base_sh;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-
-    // matches before this workgroup's range
-    {
-        u32 part = 0;
-        for (u32 g = tid; g < blockIdx.x; g += FB_THREADS)
-            part += group_counts[g];
-        // partial sums of up to 2^32-1 rows cannot overflow 32 bits in total
-        part = wave_sum(part);
-        if (lane == 0)
-            wtot[wave] = part;
-        __syncthreads();
-        if (tid == 0) {
-            u64 b = 0;
-            for (int w = 0; w < FB_WAVES; w++)
-                b += wtot[w];
-            base_sh = b;
-        }
-        __syncthreads();
-    }
-    u64 off = base_sh;
-
-    const u32 s0 = fb.sets[0], s1 = fb.sets[1], s2 = fb.sets[2], s3 = fb.sets[3];
-    const u32 fo = (u32)(first & 31);
-    const unsigned sh = fo * 2;
-    const u64 w_first = first >> 5;
-    const u64 n_tiles = (count + FB_TILE - 1) / FB_TILE;
-    u64 t0 = (u64)blockIdx.x * tiles_per_group, t1 = t0 + tiles_per_group;
-    if (t1 > n_tiles)
-        t1 = n_tiles;
-    Words3 nxt = words_load(words, n_words, w_first + t0 * (FB_TILE / 32) + tid, sh);
-    for (u64 t = t0; t < t1; t++) {
-        const u64 tile_row0 = t * FB_TILE;
-        const u64 row0 = tile_row0 + (u64)tid * FB_ROWS;
-        const Words3 cur = nxt;
-        if (t + 1 < t1)
-            nxt = words_load(words, n_words, w_first + (t + 1) * (FB_TILE / 32) + tid, sh);
-        u32 m = compact_even(match_rows(stream_of(cur, sh), s0, s1, s2, s3) &
-                             valid_rows(row0 < count ? (long long)(count - row0) : 0));
-        const u32 c = (u32)__popc(m);
-        const u32 inc = wave_incl_scan(c);
-        if (lane == 63)
-            wtot[wave] = inc;
-        __syncthreads();                             // also: the previous tile's list and words have been read
-        u32 wbase = 0, tile_cnt = 0;
-#pragma unroll
-        for (int w = 0; w < FB_WAVES; w++) {
-            const u32 v = wtot[w];
-            wbase += w < wave ? v : 0u;
-            tile_cnt += v;
-        }
-        wsh[tid] = cur.w0;
-        if (tid == FB_THREADS - 1) {
-            wsh[FB_THREADS] = cur.w1;
-            wsh[FB_THREADS + 1] = cur.w2;
-        }
-        u32 r = wbase + inc - c;
-        const u32 row_in_tile = (u32)tid * FB_ROWS;
-        while (m) {
-            const u32 j = (u32)__builtin_ctz(m);
-            m &= m - 1;
-            list[r++] = (unsigned short)(row_in_tile + j);
-        }
-        __syncthreads();
-
-        // key of tile-local row r: bits [2q, 2q + 2k) of the tile's words, q = r + first % 32
-        auto key_of = [&](u32 row) -> u64 {
-            const u32 q = row + fo;
-            return funnel(wsh[q >> 5], wsh[(q >> 5) + 1], (q & 31u) * 2u) & mask;
-        };
-        if (WIDE) {
-            // slot pairs (s, s+1) with (off + s + par) even: 16-byte aligned in both arrays
-            const int lead = (int)((off + par) & 1);
-            for (int s = 2 * tid - lead; s < (int)tile_cnt; s += 2 * FB_THREADS) {
-                const bool v0 = s >= 0, v1 = s + 1 < (int)tile_cnt;
-                const u32 r0 = list[v0 ? s : 0], r1 = list[v1 ? s + 1 : s];
-                const u64 p0 = first + tile_row0 + r0, p1 = first + tile_row0 + r1;
-                const u64 i0 = off + (u64)(long long)s;
-                if (v0 && v1 && i0 + 1 < cap) {
-                    if (HAS_KEYS) {
-                        ull2_t kv;
-                        kv.x = key_of(r0);
-                        kv.y = key_of(r1);
-                        __builtin_nontemporal_store(kv, reinterpret_cast<ull2_t *>(out_keys + i0));
-                    }
-                    if (HAS_POS) {
-                        ull2_t pv;
-                        pv.x = p0;
-                        pv.y = p1;
-                        __builtin_nontemporal_store(pv, reinterpret_cast<ull2_t *>(out_pos + i0));
-                    }
-                } else {
-                    if (v0 && i0 < cap) {
-                        if (HAS_KEYS)
-                            __builtin_nontemporal_store(key_of(r0), &out_keys[i0]);
-                        if (HAS_POS)
-                            __builtin_nontemporal_store(p0, &out_pos[i0]);
-                    }
-                    if (v1 && i0 + 1 < cap) {
-                        if (HAS_KEYS)
-                            __builtin_nontemporal_store(key_of(r1), &out_keys[i0 + 1]);
-                        if (HAS_POS)
-                            __builtin_nontemporal_store(p1, &out_pos[i0 + 1]);
-                    }
-                }
-            }
-        } else {
-            for (u32 s = tid; s < tile_cnt; s += FB_THREADS) {
-                const u32 r0 = list[s];
-                const u64 p0 = first + tile_row0 + r0;
-                const u64 i0 = off + s;
-                if (i0 < cap) {
-                    if (HAS_KEYS)
-                        __builtin_nontemporal_store(key_of(r0), &out_keys[i0]);
-                    if (HAS_POS)
-                        __builtin_nontemporal_store(p0, &out_pos[i0]);
-                }
-            }
-        }
-        off += tile_cnt;
-    }
-    if (total_out && blockIdx.x == gridDim.x - 1 && tid == 0)
-        *total_out = off;
-}
-
-// ================================================================================================
-// The same two sweeps over a TABLE of sequences (dnagpu_generate_kmers_table): the rows of every sequence's own
-// generate_kmers (FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k), test.sql:140-150, 172-176), each with the
-// sequence it came from and its ordinal inside that sequence, in table order.  Kernels of their own, so that the
-// single-sequence kernels above compile to what they were.
-//
+// ---- the rows of a TABLE of sequences (dnagpu_generate_kmers_table) ------------------------------
 // A stream row is a table row when no sequence starts among the k - 1 bases behind its first base (batch_keys_kernel's
 // rule).  For a thread's 32 rows that is one bit-sliced mask from the resident marks; it is ANDed into the match mask, so
 // a row that reaches across a boundary is never counted, listed or looked up.
 
 // the mark words under the 62 bases behind a thread's first row (mw = the word of that row's base)
 struct Marks3 {
-    u32 m0, m1, m2;
+    u32 m0 = 0, m1 = 0, m2 = 0;
 };
 
 __device__ __forceinline__ Marks3 marks_load(const u32 *__restrict__ marks, u64 n_mark_words, u64 mw, u32 fo)
@@ -365,6 +183,297 @@ __device__ __forceinline__ u32 spoiled_rows(const Marks3 &r, u32 fo, u32 span)
         M |= M >> c;
     M |= M >> (span - c);                            // span - c < c: no gap
     return (u32)M;
+}
+
+// ================================================================================================
+// The stages of the two sweeps, written once.  The single-sequence kernels (fb_*) and the table kernels (fbt_*) are
+// made of them; TABLE is a compile-time switch, so a single-sequence kernel holds no trace of the marks.
+
+// what every thread of a sweep derives once from the call's window [first, first + count)
+struct Sweep {
+    u32 s0, s1, s2, s3;                              // fb.sets[], held in scalar registers (positions >= k are N)
+    u32 fo;                                          // first % 32: where the window starts inside its first word
+    unsigned sh;                                     // the same in bits
+    u32 span;                                        // k - 1 (tables)
+    u64 w_first;
+    u64 t0, t1;                                      // the consecutive tiles of this workgroup
+};
+
+__device__ __forceinline__ Sweep sweep_of(u64 first, u64 count, const FilterBits &fb, u32 tiles_per_group)
+{
+    Sweep sw;
+    sw.s0 = fb.sets[0], sw.s1 = fb.sets[1], sw.s2 = fb.sets[2], sw.s3 = fb.sets[3];
+    sw.fo = (u32)(first & 31);
+    sw.sh = sw.fo * 2;
+    sw.span = (u32)fb.k - 1u;
+    sw.w_first = first >> 5;
+    const u64 n_tiles = (count + FB_TILE - 1) / FB_TILE;
+    sw.t0 = (u64)blockIdx.x * tiles_per_group;
+    sw.t1 = sw.t0 + tiles_per_group;
+    if (sw.t1 > n_tiles)
+        sw.t1 = n_tiles;
+    return sw;
+}
+
+// what a thread reads of tile t: the words of its 32 rows and, over a table, the marks behind them.  The sweeps ask for
+// tile t + 1 before they test tile t.
+struct TileIn {
+    Words3 w;
+    Marks3 m;
+};
+
+template <bool TABLE>
+__device__ __forceinline__ TileIn tile_load(const FilterSource &src, const Sweep &sw, u64 t)
+{
+    const int tid = threadIdx.x;
+    const u64 w = sw.w_first + t * (FB_TILE / 32) + tid;
+    TileIn r;
+    r.w = words_load(src.words, src.n_words, w, sw.sh);
+    if (TABLE)
+        r.m = marks_load(src.marks, src.n_mark_words, w, sw.fo);
+    return r;
+}
+
+// even bit 2j = row j of the thread's 32 in tile t exists and satisfies the pattern
+__device__ __forceinline__ u64 tile_match(const TileIn &in, const Sweep &sw, u64 count, u64 t)
+{
+    const int tid = threadIdx.x;
+    const u64 row0 = t * FB_TILE + (u64)tid * FB_ROWS;
+    return match_rows(stream_of(in.w, sw.sh), sw.s0, sw.s1, sw.s2, sw.s3) &
+           valid_rows(row0 < count ? (long long)(count - row0) : 0);
+}
+
+// bit j = row j is a row of the result: it matches and, over a table, lies inside one sequence
+template <bool TABLE>
+__device__ __forceinline__ u32 tile_rows(const TileIn &in, const Sweep &sw, u64 count, u64 t)
+{
+    u32 m = compact_even(tile_match(in, sw, count, t));
+    if (TABLE)
+        m &= ~spoiled_rows(in.m, sw.fo, sw.span);
+    return m;
+}
+
+// ---- sweep 1: rows of the result per workgroup range ------------------------------------------
+template <bool TABLE>
+__device__ __forceinline__ void count_sweep(const FilterSource &src, u64 first, u64 count, const FilterBits &fb,
+                                            u32 tiles_per_group, u32 *__restrict__ group_counts)
+{
+    __shared__ u32 wsum[FB_WAVES];
+    const Sweep sw = sweep_of(first, count, fb, tiles_per_group);
+    u32 c = 0;
+    TileIn nxt = tile_load<TABLE>(src, sw, sw.t0);
+    for (u64 t = sw.t0; t < sw.t1; t++) {
+        const TileIn cur = nxt;
+        if (t + 1 < sw.t1)
+            nxt = tile_load<TABLE>(src, sw, t + 1);
+        // (without marks the even-bit mask is counted as it is)
+        c += TABLE ? (u32)__popc(tile_rows<true>(cur, sw, count, t)) : (u32)__popcll(tile_match(cur, sw, count, t));
+    }
+    c = wave_sum(c);
+    if ((threadIdx.x & 63) == 0)
+        wsum[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u32 g = 0;
+        for (int w = 0; w < FB_WAVES; w++)
+            g += wsum[w];
+        group_counts[blockIdx.x] = g;
+    }
+}
+
+__global__ __launch_bounds__(FB_THREADS) void fb_count_kernel(const u64 *__restrict__ words, u64 n_words, u64 first,
+                                                              u64 count, FilterBits fb, u32 tiles_per_group,
+                                                              u32 *__restrict__ group_counts)
+{
+    count_sweep<false>(FilterSource{words, n_words, nullptr, 0, nullptr, 0}, first, count, fb, tiles_per_group, group_counts);
+}
+
+__global__ __launch_bounds__(FB_THREADS) void fbt_count_kernel(const u64 *__restrict__ words, u64 n_words,
+                                                               const u32 *__restrict__ marks, u64 n_mark_words, u64 first,
+                                                               u64 count, FilterBits fb, u32 tiles_per_group,
+                                                               u32 *__restrict__ group_counts)
+{
+    count_sweep<true>(FilterSource{words, n_words, marks, n_mark_words, nullptr, 0}, first, count, fb, tiles_per_group,
+                      group_counts);
+}
+
+// ---- sweep 2: the rows in position order ------------------------------------------------------
+// rows of the result before this workgroup's range: the sum of the group counts before it (wtot: FB_WAVES words)
+__device__ __forceinline__ u64 group_base(const u32 *__restrict__ group_counts, u32 *wtot, u64 *base_sh)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    u32 part = 0;
+    for (u32 g = tid; g < blockIdx.x; g += FB_THREADS)
+        part += group_counts[g];
+    // partial sums of up to 2^32-1 rows cannot overflow 32 bits in total
+    part = wave_sum(part);
+    if (lane == 0)
+        wtot[wave] = part;
+    __syncthreads();
+    if (tid == 0) {
+        u64 b = 0;
+        for (int w = 0; w < FB_WAVES; w++)
+            b += wtot[w];
+        *base_sh = b;
+    }
+    __syncthreads();
+    return *base_sh;
+}
+
+// Where the thread's rows m go in the tile's list, and the rows of the whole tile.  Ends behind a barrier that also says:
+// the previous tile's list and words (and whatever else the caller keeps per tile in LDS) have been read.
+__device__ __forceinline__ u32 tile_scan(u32 m, const Words3 &cur, u32 *wtot, u64 *wsh, u32 *tile_cnt)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const u32 c = (u32)__popc(m);
+    const u32 inc = wave_incl_scan(c);
+    if (lane == 63)
+        wtot[wave] = inc;
+    __syncthreads();
+    u32 wbase = 0, cnt = 0;
+#pragma unroll
+    for (int w = 0; w < FB_WAVES; w++) {
+        const u32 v = wtot[w];
+        wbase += w < wave ? v : 0u;
+        cnt += v;
+    }
+    wsh[tid] = cur.w0;
+    if (tid == FB_THREADS - 1) {
+        wsh[FB_THREADS] = cur.w1;
+        wsh[FB_THREADS + 1] = cur.w2;
+    }
+    *tile_cnt = cnt;
+    return wbase + inc - c;
+}
+
+// The tile's packed words into wsh (keys are cut from there) and the tile-local rows of m into list from slot r on, in
+// row order; ends behind a barrier.
+__device__ __forceinline__ void tile_list(u32 m, u32 r, unsigned short *list)
+{
+    const int tid = threadIdx.x;
+    const u32 row_in_tile = (u32)tid * FB_ROWS;
+    while (m) {
+        const u32 j = (u32)__builtin_ctz(m);
+        m &= m - 1;
+        list[r++] = (unsigned short)(row_in_tile + j);
+    }
+    __syncthreads();
+}
+
+// key of tile-local row r: bits [2q, 2q + 2k) of the tile's words, q = r + first % 32
+__device__ __forceinline__ u64 tile_key(const u64 *wsh, u32 q, u64 mask)
+{
+    return funnel(wsh[q >> 5], wsh[(q >> 5) + 1], (q & 31u) * 2u) & mask;
+}
+
+// The store stage: listed row s of the tile goes to slot off + s of each of the N arrays that want(a) names, slots from
+// `cap` on are not stored.  Array 0 holds the keys, key(r) of tile-local row r; rest(r, v) gives v[a] for the wanted
+// arrays a >= 1 and is called only when there is one.  Both are called only for rows that are stored, the keys of a slot
+// or pair going out before the rest is worked out.
+// WIDE: the wanted arrays are 16-byte aligned at the same index parity `par`, so slot pairs (s, s + 1) with
+// (off + s + par) even go out as one 16-byte store per array; the first and last slot of a tile and the slot before
+// `cap` may be left over as singles.
+// (A wave-granular variant -- every wave lists and writes its own 2048 rows, no workgroup barrier -- was
+// measured 8-10 % slower at selectivity 1/4: four times as many, four times shorter output bursts.)
+template <int N, bool WIDE, typename Want, typename Key, typename Rest>
+__device__ __forceinline__ void store_listed(const unsigned short *list, u32 tile_cnt, u64 off, u32 par, u64 cap,
+                                             u64 *const (&out)[N], Want want, Key key, Rest rest)
+{
+    const int tid = threadIdx.x;
+    bool more = false;                               // an array behind the keys is wanted
+#pragma unroll
+    for (int a = 1; a < N; a++)
+        more = more || want(a);
+    auto store_one = [&](u32 r, u64 i) {
+        if (want(0))
+            __builtin_nontemporal_store(key(r), &out[0][i]);
+        if (more) {
+            u64 v[N] = {};
+            rest(r, v);
+#pragma unroll
+            for (int a = 1; a < N; a++)
+                if (want(a))
+                    __builtin_nontemporal_store(v[a], &out[a][i]);
+        }
+    };
+    if (WIDE) {
+        const int lead = (int)((off + par) & 1);
+        for (int s = 2 * tid - lead; s < (int)tile_cnt; s += 2 * FB_THREADS) {
+            const bool v0 = s >= 0, v1 = s + 1 < (int)tile_cnt;
+            // (an empty tile with lead = 1 has neither slot: both reads stay inside the list)
+            const u32 r0 = list[v0 ? s : 0], r1 = list[v1 ? s + 1 : (v0 ? s : 0)];
+            const u64 i0 = off + (u64)(long long)s;
+            if (v0 && v1 && i0 + 1 < cap) {
+                ull2_t xy;
+                if (want(0)) {
+                    xy.x = key(r0);
+                    xy.y = key(r1);
+                    __builtin_nontemporal_store(xy, reinterpret_cast<ull2_t *>(out[0] + i0));
+                }
+                if (more) {
+                    u64 x[N] = {}, y[N] = {};
+                    rest(r0, x);
+                    rest(r1, y);
+#pragma unroll
+                    for (int a = 1; a < N; a++)
+                        if (want(a)) {
+                            xy.x = x[a];
+                            xy.y = y[a];
+                            __builtin_nontemporal_store(xy, reinterpret_cast<ull2_t *>(out[a] + i0));
+                        }
+                }
+            } else {
+                if (v0 && i0 < cap)
+                    store_one(r0, i0);
+                if (v1 && i0 + 1 < cap)
+                    store_one(r1, i0 + 1);
+            }
+        }
+    } else {
+        for (u32 s = tid; s < tile_cnt; s += FB_THREADS) {
+            const u32 r0 = list[s];
+            const u64 i0 = off + s;
+            if (i0 < cap)
+                store_one(r0, i0);
+        }
+    }
+}
+
+// One sequence: keys and positions (HAS_*: compile-time, so an array not asked for costs nothing).
+template <bool HAS_KEYS, bool HAS_POS, bool WIDE>
+__global__ __launch_bounds__(FB_THREADS) void fb_write_kernel(const u64 *__restrict__ words, u64 n_words, u64 first,
+                                                              u64 count, u64 mask, FilterBits fb, u32 tiles_per_group,
+                                                              const u32 *__restrict__ group_counts,
+                                                              u64 *__restrict__ out_keys, u64 *__restrict__ out_pos,
+                                                              u64 cap, u32 par, u64 *__restrict__ total_out)
+{
+    __shared__ unsigned short list[FB_TILE];         // tile-local rows of the matches, in row order
+    __shared__ u64 wsh[FB_THREADS + 2];              // the tile's packed words
+    __shared__ u32 wtot[FB_WAVES];
+    __shared__ u64 base_sh;
+    const int tid = threadIdx.x;
+    u64 off = group_base(group_counts, wtot, &base_sh);
+
+    const FilterSource src = {words, n_words, nullptr, 0, nullptr, 0};
+    const Sweep sw = sweep_of(first, count, fb, tiles_per_group);
+    u64 *const out[2] = {out_keys, out_pos};
+    TileIn nxt = tile_load<false>(src, sw, sw.t0);
+    for (u64 t = sw.t0; t < sw.t1; t++) {
+        const TileIn cur = nxt;
+        if (t + 1 < sw.t1)
+            nxt = tile_load<false>(src, sw, t + 1);
+        const u32 m = tile_rows<false>(cur, sw, count, t);
+        u32 tile_cnt;
+        const u32 r = tile_scan(m, cur.w, wtot, wsh, &tile_cnt);
+        tile_list(m, r, list);
+        const u64 tile_pos0 = first + t * FB_TILE;
+        store_listed<2, WIDE>(
+            list, tile_cnt, off, par, cap, out, [](int a) { return a == 0 ? HAS_KEYS : HAS_POS; },
+            [&](u32 row) { return tile_key(wsh, row + sw.fo, mask); }, [&](u32 row, u64 *v) { v[1] = tile_pos0 + row; });
+        off += tile_cnt;
+    }
+    if (total_out && blockIdx.x == gridDim.x - 1 && tid == 0)
+        *total_out = off;
 }
 
 // Index of the first entry of a[lo .. hi) that is > p (hi when there is none), a ascending; by the whole workgroup, every
@@ -403,58 +512,16 @@ __device__ __forceinline__ u64 block_upper_bound(const u64 *__restrict__ a, u64 
     return lo;
 }
 
-// ---- sweep 1 over a table: matching table rows per workgroup range
-__global__ __launch_bounds__(FB_THREADS) void fbt_count_kernel(const u64 *__restrict__ words, u64 n_words,
-                                                               const u32 *__restrict__ marks, u64 n_mark_words, u64 first,
-                                                               u64 count, FilterBits fb, u32 tiles_per_group,
-                                                               u32 *__restrict__ group_counts)
-{
-    __shared__ u32 wsum[FB_WAVES];
-    const u32 s0 = fb.sets[0], s1 = fb.sets[1], s2 = fb.sets[2], s3 = fb.sets[3];
-    const u32 fo = (u32)(first & 31), span = (u32)fb.k - 1u;
-    const unsigned sh = fo * 2;
-    const u64 w_first = first >> 5;
-    const u64 n_tiles = (count + FB_TILE - 1) / FB_TILE;
-    u64 t0 = (u64)blockIdx.x * tiles_per_group, t1 = t0 + tiles_per_group;
-    if (t1 > n_tiles)
-        t1 = n_tiles;
-    u32 c = 0;
-    u64 w = w_first + t0 * (FB_TILE / 32) + threadIdx.x;
-    Words3 nxt = words_load(words, n_words, w, sh);
-    Marks3 mnxt = marks_load(marks, n_mark_words, w, fo);
-    for (u64 t = t0; t < t1; t++) {
-        const Words3 cur = nxt;
-        const Marks3 mcur = mnxt;
-        if (t + 1 < t1) {
-            w = w_first + (t + 1) * (FB_TILE / 32) + threadIdx.x;
-            nxt = words_load(words, n_words, w, sh);
-            mnxt = marks_load(marks, n_mark_words, w, fo);
-        }
-        const u64 row0 = t * FB_TILE + (u64)threadIdx.x * FB_ROWS;
-        const u64 m = match_rows(stream_of(cur, sh), s0, s1, s2, s3) & valid_rows(row0 < count ? (long long)(count - row0) : 0);
-        c += (u32)__popc(compact_even(m) & ~spoiled_rows(mcur, fo, span));
-    }
-    c = wave_sum(c);
-    if ((threadIdx.x & 63) == 0)
-        wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u32 g = 0;
-        for (int wv = 0; wv < FB_WAVES; wv++)
-            g += wsum[wv];
-        group_counts[blockIdx.x] = g;
-    }
-}
-
-// ---- sweep 2 over a table: keys, sequences and ordinals in table order
+// A table of sequences (FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k), test.sql:140-150, 172-176): the rows
+// of every sequence's own generate_kmers, each with the sequence it came from and its ordinal inside that sequence, in
+// table order; any of the three arrays may be null (a run-time test).
 // The sequence of a row at stream position p is the LAST sequence that starts at or before p (an upper bound over
 // seq_starts, minus one: of a run of equal starts -- empty sequences -- only the last one has bases).  Nothing searches
 // all n_seqs + 1 starts per row: the workgroup finds the bound of its first position once (block_upper_bound); every tile
 // then reads the 256 starts from its lower bound on into LDS, counts those at or below its last position -- that is its
 // upper bound, unless all 256 are, which takes another block_upper_bound (sequences shorter than 32 bases on average) --
-// and every LISTED row searches between the tile's two bounds: in LDS, or in global memory when they are more than 256
+// and every STORED row searches between the tile's two bounds: in LDS, or in global memory when they are more than 256
 // apart.  One long sequence gives equal bounds and no search.
-// WIDE: the arrays asked for are 16-byte aligned at the same index parity `par`.
 constexpr u32 FBT_STARTS = FB_THREADS;               // starts of a tile held in LDS
 template <bool WIDE>
 __global__ __launch_bounds__(FB_THREADS) void fbt_write_kernel(const u64 *__restrict__ words, u64 n_words,
@@ -467,58 +534,28 @@ __global__ __launch_bounds__(FB_THREADS) void fbt_write_kernel(const u64 *__rest
                                                                u64 *__restrict__ total_out)
 {
     __shared__ unsigned short list[FB_TILE];         // tile-local rows of the listed table rows, in row order
-    __shared__ u64 wsh[FB_THREADS + 2];              // the tile's packed words: keys are cut from here
+    __shared__ u64 wsh[FB_THREADS + 2];              // the tile's packed words
     __shared__ u64 sst[FBT_STARTS + 1];              // seq_starts[lo - 1 .. lo + 256) of the tile's lower bound lo
     __shared__ u32 wtot[FB_WAVES], wle[FB_WAVES], wub[FB_WAVES];
     __shared__ u64 base_sh;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
+    u64 off = group_base(group_counts, wtot, &base_sh);
 
-    // listed rows before this workgroup's range
-    {
-        u32 part = 0;
-        for (u32 g = tid; g < blockIdx.x; g += FB_THREADS)
-            part += group_counts[g];
-        part = wave_sum(part);
-        if (lane == 0)
-            wtot[wave] = part;
-        __syncthreads();
-        if (tid == 0) {
-            u64 b = 0;
-            for (int w = 0; w < FB_WAVES; w++)
-                b += wtot[w];
-            base_sh = b;
-        }
-        __syncthreads();
-    }
-    u64 off = base_sh;
-
-    const u32 s0 = fb.sets[0], s1 = fb.sets[1], s2 = fb.sets[2], s3 = fb.sets[3];
-    const u32 fo = (u32)(first & 31), span = (u32)fb.k - 1u;
-    const unsigned sh = fo * 2;
-    const u64 w_first = first >> 5;
-    const u64 n_tiles = (count + FB_TILE - 1) / FB_TILE;
-    u64 t0 = (u64)blockIdx.x * tiles_per_group, t1 = t0 + tiles_per_group;
-    if (t1 > n_tiles)
-        t1 = n_tiles;
+    const FilterSource src = {words, n_words, marks, n_mark_words, seq_starts, n_seqs};
+    const Sweep sw = sweep_of(first, count, fb, tiles_per_group);
+    u64 *const out[3] = {out_keys, out_seq, out_pos};
     const bool locate = out_seq || out_pos;          // uniform
     // seq_starts[0 .. ub_lo) lie at or below every position of the tile: entry 0 is 0, entry n_seqs is above every row
     u64 ub_lo = 1;
-    if (locate && t0 < t1)
-        ub_lo = block_upper_bound(seq_starts, 1, n_seqs, first + t0 * FB_TILE, wub);
+    if (locate && sw.t0 < sw.t1)
+        ub_lo = block_upper_bound(seq_starts, 1, n_seqs, first + sw.t0 * FB_TILE, wub);
 
-    u64 w = w_first + t0 * (FB_TILE / 32) + tid;
-    Words3 nxt = words_load(words, n_words, w, sh);
-    Marks3 mnxt = marks_load(marks, n_mark_words, w, fo);
-    for (u64 t = t0; t < t1; t++) {
+    TileIn nxt = tile_load<true>(src, sw, sw.t0);
+    for (u64 t = sw.t0; t < sw.t1; t++) {
         const u64 tile_row0 = t * FB_TILE;
-        const u64 row0 = tile_row0 + (u64)tid * FB_ROWS;
-        const Words3 cur = nxt;
-        const Marks3 mcur = mnxt;
-        if (t + 1 < t1) {
-            w = w_first + (t + 1) * (FB_TILE / 32) + tid;
-            nxt = words_load(words, n_words, w, sh);
-            mnxt = marks_load(marks, n_mark_words, w, fo);
-        }
+        const TileIn cur = nxt;
+        if (t + 1 < sw.t1)
+            nxt = tile_load<true>(src, sw, t + 1);
         // the starts from the lower bound on, and how many of them the tile's last position has reached
         const u64 p_last = first + (tile_row0 + FB_TILE < count ? tile_row0 + FB_TILE : count) - 1;
         u64 sv = ~(u64)0, sv_lo = 0;
@@ -528,29 +565,15 @@ __global__ __launch_bounds__(FB_THREADS) void fbt_write_kernel(const u64 *__rest
             sv_lo = seq_starts[ub_lo - 1];
         }
         const u32 nle = (u32)__popcll(__ballot(sv <= p_last));
-        u32 m = compact_even(match_rows(stream_of(cur, sh), s0, s1, s2, s3) &
-                             valid_rows(row0 < count ? (long long)(count - row0) : 0)) &
-                ~spoiled_rows(mcur, fo, span);
-        const u32 c = (u32)__popc(m);
-        const u32 inc = wave_incl_scan(c);
-        if (lane == 63)
-            wtot[wave] = inc;
-        if (lane == 0)
-            wle[wave] = nle;
-        __syncthreads();                             // also: the previous tile's list, words and starts have been read
-        u32 wbase = 0, tile_cnt = 0, n_le = 0;
+        if ((tid & 63) == 0)
+            wle[tid >> 6] = nle;
+        const u32 m = tile_rows<true>(cur, sw, count, t);
+        u32 tile_cnt;
+        const u32 r = tile_scan(m, cur.w, wtot, wsh, &tile_cnt);
+        u32 n_le = 0;
 #pragma unroll
-        for (int wv = 0; wv < FB_WAVES; wv++) {
-            const u32 v = wtot[wv];
-            wbase += wv < wave ? v : 0u;
-            tile_cnt += v;
+        for (int wv = 0; wv < FB_WAVES; wv++)
             n_le += wle[wv];
-        }
-        wsh[tid] = cur.w0;
-        if (tid == FB_THREADS - 1) {
-            wsh[FB_THREADS] = cur.w1;
-            wsh[FB_THREADS + 1] = cur.w2;
-        }
         sst[1 + tid] = sv;
         if (tid == 0)
             sst[0] = sv_lo;
@@ -558,20 +581,8 @@ __global__ __launch_bounds__(FB_THREADS) void fbt_write_kernel(const u64 *__rest
         if (locate && n_le == FBT_STARTS && ub_hi <= n_seqs)     // uniform
             ub_hi = block_upper_bound(seq_starts, ub_hi, n_seqs, p_last, wub);
         const u64 n_between = ub_hi - ub_lo;
-        u32 r = wbase + inc - c;
-        const u32 row_in_tile = (u32)tid * FB_ROWS;
-        while (m) {
-            const u32 j = (u32)__builtin_ctz(m);
-            m &= m - 1;
-            list[r++] = (unsigned short)(row_in_tile + j);
-        }
-        __syncthreads();
+        tile_list(m, r, list);
 
-        // key of tile-local row r: bits [2q, 2q + 2k) of the tile's words, q = r + first % 32
-        auto key_of = [&](u32 row) -> u64 {
-            const u32 q = row + fo;
-            return funnel(wsh[q >> 5], wsh[(q >> 5) + 1], (q & 31u) * 2u) & mask;
-        };
         // sequence and ordinal of the row at stream position p
         auto locate_row = [&](u64 p, u64 &sq, u64 &ord) {
             if (n_between <= FBT_STARTS) {
@@ -602,72 +613,10 @@ __global__ __launch_bounds__(FB_THREADS) void fbt_write_kernel(const u64 *__rest
                 ord = p - seq_starts[lo - 1];
             }
         };
-        if (WIDE) {
-            // slot pairs (s, s+1) with (off + s + par) even: 16-byte aligned in every array
-            const int lead = (int)((off + par) & 1);
-            for (int s = 2 * tid - lead; s < (int)tile_cnt; s += 2 * FB_THREADS) {
-                const bool v0 = s >= 0, v1 = s + 1 < (int)tile_cnt;
-                const u32 r0 = v0 ? list[s] : 0u, r1 = v1 ? list[s + 1] : 0u;
-                const u64 p0 = first + tile_row0 + r0, p1 = first + tile_row0 + r1;
-                const u64 i0 = off + (u64)(long long)s;
-                ull2_t kv = {0, 0}, qv = {0, 0}, ov = {0, 0};
-                if (out_keys) {
-                    kv.x = key_of(r0);
-                    kv.y = key_of(r1);
-                }
-                if (locate) {
-                    u64 a, b;
-                    locate_row(p0, a, b);
-                    qv.x = a;
-                    ov.x = b;
-                    locate_row(p1, a, b);
-                    qv.y = a;
-                    ov.y = b;
-                }
-                if (v0 && v1 && i0 + 1 < cap) {
-                    if (out_keys)
-                        __builtin_nontemporal_store(kv, reinterpret_cast<ull2_t *>(out_keys + i0));
-                    if (out_seq)
-                        __builtin_nontemporal_store(qv, reinterpret_cast<ull2_t *>(out_seq + i0));
-                    if (out_pos)
-                        __builtin_nontemporal_store(ov, reinterpret_cast<ull2_t *>(out_pos + i0));
-                } else {
-                    if (v0 && i0 < cap) {
-                        if (out_keys)
-                            __builtin_nontemporal_store(kv.x, &out_keys[i0]);
-                        if (out_seq)
-                            __builtin_nontemporal_store(qv.x, &out_seq[i0]);
-                        if (out_pos)
-                            __builtin_nontemporal_store(ov.x, &out_pos[i0]);
-                    }
-                    if (v1 && i0 + 1 < cap) {
-                        if (out_keys)
-                            __builtin_nontemporal_store(kv.y, &out_keys[i0 + 1]);
-                        if (out_seq)
-                            __builtin_nontemporal_store(qv.y, &out_seq[i0 + 1]);
-                        if (out_pos)
-                            __builtin_nontemporal_store(ov.y, &out_pos[i0 + 1]);
-                    }
-                }
-            }
-        } else {
-            for (u32 s = tid; s < tile_cnt; s += FB_THREADS) {
-                const u32 r0 = list[s];
-                const u64 i0 = off + s;
-                if (i0 < cap) {
-                    if (out_keys)
-                        __builtin_nontemporal_store(key_of(r0), &out_keys[i0]);
-                    if (locate) {
-                        u64 a, b;
-                        locate_row(first + tile_row0 + r0, a, b);
-                        if (out_seq)
-                            __builtin_nontemporal_store(a, &out_seq[i0]);
-                        if (out_pos)
-                            __builtin_nontemporal_store(b, &out_pos[i0]);
-                    }
-                }
-            }
-        }
+        store_listed<3, WIDE>(
+            list, tile_cnt, off, par, cap, out, [&](int a) { return out[a] != nullptr; },
+            [&](u32 row) { return tile_key(wsh, row + sw.fo, mask); },
+            [&](u32 row, u64 *v) { locate_row(first + tile_row0 + row, v[1], v[2]); });
         off += tile_cnt;
         ub_lo = ub_hi;                               // at or below the next tile's first position
     }
@@ -675,6 +624,7 @@ __global__ __launch_bounds__(FB_THREADS) void fbt_write_kernel(const u64 *__rest
         *total_out = off;
 }
 
+// ---- launchers --------------------------------------------------------------------------------
 // groups of the two sweeps for `count` rows: every group takes the same number of consecutive tiles
 void filter_bits_geometry(u64 count, u32 *n_groups, u32 *tiles_per_group)
 {
@@ -686,73 +636,59 @@ void filter_bits_geometry(u64 count, u32 *n_groups, u32 *tiles_per_group)
     *n_groups = (u32)((n_tiles + tpg - 1) / tpg);
 }
 
-hipError_t launch_filter_bits_count(const u64 *words, u64 n_words, u64 first, u64 count, const FilterBits &fb,
-                                    u32 *group_counts, hipStream_t s)
-{
-    if (count == 0)
-        return hipSuccess;
-    u32 groups, tpg;
-    filter_bits_geometry(count, &groups, &tpg);
-    hipLaunchKernelGGL(fb_count_kernel, dim3(groups), dim3(FB_THREADS), 0, s, words, n_words, first, count, fb, tpg,
-                       group_counts);
-    return hipGetLastError();
-}
-
-template <bool HK, bool HP>
-static void launch_write_variant(bool wide, dim3 grid, hipStream_t s, const u64 *words, u64 n_words, u64 first, u64 count,
-                                 u64 mask, const FilterBits &fb, u32 tpw, const u32 *group_counts,
-                                 u64 *out_keys, u64 *out_pos, u64 cap, u32 par, u64 *total_out)
-{
-    if (wide)
-        hipLaunchKernelGGL((fb_write_kernel<HK, HP, true>), grid, dim3(FB_THREADS), 0, s, words, n_words, first, count,
-                           mask, fb, tpw, group_counts, out_keys, out_pos, cap, par, total_out);
-    else
-        hipLaunchKernelGGL((fb_write_kernel<HK, HP, false>), grid, dim3(FB_THREADS), 0, s, words, n_words, first, count,
-                           mask, fb, tpw, group_counts, out_keys, out_pos, cap, par, total_out);
-}
-
-hipError_t launch_filter_bits_write(const u64 *words, u64 n_words, u64 first, u64 count, int k, const FilterBits &fb,
-                                    const u32 *group_counts, u64 *out_keys, u64 *out_pos, u64 cap, u64 *total_out,
+hipError_t launch_filter_bits_count(const FilterSource &src, u64 first, u64 count, const FilterBits &fb, u32 *group_counts,
                                     hipStream_t s)
 {
     if (count == 0)
         return hipSuccess;
-    u32 groups, tpw;
-    filter_bits_geometry(count, &groups, &tpw);
-    // 16-byte stores need both arrays 8-byte aligned with the same index parity at 16-byte boundaries
-    const uintptr_t ak = reinterpret_cast<uintptr_t>(out_keys), ap = reinterpret_cast<uintptr_t>(out_pos);
-    const uintptr_t ref = out_keys ? ak : ap;
-    const bool wide = (ref & 7) == 0 && (!out_keys || !out_pos || ((ak ^ ap) & 15) == 0);
-    const u32 par = (u32)((ref >> 3) & 1);
-    const u64 mask = kmer_mask(k);
-    const dim3 grid(groups);
-    if (out_keys && out_pos)
-        launch_write_variant<true, true>(wide, grid, s, words, n_words, first, count, mask, fb, tpw, group_counts,
-                                         out_keys, out_pos, cap, par, total_out);
-    else if (out_keys)
-        launch_write_variant<true, false>(wide, grid, s, words, n_words, first, count, mask, fb, tpw, group_counts,
-                                          out_keys, out_pos, cap, par, total_out);
-    else
-        launch_write_variant<false, true>(wide, grid, s, words, n_words, first, count, mask, fb, tpw, group_counts,
-                                          out_keys, out_pos, cap, par, total_out);
-    return hipGetLastError();
-}
-
-hipError_t launch_table_bits_count(const u64 *words, u64 n_words, const u32 *marks, u64 n_mark_words, u64 first, u64 count,
-                                   const FilterBits &fb, u32 *group_counts, hipStream_t s)
-{
-    if (count == 0)
-        return hipSuccess;
     u32 groups, tpg;
     filter_bits_geometry(count, &groups, &tpg);
-    hipLaunchKernelGGL(fbt_count_kernel, dim3(groups), dim3(FB_THREADS), 0, s, words, n_words, marks, n_mark_words, first, count,
-                       fb, tpg, group_counts);
+    if (src.marks)
+        hipLaunchKernelGGL(fbt_count_kernel, dim3(groups), dim3(FB_THREADS), 0, s, src.words, src.n_words, src.marks,
+                           src.n_mark_words, first, count, fb, tpg, group_counts);
+    else
+        hipLaunchKernelGGL(fb_count_kernel, dim3(groups), dim3(FB_THREADS), 0, s, src.words, src.n_words, first, count, fb,
+                           tpg, group_counts);
     return hipGetLastError();
 }
 
-hipError_t launch_table_bits_write(const u64 *words, u64 n_words, const u32 *marks, u64 n_mark_words, const u64 *seq_starts,
-                                   u64 n_seqs, u64 first, u64 count, const FilterBits &fb, const u32 *group_counts,
-                                   u64 *out_keys, u64 *out_seq, u64 *out_pos, u64 cap, u64 *total_out, hipStream_t s)
+// what every write kernel takes behind its source
+struct WriteArgs {
+    u64 first, count, mask;
+    FilterBits fb;
+    u32 tpg;
+    const u32 *group_counts;
+    u64 *out_keys, *out_seq, *out_pos;
+    u64 cap;
+    u32 par;
+    u64 *total_out;
+};
+
+template <bool HK, bool HP, bool WIDE>
+static void launch_single_write(dim3 grid, hipStream_t s, const FilterSource &src, const WriteArgs &a)
+{
+    hipLaunchKernelGGL((fb_write_kernel<HK, HP, WIDE>), grid, dim3(FB_THREADS), 0, s, src.words, src.n_words, a.first, a.count,
+                       a.mask, a.fb, a.tpg, a.group_counts, a.out_keys, a.out_pos, a.cap, a.par, a.total_out);
+}
+
+template <bool WIDE>
+static void launch_write_variant(dim3 grid, hipStream_t s, const FilterSource &src, const WriteArgs &a)
+{
+    if (src.marks)
+        hipLaunchKernelGGL((fbt_write_kernel<WIDE>), grid, dim3(FB_THREADS), 0, s, src.words, src.n_words, src.marks,
+                           src.n_mark_words, src.seq_starts, src.n_seqs, a.first, a.count, a.mask, a.fb, a.tpg, a.group_counts,
+                           a.out_keys, a.out_seq, a.out_pos, a.cap, a.par, a.total_out);
+    else if (a.out_keys && a.out_pos)
+        launch_single_write<true, true, WIDE>(grid, s, src, a);
+    else if (a.out_keys)
+        launch_single_write<true, false, WIDE>(grid, s, src, a);
+    else
+        launch_single_write<false, true, WIDE>(grid, s, src, a);
+}
+
+hipError_t launch_filter_bits_write(const FilterSource &src, u64 first, u64 count, const FilterBits &fb,
+                                    const u32 *group_counts, u64 *out_keys, u64 *out_seq, u64 *out_pos, u64 cap,
+                                    u64 *total_out, hipStream_t s)
 {
     if (count == 0)
         return hipSuccess;
@@ -770,16 +706,12 @@ hipError_t launch_table_bits_write(const u64 *words, u64 n_words, const u32 *mar
             ref = x;
         wide = wide && (x & 7) == 0 && ((x ^ ref) & 15) == 0;
     }
-    const u32 par = (u32)((ref >> 3) & 1);
-    const u64 mask = kmer_mask(fb.k);
+    const WriteArgs wa = {first, count, kmer_mask(fb.k), fb, tpg, group_counts, out_keys, out_seq, out_pos, cap,
+                          (u32)((ref >> 3) & 1), total_out};
     if (wide)
-        hipLaunchKernelGGL((fbt_write_kernel<true>), dim3(groups), dim3(FB_THREADS), 0, s, words, n_words, marks, n_mark_words,
-                           seq_starts, n_seqs, first, count, mask, fb, tpg, group_counts, out_keys, out_seq, out_pos, cap, par,
-                           total_out);
+        launch_write_variant<true>(dim3(groups), s, src, wa);
     else
-        hipLaunchKernelGGL((fbt_write_kernel<false>), dim3(groups), dim3(FB_THREADS), 0, s, words, n_words, marks, n_mark_words,
-                           seq_starts, n_seqs, first, count, mask, fb, tpg, group_counts, out_keys, out_seq, out_pos, cap, par,
-                           total_out);
+        launch_write_variant<false>(dim3(groups), s, src, wa);
     return hipGetLastError();
 }
 

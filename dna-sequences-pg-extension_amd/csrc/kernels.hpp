@@ -15,25 +15,28 @@ hipError_t launch_extract(const u64 *words, u64 n_words, u64 first, u64 count, i
                           hipStream_t s);
 
 // position-ordered filtered extraction (filter_kernels.hip), two sweeps over the (tiny) packed input:
-//   count sweep -> matches per workgroup range (filter_bits_geometry groups, group_counts[g]);
-//   write sweep -> every group sums the counts before it, then writes keys / positions (either may be
-//   null) of rows whose output index is < cap; *total_out (may be null, may be host-mapped memory) receives
-//   the number of matching rows
+//   count sweep -> rows of the result per workgroup range (filter_bits_geometry groups, group_counts[g]);
+//   write sweep -> every group sums the counts before it, then writes the rows whose output index is < cap;
+//   *total_out (may be null, may be host-mapped memory) receives the number of rows of the result
+// One sequence (marks == nullptr): the rows that match, each with its key and its position (out_seq must be null).
+// A TABLE of sequences (marks / seq_starts: what dnagpu_dna_set_sequences keeps resident): only stream rows that lie
+// inside one sequence, in ascending stream position, each with its key, its sequence (0-based) and its ordinal inside
+// that sequence.  Any of the arrays may be null.  k = fb.k.
 constexpr int FILTER_MAX_GROUPS = 8192;
+struct FilterSource {
+    const u64 *words;
+    u64 n_words;
+    const u32 *marks;
+    u64 n_mark_words;
+    const u64 *seq_starts;
+    u64 n_seqs;
+};
 void filter_bits_geometry(u64 count, u32 *n_groups, u32 *tiles_per_group);
-hipError_t launch_filter_bits_count(const u64 *words, u64 n_words, u64 first, u64 count, const FilterBits &fb,
-                                    u32 *group_counts, hipStream_t s);
-hipError_t launch_filter_bits_write(const u64 *words, u64 n_words, u64 first, u64 count, int k, const FilterBits &fb,
-                                    const u32 *group_counts, u64 *out_keys, u64 *out_pos, u64 cap, u64 *total_out,
+hipError_t launch_filter_bits_count(const FilterSource &src, u64 first, u64 count, const FilterBits &fb, u32 *group_counts,
                                     hipStream_t s);
-// the same two sweeps over a TABLE of sequences (marks / seq_starts: what dnagpu_dna_set_sequences keeps resident): only
-// stream rows that lie inside one sequence are counted and written, in ascending stream position, each with its key, its
-// sequence (0-based) and its ordinal inside that sequence (any of the three arrays may be null).  fb.k = k.
-hipError_t launch_table_bits_count(const u64 *words, u64 n_words, const u32 *marks, u64 n_mark_words, u64 first, u64 count,
-                                   const FilterBits &fb, u32 *group_counts, hipStream_t s);
-hipError_t launch_table_bits_write(const u64 *words, u64 n_words, const u32 *marks, u64 n_mark_words, const u64 *seq_starts,
-                                   u64 n_seqs, u64 first, u64 count, const FilterBits &fb, const u32 *group_counts,
-                                   u64 *out_keys, u64 *out_seq, u64 *out_pos, u64 cap, u64 *total_out, hipStream_t s);
+hipError_t launch_filter_bits_write(const FilterSource &src, u64 first, u64 count, const FilterBits &fb,
+                                    const u32 *group_counts, u64 *out_keys, u64 *out_seq, u64 *out_pos, u64 cap,
+                                    u64 *total_out, hipStream_t s);
 
 hipError_t launch_hash_batch(const u64 *keys, u64 n, u32 *out, hipStream_t s);
 hipError_t launch_match_batch(const u64 *keys, u64 n, const FilterDev &f, uint8_t *flags, hipStream_t s);

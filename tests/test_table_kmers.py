@@ -392,7 +392,7 @@ def test_caps_and_single_arrays(ctx, pkg):
     wk, ws, wp = t.expected(k, spec)
     total = len(wk)
     assert total > 1000
-    for cap in (0, 1, 1000, total - 1):
+    for cap in (0, 1, 1000, 1001, total - 1):         # (1001: the last slot is the first half of a 16-byte pair)
         gk, gs, gp, n = ctx.generate_kmers_table(d, k, flt, cap=cap)
         assert n == total
         assert np.array_equal(gk, wk[:cap]) and np.array_equal(gs, ws[:cap]) and np.array_equal(gp, wp[:cap])
