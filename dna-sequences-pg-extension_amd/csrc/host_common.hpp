@@ -221,8 +221,11 @@ int run_tree(dnagpu_ctx *ctx, PoolScope &ps, const dnagpu_dna *dna, u64 first, u
 bool dense_pays(u64 n, int k);
 
 // ---------------------------------------------------------------- sk_host.hip
-// DNAGPU_SK_SKEWED: a bucket is too heavy (low-complexity input): the caller counts with the ordinary tree
-// instead, which has the skew paths.
+// The record count.  What it shares with the other host files is below; its state (SkParts) and its stages -- level 0,
+// the sk_l1_* stages of level 1, sk_level2, the sk_tail_* stages -- are local to sk_host.hip.
+// DNAGPU_SK_SKEWED (from the census of level 1, sk_l1_census; nothing has moved yet): the set is too heavy for the record
+// path (low-complexity input): count_sk hands it up and the caller counts with the ordinary tree instead, which has the
+// skew paths; count_sk_received expands everything to keys.
 constexpr int DNAGPU_SK_SKEWED = -1;
 // geometry of a count of n rows: final buckets of ~SK_LEAF_MEAN k-mers = 16 per mid bucket; mid buckets = c0n coarse x 2^b1.
 // A multi-GPU count derives it from the GLOBAL row count on every rank (the digits are part of the records).

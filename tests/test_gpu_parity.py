@@ -1088,6 +1088,61 @@ def test_records_exchange_one_process(ctx, pkg, world, n, k, motif):
         ctx.count_records([(0, 5, n_buckets)], k, rows)          # a bucket the geometry does not have
 
 
+def test_count_records_takes_every_level1_route(ctx, pkg):
+    """dnagpu_count_records, one "rank", through every route of level 1, told apart by the phase names as
+    test_level1_speculative_and_exact_agree and test_level1_sampled_regions_keep_repeats_speculative do for the single-GPU
+    count: the speculative sweep alone, the exact level alone (DNAGPU_DEBUG_NO_SPEC1), both after an overflow
+    (DNAGPU_DEBUG_SPEC1_OVERFLOW), and on a tiled motif the sampled histogram (DNAGPU_DEBUG_SAMPLE1).  On this side the
+    sampled regions do NOT make the sweep speculative: the landing buffer is sized by sk_received_cap (the records, or the
+    regions of an even level 1), without the third of slack that level 0 adds for sampled regions, so they do not fit and
+    the exact level follows "sk_sample1" -- "sk_hist1", no "sk_spec1".  So dnagpu_count_records does not reach level 1's
+    third route today (sampled regions AND the speculative sweep, SkL1Route::SpeculativeSampled in sk_host.hip), and no test
+    pins it on this side; the single-GPU count's tests do (test_level1_sampled_regions_keep_repeats_speculative).
+    More than half the motif input's k-mers are in heavy mid buckets: without DNAGPU_DEBUG_HEAVY_EXPAND that is no SKEWED
+    fall-back (which would skip level 2, "sk_regroup"): the heavy buckets are split by d2 ("sk_heavy_split"), and what
+    sk_count_big gives up on is expanded ("sk_expand_flat")."""
+    k = 31
+    cases = [("speculative", 3_000_000, 0, 0), ("exact", 3_000_000, 0, pkg.DEBUG_NO_SPEC1),
+             ("overflow forced", 3_000_000, 0, pkg.DEBUG_SPEC1_OVERFLOW), ("sampled", 4_000_000, 1000, pkg.DEBUG_SAMPLE1)]
+    inputs = {}
+    ctx.set_profiling(True)
+    for name, n, motif, flag in cases:
+        if (n, motif) not in inputs:
+            seed = 0xD2A0003 + n
+            words = orc.synth_words_repeat(seed, n, motif) if motif else orc.synth_words(seed, n)
+            inputs[(n, motif)] = (words,) + orc.count_kmers(words, n, k)
+        words, ok, oc = inputs[(n, motif)]
+        rows = n - k + 1
+        d = ctx.upload(words, n)
+        ctx.set_debug(pkg.DEBUG_FORCE_SUPERKMER | flag)
+        try:
+            r = ctx.sk_records(d, k, 0, rows, rows)
+            pieces = [(r.device_ptr + 16 * int(r.offsets[b]), int(r.offsets[b + 1] - r.offsets[b]), b) for b in range(r.n_buckets)]
+            h = ctx.count_records(pieces, k, rows)
+        finally:
+            ctx.set_debug(0)
+        phases = [a for a, _ in ctx.last_phase_times()]
+        print(f"count_records {name}: {phases}")
+        assert h.total == rows and not h.is_sorted
+        gk, gc = h.download()
+        order = np.argsort(gk, kind="stable")
+        assert_same(gk[order], ok, f"count_records {name} keys")
+        assert_same(gc[order], oc, f"count_records {name} counts")
+        for o in (h, r, d):
+            o.free()
+        assert "sk_regroup" in phases, (name, phases)
+        if name == "speculative":
+            assert "sk_spec1" in phases and "sk_hist1" not in phases, phases
+        elif name == "exact":
+            assert "sk_hist1" in phases and "sk_spec1" not in phases, phases
+        elif name == "overflow forced":
+            assert "sk_spec1" in phases and "sk_hist1" in phases, phases
+        else:
+            assert "sk_sample1" in phases and "sk_hist1" in phases and "sk_spec1" not in phases, phases
+            assert "sk_heavy_split" in phases and "sk_expand_flat" in phases, phases
+    ctx.set_profiling(False)
+
+
 def test_count_records_mostly_repeats_expand_everything(ctx, pkg):
     """dnagpu_count_records over records that are almost all heavy (a periodic sequence), with the heavy mid buckets
     expanded as a whole (DNAGPU_DEBUG_HEAVY_EXPAND): levels 1-2 report the set skewed, every coarse bucket becomes one
