@@ -28,6 +28,7 @@ from .binding import (  # noqa: F401
     DnaGpuError,
     Filter,
     Hist,
+    KmerIndex,
     Records,
     SPECTRUM_MAX_BINS,
     TOP_MAX,

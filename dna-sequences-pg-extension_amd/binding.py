@@ -195,6 +195,16 @@ def lib():
     L.dnagpu_buffer_upload.argtypes = [vp, vp, vp, C.c_uint64]
     L.dnagpu_kmer_hash.argtypes = [vp, vp, C.c_uint64, vp, C.c_int]
     L.dnagpu_kmer_match.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(_FilterC), vp, C.c_int]
+    L.dnagpu_kmer_index_build.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(vp)]
+    for f in ("rows", "distinct"):
+        getattr(L, f"dnagpu_kmer_index_{f}").argtypes = [vp]
+        getattr(L, f"dnagpu_kmer_index_{f}").restype = C.c_uint64
+    L.dnagpu_kmer_index_k.argtypes = [vp]
+    L.dnagpu_kmer_index_scan.argtypes = [vp, vp, C.POINTER(_FilterC), vp, vp, C.c_uint64, u64p, u64p, C.c_int]
+    L.dnagpu_kmer_index_lookup.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_int]
+    L.dnagpu_kmer_index_read.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_int]
+    L.dnagpu_kmer_index_free.argtypes = [vp, vp]
+    L.dnagpu_kmer_index_free.restype = None
     L.dnagpu_multi_init.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(vp)]
     L.dnagpu_multi_destroy.argtypes = [vp]
     L.dnagpu_multi_destroy.restype = None
@@ -380,6 +390,83 @@ class Ranking:
             if self.ctx._base_debug & DEBUG_GUARD_POOL:
                 self.ctx.synchronize()          # raises if a kernel wrote past the end of a work buffer
             lib().dnagpu_ranking_free(self.ctx.h, self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
+class KmerIndex:
+    """dnagpu_kmer_index: the index over a stored kmer column (Context.kmer_index): built once, asked `=`, `^@` and `@>` many
+    times; answers are row ids in INDEX order (text order of the key under A < T < C < G, row ids ascending inside a key)"""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+
+    @property
+    def rows(self):
+        return int(lib().dnagpu_kmer_index_rows(self.h))
+
+    @property
+    def distinct(self):
+        return int(lib().dnagpu_kmer_index_distinct(self.h))
+
+    @property
+    def k(self):
+        return int(lib().dnagpu_kmer_index_k(self.h))
+
+    def scan(self, flt, cap=None, want_rows=True, want_keys=True, on_device=False, out=None):
+        """the rows that satisfy flt.  host: -> (rows, keys, n_out, visited), rows / keys the first min(cap, n_out) matches
+        (None where not wanted; cap=None: all of them, found with a counting call first).  on_device: into
+        out=(dev_rows, dev_keys) of cap uint64 each (either may be None) -> (n_out, visited)"""
+        fn = lib().dnagpu_kmer_index_scan
+        n_out, visited = C.c_uint64(), C.c_uint64()
+        if on_device:
+            dr, dk = out
+            _chk(fn(self.ctx.h, self.h, C.byref(flt.c), dr, dk, cap or 0, C.byref(n_out), C.byref(visited), 1))
+            return n_out.value, visited.value
+        if cap is None:
+            _chk(fn(self.ctx.h, self.h, C.byref(flt.c), None, None, 0, C.byref(n_out), C.byref(visited), 0))
+            cap = n_out.value
+        rows = np.empty(max(cap, 1), dtype=np.uint64) if want_rows else None
+        keys = np.empty(max(cap, 1), dtype=np.uint64) if want_keys else None
+        _chk(fn(self.ctx.h, self.h, C.byref(flt.c), rows.ctypes.data if want_rows else None,
+                keys.ctypes.data if want_keys else None, cap, C.byref(n_out), C.byref(visited), 0))
+        m = min(cap, n_out.value)
+        return (rows[:m] if want_rows else None, keys[:m] if want_keys else None, n_out.value, visited.value)
+
+    def lookup(self, keys):
+        """batch equality: -> (first, count) per query key: its window of the index order (count 0: absent)"""
+        q = np.ascontiguousarray(keys, dtype=np.uint64)
+        first = np.empty(max(q.size, 1), dtype=np.uint64)
+        count = np.empty(max(q.size, 1), dtype=np.uint64)
+        _chk(lib().dnagpu_kmer_index_lookup(self.ctx.h, self.h, q.ctypes.data, q.size, first.ctypes.data, count.ctypes.data, 0))
+        return first[:q.size], count[:q.size]
+
+    def lookup_device(self, dev_keys, m, dev_first, dev_count):
+        _chk(lib().dnagpu_kmer_index_lookup(self.ctx.h, self.h, dev_keys, m, dev_first, dev_count, 1))
+
+    def read(self, first=0, count=None, want_rows=True, want_keys=True):
+        """entries [first, first + count) of the index order (count=None: all from first on) -> (rows, keys)"""
+        if count is None:
+            count = self.rows - first
+        rows = np.empty(max(count, 1), dtype=np.uint64) if want_rows else None
+        keys = np.empty(max(count, 1), dtype=np.uint64) if want_keys else None
+        _chk(lib().dnagpu_kmer_index_read(self.ctx.h, self.h, first, count, rows.ctypes.data if want_rows else None,
+                                          keys.ctypes.data if want_keys else None, 0))
+        return (rows[:count] if want_rows else None, keys[:count] if want_keys else None)
+
+    def read_device(self, first, count, dev_rows, dev_keys):
+        _chk(lib().dnagpu_kmer_index_read(self.ctx.h, self.h, first, count, dev_rows, dev_keys, 1))
+
+    def free(self):
+        if self.h:
+            if self.ctx._base_debug & DEBUG_GUARD_POOL:
+                self.ctx.synchronize()          # raises if a kernel wrote past the end of a work buffer
+            lib().dnagpu_kmer_index_free(self.ctx.h, self.h)
             self.h = None
 
     def __enter__(self):
@@ -894,6 +981,20 @@ class Context:
     def kmer_match_device(self, dev_keys, n, k, flt, dev_flags):
         """n keys in device memory -> n uint8 flags in device memory"""
         _chk(lib().dnagpu_kmer_match(self.h, dev_keys, n, k, C.byref(flt.c), dev_flags, 1))
+
+    # ---- the index over a stored kmer column
+    def kmer_index(self, keys, k):
+        """CREATE INDEX over a column of n keys of k bases (host array; row id = position) -> KmerIndex"""
+        a = np.ascontiguousarray(keys, dtype=np.uint64)
+        h = C.c_void_p()
+        _chk(lib().dnagpu_kmer_index_build(self.h, a.ctypes.data if a.size else None, a.size, k, 0, C.byref(h)))
+        return KmerIndex(self, h)
+
+    def kmer_index_device(self, dev_keys, n, k):
+        """the same over n keys already in device memory (left as they are)"""
+        h = C.c_void_p()
+        _chk(lib().dnagpu_kmer_index_build(self.h, dev_keys, n, k, 1, C.byref(h)))
+        return KmerIndex(self, h)
 
     def kmer_match(self, keys, k, flt):
         a = np.ascontiguousarray(keys, dtype=np.uint64)

@@ -109,7 +109,7 @@ static FilterBits all_rows(int k)
 // The same operator as per-position sets for the bit-sliced stream kernels.  *none: no row can match
 // (an `=` of another length, stray bits behind the right-hand kmer's length, a 'U' in the pattern, an operator that
 // would raise *op_error).
-static int build_filter_bits(const dnagpu_filter *f, int k, FilterBits *out, bool *none, int *op_error)
+int dnagpu::build_filter_bits(const dnagpu_filter *f, int k, FilterBits *out, bool *none, int *op_error)
 {
     FilterDev fd;
     RC_TRY(build_filter(f, k, &fd, op_error));           // argument checks and the reference's ERRORs

@@ -1,5 +1,5 @@
 // host_common.hpp -- what the host files of the C-ABI (dnagpu_api.hip, count_host.hip, sk_host.hip, multi_host.hip, query_host.hip,
-// filter_host.hip) share
+// filter_host.hip, index_host.hip) share
 // (internal, like kernels.hpp): the error macros, the context / dna / histogram objects, the buffer pool, and the few
 // functions one of the files calls in another.  Declarations only, plus the templates and macros that must be visible;
 // the definitions are in dnagpu_api.hip unless a section says otherwise.
@@ -195,6 +195,13 @@ void prof_end(dnagpu_ctx *ctx);      // names[i] labels the interval [mark i, ma
 inline u64 words_for(u64 n_bases) { return (n_bases + 31) / 32; }
 // validates [first, first+count) against the row count of generate_kmers(dna, k)
 int check_range(const dnagpu_dna *dna, int k, u64 first, u64 count);
+
+// ---------------------------------------------------------------- filter_host.hip
+// A WHERE operator as per-position sets, with the argument checks and the reference's ERRORs of every entry point that
+// takes a dnagpu_filter (the fused extractions, the index scan of index_host.hip).  Returns the error of a malformed filter.
+// *op_error: the operator's own ERROR, which the reference raises only when a row reaches the operator; *none: no row can
+// match.
+int build_filter_bits(const dnagpu_filter *f, int k, FilterBits *out, bool *none, int *op_error);
 
 // ---------------------------------------------------------------- count_host.hip
 struct TreeResult {

@@ -268,6 +268,53 @@ hipError_t launch_batch_rows(const u64 *starts, u64 n_seqs, int k, u64 *rows, hi
 hipError_t launch_batch_keys(const u64 *words, u64 n_words, const u32 *marks, u64 n_mark_words, u64 n_rows, int k, u64 *out_keys,
                              unsigned long long *cursor, hipStream_t s);
 
+// ---------------------------------------------------------------- index_kernels.hip
+// The index over a stored kmer column: n (r, row) pairs sorted by r = the base-reversed key
+// (index_math.hpp), a stable LSD radix sort by 8-bit digits.  One pass = launch_index_hist (hist[d * tiles + tile], tiles =
+// index_sort_tiles(n)) -> launch_scan_u32 over the 256 * tiles words -> launch_index_scatter; launch_index_digit_bins tells
+// from the scanned matrix how many digits occur at all (one: the scatter would move nothing).
+constexpr int INDEX_SORT_TILE = 2048;     // keys per workgroup of the sort: 256 threads x 8, each wave a contiguous quarter
+constexpr int INDEX_SCAN_TILE = 2048;     // candidates per workgroup of the scan's sweeps
+struct IndexSortSrc {                     // what a pass reads: the caller's keys (r is formed on the fly, row = position) while
+    const u64 *keys;                      // nothing has moved yet (keys != null), else the pairs of the pass before
+    const u64 *r;
+    const u32 *row;
+    int k;
+};
+u32 index_sort_tiles(u64 n);
+hipError_t launch_index_hist(const IndexSortSrc &src, u64 n, int shift, u32 *hist, hipStream_t s);
+hipError_t launch_index_digit_bins(const u32 *off, u64 n, u32 *nonempty, hipStream_t s);
+hipError_t launch_index_scatter(const IndexSortSrc &src, u64 n, int shift, const u32 *off, u64 *out_r, u32 *out_row, hipStream_t s);
+// *distinct (zeroed by the caller) += the keys of the sorted r[0 .. n) that differ from their predecessor
+hipError_t launch_index_distinct(const u64 *r, u64 n, u64 *distinct, hipStream_t s);
+// The scan.  ranges: the R <= 1024 concrete prefixes of p bases that fb admits (index_prune_depth), in ascending order, each
+// looked up in r: beg[j] = first slot, off[0 .. R] = exclusive scan of the lengths, *visited = off[R] = the candidates C.
+hipError_t launch_index_ranges(const u64 *r, u64 n, const FilterBits &fb, int p, u32 R, u32 *off, u32 *beg, u64 *visited,
+                               hipStream_t s);
+// sweeps over the C candidates in tiles of INDEX_SCAN_TILE (index_scan_tiles(C) tiles): test != 0: a candidate matches when
+// its key passes fd (the positions behind the prune depth); count -> tile_counts[tile]; write (tile_offsets = their
+// exclusive scan; unused when test == 0) -> the matches in index order, row ids widened to u64 and keys un-reversed, rows
+// from cap on not stored; either array may be null.
+struct IndexScanArgs {
+    const u64 *r;
+    const u32 *row;
+    const u32 *off;
+    const u32 *beg;
+    u32 R;
+    u32 C;
+    int k;
+    int test;
+    FilterDev fd;
+};
+u32 index_scan_tiles(u64 C);
+hipError_t launch_index_sweep_count(const IndexScanArgs &a, u32 *tile_counts, hipStream_t s);
+hipError_t launch_index_sweep_write(const IndexScanArgs &a, const u32 *tile_offsets, u64 *out_rows, u64 *out_keys, u64 cap,
+                                    hipStream_t s);
+// out_first[j], out_count[j] = the window of the index that holds keys[j] (count 0: absent, or bits above 2k set)
+hipError_t launch_index_lookup(const u64 *r, u64 n, int k, const u64 *keys, u64 m, u64 *out_first, u64 *out_count, hipStream_t s);
+// entries [first, first + count) as u64 row ids and un-reversed keys (either may be null)
+hipError_t launch_index_read(const u64 *r, const u32 *row, int k, u64 first, u64 count, u64 *out_rows, u64 *out_keys, hipStream_t s);
+
 // ---------------------------------------------------------------- superkmer_kernels.hip
 // super-k-mer (minimizer) partitioning for long k-mers: the dna sweeps (level 0: records per coarse digit of every
 // chunk of rows / records scattered into the coarse buckets), the record level (level 1: d1), and the expansion of

@@ -109,6 +109,17 @@ def lib():
         L.table_kmers_failed.argtypes = [vp]
         L.table_kmers_end.restype = None
         L.table_kmers_end.argtypes = [vp]
+        L.kmer_index_create.restype = vp
+        L.kmer_index_create.argtypes = [C.POINTER(_Kmer), C.c_uint64]
+        L.kmer_index_rows.restype = C.c_uint64
+        L.kmer_index_rows.argtypes = [vp]
+        for f in (L.kmer_index_scan_eq, L.kmer_index_scan_starts_with):
+            f.restype = C.c_int64
+            f.argtypes = [vp, C.POINTER(_Kmer), C.POINTER(C.POINTER(C.c_int64))]
+        L.kmer_index_scan_contains.restype = C.c_int64
+        L.kmer_index_scan_contains.argtypes = [vp, C.POINTER(_Qkmer), C.POINTER(C.POINTER(C.c_int64))]
+        L.kmer_index_end.restype = None
+        L.kmer_index_end.argtypes = [vp]
         _LIB = L
     return _LIB
 
@@ -381,3 +392,42 @@ def table_kmers(rows, k, op=None, rhs=None):
         return np.array(seq, dtype=np.int64), np.array(pos, dtype=np.int64), np.array(keys, dtype=np.uint64)
     finally:
         lib().table_kmers_end(t)
+
+
+class kmer_index:
+    """CREATE INDEX ... USING spgist (kmer_sequence spgist_kmer_ops) over a stored column (a list of kmer; row id = position),
+    then SELECT ... WHERE kmer_sequence <op> rhs as an index scan: scan('=', kmer), scan('^@', kmer), scan('@>', qkmer) ->
+    the row ids, ascending (test.sql:156-270)"""
+
+    def __init__(self, column):
+        arr = (_Kmer * max(len(column), 1))()
+        for i, x in enumerate(column):
+            arr[i].length, arr[i].bit_sequence = x.c.length, x.c.bit_sequence
+        self.p = lib().kmer_index_create(arr, len(column))
+        if not self.p:
+            raise _err()
+
+    def __len__(self):
+        return int(lib().kmer_index_rows(self.p))
+
+    def scan(self, op, rhs):
+        fn = {"=": lib().kmer_index_scan_eq, "^@": lib().kmer_index_scan_starts_with, "@>": lib().kmer_index_scan_contains}[op]
+        rows = C.POINTER(C.c_int64)()
+        n = fn(self.p, C.byref(rhs.c), C.byref(rows))
+        if n < 0:
+            raise _err()
+        out = [int(rows[i]) for i in range(n)]
+        if n:
+            _libc.free(C.cast(rows, C.c_void_p))
+        return out
+
+    def end(self):
+        if self.p:
+            lib().kmer_index_end(self.p)
+            self.p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.end()

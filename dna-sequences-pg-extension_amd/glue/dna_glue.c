@@ -1140,3 +1140,112 @@ void table_kmers_end(TableKmers *t)
     free(t->pos);
     free(t);
 }
+
+/* ------------------------------------------------------------------ the index over a stored kmer column */
+
+struct KmerIndex {
+    dnagpu_kmer_index *idx;
+    int k;
+};
+
+KmerIndex *kmer_index_create(const Kmer *column, uint64_t n)
+{
+    int k = n ? column[0].length : 1;                /* (an empty column: any length does, no scan finds a row) */
+    for (uint64_t i = 1; i < n; i++)
+        if (column[i].length != k) {
+            ereport_error("kmer_index_create: the column holds kmers of %d and %d bases; an index covers one length", k,
+                          (int)column[i].length);
+            return NULL;
+        }
+    KmerIndex *x = (KmerIndex *)calloc(1, sizeof *x);
+    uint64_t *keys = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(n ? n : 1));
+    if (!x || !keys) {
+        free(x);
+        free(keys);
+        ereport_error("out of memory");
+        return NULL;
+    }
+    for (uint64_t i = 0; i < n; i++)
+        keys[i] = column[i].bit_sequence;
+    x->k = k;
+    const bool ok = ctx() && gpu_ok(dnagpu_kmer_index_build(g_ctx, keys, n, k, 0, &x->idx));    /* a bad length: dna.c:773 */
+    free(keys);
+    if (!ok) {
+        free(x);
+        return NULL;
+    }
+    return x;
+}
+
+uint64_t kmer_index_rows(const KmerIndex *idx)
+{
+    return idx ? dnagpu_kmer_index_rows(idx->idx) : 0;
+}
+
+static int cmp_i64(const void *a, const void *b)
+{
+    const int64_t x = *(const int64_t *)a, y = *(const int64_t *)b;
+    return (x > y) - (x < y);
+}
+
+/* the rows of one index scan, sorted into heap order */
+static int64_t index_scan(KmerIndex *x, const dnagpu_filter *f, int64_t **rows)
+{
+    *rows = NULL;
+    uint64_t n = 0;
+    if (!ctx() || !gpu_ok(dnagpu_kmer_index_scan(g_ctx, x->idx, f, NULL, NULL, 0, &n, NULL, 0)))
+        return -1;
+    if (n == 0)
+        return 0;
+    int64_t *out = (int64_t *)malloc(sizeof(int64_t) * (size_t)n);
+    if (!out) {
+        ereport_error("out of memory");
+        return -1;
+    }
+    uint64_t got = 0;
+    if (!gpu_ok(dnagpu_kmer_index_scan(g_ctx, x->idx, f, (uint64_t *)out, NULL, n, &got, NULL, 0)) || got != n) {
+        free(out);
+        return -1;
+    }
+    qsort(out, (size_t)n, sizeof *out, cmp_i64);     /* row ids are < 2^32: the same order signed or unsigned */
+    *rows = out;
+    return (int64_t)n;
+}
+
+static int64_t index_scan_kmer(KmerIndex *x, int kind, const Kmer *rhs, int64_t **rows)
+{
+    dnagpu_filter f;
+    memset(&f, 0, sizeof f);
+    f.kind = kind;
+    f.length = rhs->length;
+    f.bits = rhs->bit_sequence;
+    return index_scan(x, &f, rows);
+}
+
+int64_t kmer_index_scan_eq(KmerIndex *idx, const Kmer *rhs, int64_t **rows)
+{
+    return index_scan_kmer(idx, DNAGPU_FILTER_EQUALS, rhs, rows);
+}
+
+int64_t kmer_index_scan_starts_with(KmerIndex *idx, const Kmer *prefix, int64_t **rows)
+{
+    return index_scan_kmer(idx, DNAGPU_FILTER_STARTS_WITH, prefix, rows);
+}
+
+int64_t kmer_index_scan_contains(KmerIndex *idx, const Qkmer *pattern, int64_t **rows)
+{
+    dnagpu_filter f;
+    memset(&f, 0, sizeof f);
+    f.kind = DNAGPU_FILTER_CONTAINS;
+    strncpy(f.pattern, pattern->sequence, sizeof f.pattern - 1);
+    return index_scan(idx, &f, rows);
+}
+
+void kmer_index_end(KmerIndex *idx)
+{
+    if (!idx)
+        return;
+    if (g_ctx)
+        dnagpu_kmer_index_free(g_ctx, idx->idx);
+    free(idx);
+}

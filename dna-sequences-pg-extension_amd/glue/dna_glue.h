@@ -162,6 +162,24 @@ bool table_kmers_next(TableKmers *t, int64_t *seq, int64_t *pos, Kmer *out);
 bool table_kmers_failed(const TableKmers *t);
 void table_kmers_end(TableKmers *t);
 
+/* ---- CREATE INDEX ... ON kmer_data_t USING spgist (kmer_sequence spgist_kmer_ops) and the index scans of `=`, `^@` and `@>`
+ * over the stored column (dna--1.0.sql:304-314; test.sql:156-270) ----
+ * create: column[i] = the kmer of heap row i; the keys go to the device once and are sorted there (dnagpu_kmer_index_build).
+ * An index covers ONE length: a column of mixed lengths is refused with a message of its own (a divergence: the reference's
+ * operator class takes any kmer).  n == 0 is a valid, empty index.
+ * scan_eq / scan_starts_with / scan_contains: the row ids that satisfy the operator, in ASCENDING ROW ORDER -- the order a
+ * bitmap heap scan hands rows out in; the device answers in index order and the glue sorts on the host.  Returns the number
+ * of rows and stores a malloc'd array in *rows (NULL when there are none); -1 + dna_glue_errmsg() on an ERROR: the reference's
+ * own texts (dna.c:854-856, 1106-1108), raised only when the index has a row.  Exact, where the reference's index scans lose
+ * rows (test.sql:191 against :208, :223 against :237) and its `@>` strategy does not work (dna--1.0.sql:308). */
+typedef struct KmerIndex KmerIndex;
+KmerIndex *kmer_index_create(const Kmer *column, uint64_t n);
+uint64_t kmer_index_rows(const KmerIndex *idx);
+int64_t kmer_index_scan_eq(KmerIndex *idx, const Kmer *rhs, int64_t **rows);
+int64_t kmer_index_scan_starts_with(KmerIndex *idx, const Kmer *prefix, int64_t **rows);
+int64_t kmer_index_scan_contains(KmerIndex *idx, const Qkmer *pattern, int64_t **rows);
+void kmer_index_end(KmerIndex *idx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,7 +34,8 @@ extern "C" {
 /* 2: histograms of several parts (dnagpu_hist_parts: what dnagpu_count_multi_unordered returns with its default of three
  * bucket groups per owner -- dnagpu_hist_device_keys / _counts are NULL for those), the dnagpu_multi_* options, the
  * table-of-sequences count (dnagpu_count_kmers_batch, dnagpu_dna_set_sequences + dnagpu_count_kmers_table,
- * dnagpu_hist_merge), the rows of a table of sequences with the fused WHERE forms (dnagpu_generate_kmers_table) */
+ * dnagpu_hist_merge), the rows of a table of sequences with the fused WHERE forms (dnagpu_generate_kmers_table), the index
+ * over a stored kmer column (dnagpu_kmer_index_*: additions only, so the number stays) */
 #define DNAGPU_ABI_VERSION 2
 
 /* ---- status codes ------------------------------------------------------------------------
@@ -562,6 +563,55 @@ int dnagpu_kmer_hash(dnagpu_ctx *ctx, const uint64_t *keys, uint64_t n, uint32_t
  * dnagpu_generate_kmers_filtered. */
 int dnagpu_kmer_match(dnagpu_ctx *ctx, const uint64_t *keys, uint64_t n, int k,
                       const dnagpu_filter *filter, uint8_t *flags, int on_device);
+
+/* ---- index over a stored kmer column: CREATE INDEX ... USING spgist (kmer_sequence spgist_kmer_ops) and the index scans
+ * of `=`, `^@` and `@>` (dna--1.0.sql:304-314, dna.c:1234-1738; test.sql:156-270: kmer_data_t filled from generate_kmers,
+ * indexed, asked the three operators) --------------------------------------------------------------------------------
+ * dnagpu_kmer_match above is the sequential scan of such a column: it reads all of it for every query and returns flags.
+ * An index is built once and asked many times; a query reads only the part of it that can hold matches and returns ROW IDS.
+ * It is not an SP-GiST tree (a page-by-page access method PostgreSQL drives) but what the tree is for, as a sort and a few
+ * binary searches, and it is exact: the reference's index scans lose rows (1021 of 1025 at test.sql:191 /
+ * 208, 4036 of 4044 at :223 / :237) and its `@>` strategy is marked "DOES NOT WORK" (dna--1.0.sql:308).
+ * Order: entries are sorted by the key's TEXT under A < T < C < G (base 0 most significant), row ids ascending among equal
+ *   keys: "index order".  The keys that start with a given prefix are one contiguous window of it.
+ * Snapshot: an index of n rows owns 12 bytes per row from the context's pool (the stream rule below) and does not depend on
+ *   the caller's key array afterwards; the build only reads that array (unlike dnagpu_count_keys).  No incremental insert.
+ * dnagpu_kmer_index_build: keys = n keys of k bases, host memory, or device memory when on_device != 0; bits of a key above
+ *   2k are masked off; row id = position in keys.  Checks, in order: k outside 1..32: DNAGPU_ERR_INVALID_K; NULL ctx / out,
+ *   NULL keys with n > 0: DNAGPU_ERR_BAD_ARG; n > 2^32 - 1: DNAGPU_ERR_TOO_LARGE (before any device work).  n == 0: a valid
+ *   index of 0 rows that holds no device memory; every scan of it returns 0 rows.  An allocation failure is DNAGPU_ERR_OOM
+ *   with nothing leaked and *out = NULL.
+ * dnagpu_kmer_index_rows / _distinct / _k: rows, distinct keys, k (0 for NULL).
+ * dnagpu_kmer_index_scan: the rows that satisfy `filter`, in index order (NOT heap order: a caller that wants ascending row
+ *   ids sorts the answer): row ids (as uint64) to out_rows and the keys to out_keys (either may be NULL), at most cap of
+ *   each, host memory, or device memory when out_on_device != 0; *n_out = all matches even beyond cap; *visited (may be
+ *   NULL) = the index entries inside the pruned ranges, i.e. what the query read.  Pruning: with S_i the set of codes the
+ *   filter admits at position i, the prune depth p is the largest p in 0..k with |S_0| * ... * |S_(p-1)| <=
+ *   DNAGPU_INDEX_MAX_RANGES; the entries whose first p bases lie in the sets are visited and positions p..k-1 are tested on
+ *   each.  `=` visits its matches only, `^@` too (p = min(k, length + 5)); a pattern that opens with N's prunes little, as
+ *   in any prefix tree.  NULL ctx / idx / n_out / filter: DNAGPU_ERR_BAD_ARG.  Otherwise dnagpu_kmer_match's rules exactly:
+ *   a malformed filter is always an error; DNAGPU_ERR_QKMER_LEN_MISMATCH and DNAGPU_ERR_PREFIX_TOO_LONG are raised only when
+ *   the index has at least one row; an EQUALS filter of another length, and a pattern with 'U', give 0 rows (visited = 0);
+ *   a 32-base prefix compares all 64 bits.
+ * dnagpu_kmer_index_lookup: batch equality (the join of a key list with the column): for each of m query keys of k bases
+ *   the window of the index order that holds it, out_first[j] / out_count[j] (count 0: absent; first is then unspecified).
+ *   A query key with bits above 2k matches nothing.  keys / out_* all host, or all device when on_device != 0.
+ * dnagpu_kmer_index_read: entries [first, first + count) of the index order (dnagpu_hist_download's window rule: first > rows
+ *   or count > rows - first is DNAGPU_ERR_BAD_ARG; count == 0 or both outputs NULL is DNAGPU_OK).
+ * dnagpu_kmer_index_free returns the arrays to ctx's pool (NULL idx: nothing). */
+typedef struct dnagpu_kmer_index dnagpu_kmer_index;
+#define DNAGPU_INDEX_MAX_RANGES 1024u
+int dnagpu_kmer_index_build(dnagpu_ctx *ctx, const uint64_t *keys, uint64_t n, int k, int on_device, dnagpu_kmer_index **out);
+uint64_t dnagpu_kmer_index_rows(const dnagpu_kmer_index *idx);
+uint64_t dnagpu_kmer_index_distinct(const dnagpu_kmer_index *idx);
+int dnagpu_kmer_index_k(const dnagpu_kmer_index *idx);
+int dnagpu_kmer_index_scan(dnagpu_ctx *ctx, const dnagpu_kmer_index *idx, const dnagpu_filter *filter, uint64_t *out_rows,
+                           uint64_t *out_keys, uint64_t cap, uint64_t *n_out, uint64_t *visited, int out_on_device);
+int dnagpu_kmer_index_lookup(dnagpu_ctx *ctx, const dnagpu_kmer_index *idx, const uint64_t *keys, uint64_t m,
+                             uint64_t *out_first, uint64_t *out_count, int on_device);
+int dnagpu_kmer_index_read(dnagpu_ctx *ctx, const dnagpu_kmer_index *idx, uint64_t first, uint64_t count, uint64_t *out_rows,
+                           uint64_t *out_keys, int out_on_device);
+void dnagpu_kmer_index_free(dnagpu_ctx *ctx, dnagpu_kmer_index *idx);
 
 /* ---- debug aids (off by default) ---------------------------------------------------------------
  * DNAGPU_DEBUG_POISON_POOL: every work buffer the pool hands out -- fresh or recycled, internal or through
