@@ -196,7 +196,7 @@ def lib():
     L.dnagpu_kmer_hash.argtypes = [vp, vp, C.c_uint64, vp, C.c_int]
     L.dnagpu_kmer_match.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(_FilterC), vp, C.c_int]
     L.dnagpu_kmer_index_build.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(vp)]
-    for f in ("rows", "distinct"):
+    for f in ("rows", "distinct", "next_row"):
         getattr(L, f"dnagpu_kmer_index_{f}").argtypes = [vp]
         getattr(L, f"dnagpu_kmer_index_{f}").restype = C.c_uint64
     L.dnagpu_kmer_index_k.argtypes = [vp]
@@ -205,6 +205,8 @@ def lib():
     L.dnagpu_kmer_index_read.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_int]
     L.dnagpu_kmer_index_free.argtypes = [vp, vp]
     L.dnagpu_kmer_index_free.restype = None
+    L.dnagpu_kmer_index_append.argtypes = [vp, vp, vp, C.c_uint64, C.c_int]
+    L.dnagpu_kmer_index_delete.argtypes = [vp, vp, vp, C.c_uint64, C.c_int, u64p]
     L.dnagpu_multi_init.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(vp)]
     L.dnagpu_multi_destroy.argtypes = [vp]
     L.dnagpu_multi_destroy.restype = None
@@ -401,7 +403,7 @@ class Ranking:
 
 class KmerIndex:
     """dnagpu_kmer_index: the index over a stored kmer column (Context.kmer_index): built once, asked `=`, `^@` and `@>` many
-    times; answers are row ids in INDEX order (text order of the key under A < T < C < G, row ids ascending inside a key)"""
+    times, kept up to date with append / delete; answers are row ids in INDEX order (text order of the key under A < T < C < G, row ids ascending inside a key)"""
 
     def __init__(self, ctx, handle):
         self.ctx, self.h = ctx, handle
@@ -417,6 +419,32 @@ class KmerIndex:
     @property
     def k(self):
         return int(lib().dnagpu_kmer_index_k(self.h))
+
+    @property
+    def next_row(self):
+        """the rows the index has ever been given = the row id of the next appended key"""
+        return int(lib().dnagpu_kmer_index_next_row(self.h))
+
+    def append(self, keys, on_device=False):
+        """appends keys (row ids next_row, next_row + 1, ...).  host: an array of keys; on_device: (dev_keys, m)"""
+        if on_device:
+            dev_keys, m = keys
+            _chk(lib().dnagpu_kmer_index_append(self.ctx.h, self.h, dev_keys, m, 1))
+            return
+        a = np.ascontiguousarray(keys, dtype=np.uint64)
+        _chk(lib().dnagpu_kmer_index_append(self.ctx.h, self.h, a.ctypes.data if a.size else None, a.size, 0))
+
+    def delete(self, rows, on_device=False):
+        """removes the entries of the listed row ids (ids the index does not hold are ignored) -> the entries removed.
+        host: an array of ids; on_device: (dev_rows, m)"""
+        n_deleted = C.c_uint64()
+        if on_device:
+            dev_rows, m = rows
+            _chk(lib().dnagpu_kmer_index_delete(self.ctx.h, self.h, dev_rows, m, 1, C.byref(n_deleted)))
+            return n_deleted.value
+        a = np.ascontiguousarray(rows, dtype=np.uint64)
+        _chk(lib().dnagpu_kmer_index_delete(self.ctx.h, self.h, a.ctypes.data if a.size else None, a.size, 0, C.byref(n_deleted)))
+        return n_deleted.value
 
     def scan(self, flt, cap=None, want_rows=True, want_keys=True, on_device=False, out=None):
         """the rows that satisfy flt.  host: -> (rows, keys, n_out, visited), rows / keys the first min(cap, n_out) matches

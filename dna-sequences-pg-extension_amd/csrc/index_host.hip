@@ -2,7 +2,8 @@
 // reference answers with CREATE INDEX ... USING spgist (kmer_sequence spgist_kmer_ops) and index scans of `=`, `^@` and `@>`
 // (dna--1.0.sql:304-314, test.sql:156-270).  Build = a stable LSD radix sort of (r, row) pairs, r the base-reversed key
 // (index_math.hpp); scan = the ranges of up to DNAGPU_INDEX_MAX_RANGES concrete prefixes plus a test of the positions
-// behind them (index_kernels.hip).
+// behind them; append = the same sort of the batch, then one stable merge with the index; delete = a bitmap of the listed
+// row ids, then one stable compaction (index_kernels.hip).  An update builds new arrays that take over when it succeeds.
 #include "host_common.hpp"
 #include "index_math.hpp"
 
@@ -12,18 +13,34 @@ static_assert(DNAGPU_INDEX_MAX_RANGES == INDEX_MAX_RANGES, "the header's limit i
 
 struct dnagpu_kmer_index {
     u64 *r = nullptr;         // n base-reversed keys, ascending (pool memory)
-    u32 *row = nullptr;       // n positions in the caller's column; ascending among equal keys
-    u64 n = 0;
+    u32 *row = nullptr;       // n row ids; ascending among equal keys
+    u64 n = 0;                // entries now
+    u64 next_row = 0;         // rows ever given (the build's n + every append's m): the id of the next appended row
     u64 distinct = 0;
     int k = 0;
 };
 
 namespace {
 
-// dev_keys: the n >= 1 keys of the column in device memory (read only)
-int build_core(dnagpu_ctx *ctx, const u64 *dev_keys, u64 n, int k, dnagpu_kmer_index *idx)
+// `count` words of the caller's array as device memory: the array itself, or a copy in a buffer of `ps`
+int device_words(dnagpu_ctx *ctx, PoolScope &ps, const u64 *words, u64 count, int on_device, const u64 **out)
 {
-    PoolScope ps(ctx);
+    *out = words;
+    if (on_device)
+        return DNAGPU_OK;
+    u64 *up = nullptr;
+    RC_TRY(ps.alloc((size_t)count, &up));
+    HIP_TRY(hipMemcpyAsync(up, words, count * 8, hipMemcpyHostToDevice, ctx->stream));
+    *out = up;
+    return DNAGPU_OK;
+}
+
+// The LSD passes over dev_keys: the n >= 1 keys in device memory (read only), key j with row id row_base + j.  *out_r /
+// *out_row = the sorted pairs, buffers of `ps`; the other buffer pair and the histogram have gone back to the pool.
+// Every pass is labelled `mark` (the caller has called prof_begin).
+int sort_pairs(dnagpu_ctx *ctx, PoolScope &ps, const u64 *dev_keys, u64 n, int k, u32 row_base, const char *mark, u64 **out_r,
+               u32 **out_row)
+{
     u64 *r[2] = {nullptr, nullptr};
     u32 *row[2] = {nullptr, nullptr};
     for (int b = 0; b < 2; b++) {
@@ -31,42 +48,148 @@ int build_core(dnagpu_ctx *ctx, const u64 *dev_keys, u64 n, int k, dnagpu_kmer_i
         RC_TRY(ps.alloc((size_t)n, &row[b]));
     }
     const u64 n_hist = (u64)256 * index_sort_tiles(n);
-    u32 *hist = nullptr, *scan_tmp = nullptr, *small = nullptr;
+    u32 *hist = nullptr, *scan_tmp = nullptr, *bins_dev = nullptr;
     RC_TRY(ps.alloc((size_t)n_hist, &hist));
     RC_TRY(ps.alloc((size_t)scan_tmp_words(n_hist), &scan_tmp));
-    RC_TRY(ps.alloc((size_t)4, &small));                 // [0]: digits that occur; [2..3]: the distinct keys
+    RC_TRY(ps.alloc((size_t)2, &bins_dev));              // [0]: digits that occur
     const int passes = (2 * k + 7) / 8;                  // the bits above 2k are zero: the last digit may be partial
-    IndexSortSrc src{dev_keys, nullptr, nullptr, k};
+    IndexSortSrc src{dev_keys, nullptr, nullptr, k, row_base};
     int cur = -1;                                        // the buffer pair that holds the pairs (-1: still the caller's keys)
-    prof_begin(ctx);
     for (int p = 0; p < passes; p++) {
-        prof_mark(ctx, "index_pass");
+        prof_mark(ctx, mark);
         HIP_TRY(launch_index_hist(src, n, 8 * p, hist, ctx->stream));
         HIP_TRY(launch_scan_u32(hist, hist, n_hist, scan_tmp, nullptr, ctx->stream));
-        HIP_TRY(launch_index_digit_bins(hist, n, small, ctx->stream));
+        HIP_TRY(launch_index_digit_bins(hist, n, bins_dev, ctx->stream));
         u32 bins = 0;
-        RC_TRY(read_back(ctx, &bins, small, 4));
+        RC_TRY(read_back(ctx, &bins, bins_dev, 4));
         // one digit only: the scatter would copy the tile order.  (The last pass still runs if nothing has formed the
         // pairs yet: a column of one key.)
         if (bins <= 1 && !(p == passes - 1 && cur < 0))
             continue;
         const int dst = cur == 0 ? 1 : 0;
         HIP_TRY(launch_index_scatter(src, n, 8 * p, hist, r[dst], row[dst], ctx->stream));
-        src = IndexSortSrc{nullptr, r[dst], row[dst], k};
+        src = IndexSortSrc{nullptr, r[dst], row[dst], k, 0};
         cur = dst;
     }
-    prof_mark(ctx, "index_distinct");
-    u64 *distinct = reinterpret_cast<u64 *>(small + 2);
+    for (void *p : {(void *)r[1 - cur], (void *)row[1 - cur], (void *)hist, (void *)scan_tmp, (void *)bins_dev})
+        ps.free_now(p);
+    *out_r = r[cur];
+    *out_row = row[cur];
+    return DNAGPU_OK;
+}
+
+// *out = the distinct keys of the sorted r[0 .. n), n >= 1; waits
+int count_distinct(dnagpu_ctx *ctx, PoolScope &ps, const u64 *r, u64 n, u64 *out)
+{
+    u64 *distinct = nullptr;
+    RC_TRY(ps.alloc((size_t)1, &distinct));
     HIP_TRY(hipMemsetAsync(distinct, 0, 8, ctx->stream));
-    HIP_TRY(launch_index_distinct(r[cur], n, distinct, ctx->stream));
+    HIP_TRY(launch_index_distinct(r, n, distinct, ctx->stream));
     prof_mark(ctx, "end");
-    RC_TRY(read_back(ctx, &idx->distinct, distinct, 8));
-    prof_end(ctx);
-    ps.release(r[cur]);
-    ps.release(row[cur]);
-    idx->r = r[cur];
-    idx->row = row[cur];
+    RC_TRY(read_back(ctx, out, distinct, 8));
+    ps.free_now(distinct);
+    return DNAGPU_OK;
+}
+
+// idx takes the arrays (buffers of `ps`, or null with n == 0) over and returns its own to the pool: the hand-over of a
+// build, an append and a delete, after which nothing can fail
+void adopt(dnagpu_ctx *ctx, PoolScope &ps, dnagpu_kmer_index *idx, u64 *r, u32 *row, u64 n, u64 distinct)
+{
+    ps.release(r);
+    ps.release(row);
+    pool_free(ctx, idx->r);
+    pool_free(ctx, idx->row);
+    idx->r = r;
+    idx->row = row;
     idx->n = n;
+    idx->distinct = distinct;
+}
+
+// dev_keys: the n >= 1 keys of the column in device memory (read only)
+int build_core(dnagpu_ctx *ctx, const u64 *dev_keys, u64 n, int k, dnagpu_kmer_index *idx)
+{
+    PoolScope ps(ctx);
+    u64 *r = nullptr, distinct = 0;
+    u32 *row = nullptr;
+    prof_begin(ctx);
+    RC_TRY(sort_pairs(ctx, ps, dev_keys, n, k, 0, "index_pass", &r, &row));
+    prof_mark(ctx, "index_distinct");
+    RC_TRY(count_distinct(ctx, ps, r, n, &distinct));
+    prof_end(ctx);
+    adopt(ctx, ps, idx, r, row, n, distinct);
+    idx->next_row = n;
+    return DNAGPU_OK;
+}
+
+// dev_keys: the m >= 1 keys of the batch in device memory (read only); next_row + m <= 2^32 - 1
+int append_core(dnagpu_ctx *ctx, const u64 *dev_keys, u64 m, dnagpu_kmer_index *idx)
+{
+    PoolScope ps(ctx);
+    u64 *br = nullptr, *nr = nullptr, distinct = 0;
+    u32 *brow = nullptr, *nrow = nullptr;
+    prof_begin(ctx);
+    RC_TRY(sort_pairs(ctx, ps, dev_keys, m, idx->k, (u32)idx->next_row, "index_batch_sort", &br, &brow));
+    const u64 total = idx->n + m;
+    if (idx->n == 0) {                                   // nothing to merge with: the sorted batch is the index
+        nr = br;
+        nrow = brow;
+    } else {
+        u32 *part = nullptr;
+        RC_TRY(ps.alloc((size_t)total, &nr));
+        RC_TRY(ps.alloc((size_t)total, &nrow));
+        RC_TRY(ps.alloc((size_t)index_sort_tiles(total) + 1, &part));
+        prof_mark(ctx, "index_merge");
+        HIP_TRY(launch_index_merge_partition(idx->r, idx->n, br, m, part, ctx->stream));
+        HIP_TRY(launch_index_merge(idx->r, idx->row, idx->n, br, brow, m, part, nr, nrow, ctx->stream));
+    }
+    prof_mark(ctx, "index_distinct");
+    RC_TRY(count_distinct(ctx, ps, nr, total, &distinct));
+    prof_end(ctx);
+    adopt(ctx, ps, idx, nr, nrow, total, distinct);
+    idx->next_row += m;
+    return DNAGPU_OK;
+}
+
+// dev_ids: the m >= 1 listed row ids in device memory (read only); the index has n >= 1 entries
+int delete_core(dnagpu_ctx *ctx, const u64 *dev_ids, u64 m, dnagpu_kmer_index *idx, u64 *n_deleted)
+{
+    PoolScope ps(ctx);
+    const u64 n = idx->n, words = index_bitmap_words(idx->next_row);
+    const u32 nt = index_sort_tiles(n);
+    u32 *bitmap = nullptr, *tiles = nullptr, *scan_tmp = nullptr, *sum = nullptr;
+    RC_TRY(ps.alloc((size_t)words, &bitmap));
+    RC_TRY(ps.alloc((size_t)nt, &tiles));
+    RC_TRY(ps.alloc((size_t)scan_tmp_words(nt), &scan_tmp));
+    RC_TRY(ps.alloc((size_t)2, &sum));
+    prof_begin(ctx);
+    prof_mark(ctx, "index_mark");
+    HIP_TRY(hipMemsetAsync(bitmap, 0, words * 4, ctx->stream));
+    HIP_TRY(launch_index_mark(dev_ids, m, idx->next_row, bitmap, ctx->stream));
+    prof_mark(ctx, "index_compact");
+    HIP_TRY(launch_index_compact_count(idx->row, n, bitmap, tiles, ctx->stream));
+    HIP_TRY(launch_scan_u32(tiles, tiles, nt, scan_tmp, sum, ctx->stream));
+    u32 kept = 0;
+    RC_TRY(read_back(ctx, &kept, sum, 4));
+    if (kept > n)
+        return DNAGPU_ERR_INTERNAL;
+    if (kept == n || kept == 0) {                        // nothing listed is in the index / nothing is left of it
+        prof_mark(ctx, "end");
+        prof_end(ctx);
+        if (kept == 0)
+            adopt(ctx, ps, idx, nullptr, nullptr, 0, 0);
+        *n_deleted = n - kept;
+        return DNAGPU_OK;
+    }
+    u64 *nr = nullptr, distinct = 0;
+    u32 *nrow = nullptr;
+    RC_TRY(ps.alloc((size_t)kept, &nr));
+    RC_TRY(ps.alloc((size_t)kept, &nrow));
+    HIP_TRY(launch_index_compact_write(idx->r, idx->row, n, bitmap, tiles, nr, nrow, kept, ctx->stream));
+    prof_mark(ctx, "index_distinct");
+    RC_TRY(count_distinct(ctx, ps, nr, kept, &distinct));
+    prof_end(ctx);
+    adopt(ctx, ps, idx, nr, nrow, kept, distinct);
+    *n_deleted = n - kept;
     return DNAGPU_OK;
 }
 
@@ -184,13 +307,8 @@ extern "C" int dnagpu_kmer_index_build(dnagpu_ctx *ctx, const uint64_t *keys, ui
     }
     HIP_TRY(hipSetDevice(ctx->device));
     PoolScope ps(ctx);
-    const u64 *dev_keys = keys;
-    if (!on_device) {
-        u64 *up = nullptr;
-        RC_TRY(ps.alloc((size_t)n, &up));
-        HIP_TRY(hipMemcpyAsync(up, keys, n * 8, hipMemcpyHostToDevice, ctx->stream));
-        dev_keys = up;
-    }
+    const u64 *dev_keys = nullptr;
+    RC_TRY(device_words(ctx, ps, keys, n, on_device, &dev_keys));
     RC_TRY(build_core(ctx, dev_keys, n, k, idx.get()));
     *out = idx.release();
     return DNAGPU_OK;
@@ -200,6 +318,49 @@ extern "C" int dnagpu_kmer_index_build(dnagpu_ctx *ctx, const uint64_t *keys, ui
 extern "C" uint64_t dnagpu_kmer_index_rows(const dnagpu_kmer_index *idx) { return idx ? idx->n : 0; }
 extern "C" uint64_t dnagpu_kmer_index_distinct(const dnagpu_kmer_index *idx) { return idx ? idx->distinct : 0; }
 extern "C" int dnagpu_kmer_index_k(const dnagpu_kmer_index *idx) { return idx ? idx->k : 0; }
+
+extern "C" uint64_t dnagpu_kmer_index_next_row(const dnagpu_kmer_index *idx) { return idx ? idx->next_row : 0; }
+
+extern "C" int dnagpu_kmer_index_append(dnagpu_ctx *ctx, dnagpu_kmer_index *idx, const uint64_t *keys, uint64_t m, int on_device)
+{
+    return guarded([&]() -> int {
+    if (!ctx || !idx || (m && !keys))
+        return DNAGPU_ERR_BAD_ARG;
+    if (m > 0xFFFFFFFFull || idx->next_row + m > 0xFFFFFFFFull)      // row ids are 32-bit; refused before any device work
+        return DNAGPU_ERR_TOO_LARGE;
+    if (m == 0)
+        return DNAGPU_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    PoolScope ps(ctx);
+    const u64 *dev_keys = nullptr;
+    RC_TRY(device_words(ctx, ps, keys, m, on_device, &dev_keys));
+    return append_core(ctx, dev_keys, m, idx);
+    });
+}
+
+extern "C" int dnagpu_kmer_index_delete(dnagpu_ctx *ctx, dnagpu_kmer_index *idx, const uint64_t *rows, uint64_t m, int on_device,
+                                        uint64_t *n_deleted)
+{
+    return guarded([&]() -> int {
+    if (n_deleted)
+        *n_deleted = 0;
+    if (!ctx || !idx || (m && !rows))
+        return DNAGPU_ERR_BAD_ARG;
+    if (m > 0xFFFFFFFFull)
+        return DNAGPU_ERR_TOO_LARGE;
+    if (m == 0 || idx->n == 0)
+        return DNAGPU_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    PoolScope ps(ctx);
+    const u64 *dev_ids = nullptr;
+    RC_TRY(device_words(ctx, ps, rows, m, on_device, &dev_ids));
+    u64 gone = 0;
+    RC_TRY(delete_core(ctx, dev_ids, m, idx, &gone));
+    if (n_deleted)
+        *n_deleted = gone;
+    return DNAGPU_OK;
+    });
+}
 
 extern "C" int dnagpu_kmer_index_scan(dnagpu_ctx *ctx, const dnagpu_kmer_index *idx, const dnagpu_filter *filter,
                                       uint64_t *out_rows, uint64_t *out_keys, uint64_t cap, uint64_t *n_out, uint64_t *visited,

@@ -1,5 +1,6 @@
 // index_kernels.hip -- the index over a stored kmer column (test.sql:156-270): a stable LSD radix sort of
-// (r, row) pairs by 8-bit digits, the range-pruned scan behind `=`, `^@` and `@>`, the batch lookup and the window read.
+// (r, row) pairs by 8-bit digits, the range-pruned scan behind `=`, `^@` and `@>`, the batch lookup and the window read, and
+// the two updates: the merge-path merge of an appended batch and the bitmap + compaction of a delete.
 // No workgroup ever waits for another inside a launch: every pass is histogram -> scan -> scatter, three launches.
 #include <algorithm>
 
@@ -19,9 +20,9 @@ static_assert(IX_DIGITS == IX_THREADS, "one thread per digit scans the waves' co
 
 __device__ __forceinline__ void ix_load(const IndexSortSrc &s, u64 idx, u64 *r, u32 *row)
 {
-    if (s.keys) {               // the first pass that moves anything: the caller's keys, row = position
+    if (s.keys) {               // the first pass that moves anything: the caller's keys, row = row_base + position
         *r = index_r_of_key(s.keys[idx], s.k);
-        *row = (u32)idx;
+        *row = s.row_base + (u32)idx;
     } else {
         *r = s.r[idx];
         *row = s.row[idx];
@@ -303,6 +304,163 @@ __global__ __launch_bounds__(IX_THREADS) void index_read_kernel(const u64 *__res
         out_keys[i] = index_key_of_r(r[first + i], k);
 }
 
+
+// ---- append: the stable merge of the index (A) and the sorted batch (B)
+
+// part[t] = the split of diagonal min(t * INDEX_SORT_TILE, na + nb), t = 0 .. n_tiles: one thread per tile boundary
+__global__ __launch_bounds__(IX_THREADS) void index_merge_partition_kernel(const u64 *__restrict__ ar, u64 na, const u64 *__restrict__ br,
+                                                                           u64 nb, u32 n_tiles, u32 *__restrict__ part)
+{
+    const u64 t = (u64)blockIdx.x * IX_THREADS + threadIdx.x;
+    if (t > n_tiles)
+        return;
+    const u64 d = std::min(t * INDEX_SORT_TILE, na + nb);
+    part[t] = (u32)index_merge_split([=](u64 i) { return ar[i]; }, na, [=](u64 i) { return br[i]; }, nb, d);
+}
+
+// Where entry p of a staged tile lies in LDS: one slot of padding behind every 16.  Thread t then meets its 8 consecutive
+// entries at 8 t + t / 2 + i: the 16 lanes of an LDS write group (and the 32 of a read group) on 16 (32) different 8-byte
+// columns of the bank row, where the dense layout puts them on two.  Lane-consecutive accesses stay conflict-free.
+constexpr int IX_MERGE_SLOTS = INDEX_SORT_TILE + INDEX_SORT_TILE / 16;
+__device__ __forceinline__ u32 ix_pad(u32 p)
+{
+    return p + (p >> 4);
+}
+
+// One tile of INDEX_SORT_TILE outputs: its slices of A and B (part[tile] .. part[tile + 1] of A, the rest of the diagonal
+// of B: together the tile's outputs, at most INDEX_SORT_TILE entries) are staged in LDS, A's slice first; thread t finds
+// the split of its own diagonal 8 t there and merges 8 outputs into registers; the outputs go back into LDS in output
+// order and leave as whole lines.  r compares as unsigned 64-bit; an exhausted side is never read.
+__global__ __launch_bounds__(IX_THREADS) void index_merge_kernel(const u64 *__restrict__ ar, const u32 *__restrict__ arow, u64 na,
+                                                                 const u64 *__restrict__ br, const u32 *__restrict__ brow, u64 nb,
+                                                                 const u32 *__restrict__ part, u64 *__restrict__ out_r,
+                                                                 u32 *__restrict__ out_row)
+{
+    __shared__ u64 s_r[IX_MERGE_SLOTS];
+    __shared__ u32 s_row[IX_MERGE_SLOTS];
+    const u32 tid = threadIdx.x;
+    const u64 d0 = (u64)blockIdx.x * INDEX_SORT_TILE;
+    const u64 d1 = std::min(d0 + INDEX_SORT_TILE, na + nb);
+    const u64 a0 = part[blockIdx.x], a1 = part[blockIdx.x + 1];
+    const u64 b0 = d0 - a0, b1 = d1 - a1;
+    if (a1 < a0 || a1 > na || b1 < b0 || b1 > nb)       // (never: the splits ascend with the diagonal)
+        return;
+    const u32 ta = (u32)(a1 - a0), tb = (u32)(b1 - b0), tn = ta + tb;       // tn = d1 - d0 <= INDEX_SORT_TILE
+    for (u32 i = tid; i < tn; i += IX_THREADS) {
+        const u32 p = ix_pad(i);
+        if (i < ta) {
+            s_r[p] = ar[a0 + i];
+            s_row[p] = arow[a0 + i];
+        } else {
+            s_r[p] = br[b0 + (i - ta)];
+            s_row[p] = brow[b0 + (i - ta)];
+        }
+    }
+    __syncthreads();
+    const u32 d = std::min(tid * (u32)IX_ITEMS, tn);
+    u32 a = (u32)index_merge_split([&](u64 i) { return s_r[ix_pad((u32)i)]; }, ta, [&](u64 i) { return s_r[ix_pad(ta + (u32)i)]; },
+                                   tb, d);
+    u32 b = d - a;
+    u64 va = a < ta ? s_r[ix_pad(a)] : 0, vb = b < tb ? s_r[ix_pad(ta + b)] : 0;
+    u64 r[IX_ITEMS];
+    u32 row[IX_ITEMS];
+#pragma unroll
+    for (int i = 0; i < IX_ITEMS; i++) {
+        const bool has_a = a < ta, has_b = b < tb;
+        const bool take_a = has_a && (!has_b || va <= vb);      // a tie goes to A: the old entry has the smaller row id
+        r[i] = take_a ? va : vb;
+        row[i] = 0;
+        if (take_a) {
+            row[i] = s_row[ix_pad(a)];
+            a++;
+            if (a < ta)
+                va = s_r[ix_pad(a)];
+        } else if (has_b) {
+            row[i] = s_row[ix_pad(ta + b)];
+            b++;
+            if (b < tb)
+                vb = s_r[ix_pad(ta + b)];
+        }
+    }
+    __syncthreads();                                    // every thread has read its inputs
+#pragma unroll
+    for (int i = 0; i < IX_ITEMS; i++) {
+        const u32 o = tid * IX_ITEMS + i;
+        if (o < tn) {
+            s_r[ix_pad(o)] = r[i];
+            s_row[ix_pad(o)] = row[i];
+        }
+    }
+    __syncthreads();
+    for (u32 i = tid; i < tn; i += IX_THREADS) {
+        out_r[d0 + i] = s_r[ix_pad(i)];
+        out_row[d0 + i] = s_row[ix_pad(i)];
+    }
+}
+
+// ---- delete: one bit per listed row id, then a stable compaction of the entries whose bit is clear
+
+__global__ __launch_bounds__(IX_THREADS) void index_mark_kernel(const u64 *__restrict__ ids, u64 m, u64 n_bits, u32 *__restrict__ bitmap)
+{
+    const u64 j = (u64)blockIdx.x * IX_THREADS + threadIdx.x;
+    if (j >= m)
+        return;
+    const u64 id = ids[j];
+    if (id < n_bits)                                    // an id the index was never given: ignored
+        atomicOr(&bitmap[id >> 5], 1u << (id & 31));
+}
+
+// The two sweeps of the compaction, the tile layout of the sort's scatter: wave w owns the slice [w * 64 * IX_ITEMS, ...)
+// of the tile, element (item i, lane l) at slice + 64 i + l, so that every load is a whole line and the kept entries of an
+// item land side by side.  An entry's rank in its tile = the kept entries of earlier waves (wsum) + of earlier items of its
+// wave (a running count) + of lower lanes of its item (one ballot).  WRITE = false: tiles[tile] = the kept entries;
+// WRITE = true: tiles = their exclusive scan.
+template <bool WRITE>
+__global__ __launch_bounds__(IX_THREADS) void index_compact_kernel(const u64 *__restrict__ r, const u32 *__restrict__ row, u64 n,
+                                                                   const u32 *__restrict__ bitmap, u32 *__restrict__ tiles,
+                                                                   u64 *__restrict__ out_r, u32 *__restrict__ out_row, u64 n_out)
+{
+    __shared__ u32 wsum[IX_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const u64 slice = (u64)blockIdx.x * INDEX_SORT_TILE + (u64)wave * 64 * IX_ITEMS;
+    u32 id[IX_ITEMS], rank[IX_ITEMS];
+    u32 kept = 0, cnt = 0;
+#pragma unroll
+    for (int i = 0; i < IX_ITEMS; i++) {
+        const u64 idx = slice + (u64)i * 64 + lane;
+        bool keep = false;
+        id[i] = 0;
+        if (idx < n) {
+            id[i] = row[idx];
+            keep = !((bitmap[id[i] >> 5] >> (id[i] & 31)) & 1u);
+        }
+        const u64 bal = __ballot(keep);
+        rank[i] = cnt + (u32)__popcll(bal & (((u64)1 << lane) - 1));
+        cnt += (u32)__popcll(bal);
+        kept |= keep ? 1u << i : 0u;
+    }
+    if (lane == 0)
+        wsum[wave] = cnt;
+    __syncthreads();
+    if (!WRITE) {
+        if (tid == 0)
+            tiles[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        return;
+    }
+    u64 base = tiles[blockIdx.x];
+    for (int w = 0; w < wave; w++)
+        base += wsum[w];
+#pragma unroll
+    for (int i = 0; i < IX_ITEMS; i++)
+        if (kept & (1u << i)) {
+            const u64 pos = base + rank[i];
+            if (pos < n_out) {                          // (always: the count sweep saw the same bits)
+                out_r[pos] = r[slice + (u64)i * 64 + lane];
+                out_row[pos] = id[i];
+            }
+        }
+}
+
 }  // namespace
 
 u32 index_sort_tiles(u64 n)
@@ -378,6 +536,48 @@ hipError_t launch_index_read(const u64 *r, const u32 *row, int k, u64 first, u64
 {
     hipLaunchKernelGGL(index_read_kernel, dim3((unsigned)((count + IX_THREADS - 1) / IX_THREADS)), dim3(IX_THREADS), 0, s, r, row,
                        k, first, count, out_rows, out_keys);
+    return hipGetLastError();
+}
+
+hipError_t launch_index_merge_partition(const u64 *ar, u64 na, const u64 *br, u64 nb, u32 *part, hipStream_t s)
+{
+    const u32 nt = index_sort_tiles(na + nb);
+    hipLaunchKernelGGL(index_merge_partition_kernel, dim3(nt / IX_THREADS + 1), dim3(IX_THREADS), 0, s, ar, na, br, nb, nt, part);
+    return hipGetLastError();
+}
+
+hipError_t launch_index_merge(const u64 *ar, const u32 *arow, u64 na, const u64 *br, const u32 *brow, u64 nb, const u32 *part,
+                              u64 *out_r, u32 *out_row, hipStream_t s)
+{
+    hipLaunchKernelGGL(index_merge_kernel, dim3(index_sort_tiles(na + nb)), dim3(IX_THREADS), 0, s, ar, arow, na, br, brow, nb, part,
+                       out_r, out_row);
+    return hipGetLastError();
+}
+
+u64 index_bitmap_words(u64 n_bits)
+{
+    return (n_bits + 31) / 32;
+}
+
+hipError_t launch_index_mark(const u64 *ids, u64 m, u64 n_bits, u32 *bitmap, hipStream_t s)
+{
+    hipLaunchKernelGGL(index_mark_kernel, dim3((unsigned)((m + IX_THREADS - 1) / IX_THREADS)), dim3(IX_THREADS), 0, s, ids, m, n_bits,
+                       bitmap);
+    return hipGetLastError();
+}
+
+hipError_t launch_index_compact_count(const u32 *row, u64 n, const u32 *bitmap, u32 *tile_counts, hipStream_t s)
+{
+    hipLaunchKernelGGL(index_compact_kernel<false>, dim3(index_sort_tiles(n)), dim3(IX_THREADS), 0, s, (const u64 *)nullptr, row, n,
+                       bitmap, tile_counts, (u64 *)nullptr, (u32 *)nullptr, (u64)0);
+    return hipGetLastError();
+}
+
+hipError_t launch_index_compact_write(const u64 *r, const u32 *row, u64 n, const u32 *bitmap, const u32 *tile_offsets, u64 *out_r,
+                                      u32 *out_row, u64 n_out, hipStream_t s)
+{
+    hipLaunchKernelGGL(index_compact_kernel<true>, dim3(index_sort_tiles(n)), dim3(IX_THREADS), 0, s, r, row, n, bitmap,
+                       const_cast<u32 *>(tile_offsets), out_r, out_row, n_out);
     return hipGetLastError();
 }
 

@@ -103,4 +103,22 @@ __host__ __device__ inline bool index_rest_is_any(const FilterBits &fb, int p)
     return true;
 }
 
+// Merge path (the append: a stable merge of the sorted runs A, the index, and B, the sorted batch).  The split of diagonal
+// d, 0 <= d <= na + nb: the a in [0, na] (b = d - a in [0, nb]) with A[a-1] <= B[b] and B[b-1] < A[a] wherever both sides
+// exist -- the first d outputs of the merge are A[0 .. a) and B[0 .. b), ties taken from A.  a_at(i) / b_at(i) read A[i] /
+// B[i] and are only called with i < na / i < nb: neither run is read past its end and no value of r is special.
+template <typename AAt, typename BAt>
+__host__ __device__ __forceinline__ u64 index_merge_split(AAt a_at, u64 na, BAt b_at, u64 nb, u64 d)
+{
+    u64 lo = d > nb ? d - nb : 0, hi = d < na ? d : na;
+    while (lo < hi) {
+        const u64 mid = lo + ((hi - lo) >> 1);      // lo <= mid < hi: mid < na, and 0 <= d - 1 - mid < nb
+        if (a_at(mid) <= b_at(d - 1 - mid))
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
 }  // namespace dnagpu

@@ -280,6 +280,7 @@ struct IndexSortSrc {                     // what a pass reads: the caller's key
     const u64 *r;
     const u32 *row;
     int k;
+    u32 row_base;                         // keys != null: row = row_base + position (the build: 0; an appended batch: next_row)
 };
 u32 index_sort_tiles(u64 n);
 hipError_t launch_index_hist(const IndexSortSrc &src, u64 n, int shift, u32 *hist, hipStream_t s);
@@ -314,6 +315,22 @@ hipError_t launch_index_sweep_write(const IndexScanArgs &a, const u32 *tile_offs
 hipError_t launch_index_lookup(const u64 *r, u64 n, int k, const u64 *keys, u64 m, u64 *out_first, u64 *out_count, hipStream_t s);
 // entries [first, first + count) as u64 row ids and un-reversed keys (either may be null)
 hipError_t launch_index_read(const u64 *r, const u32 *row, int k, u64 first, u64 count, u64 *out_rows, u64 *out_keys, hipStream_t s);
+// The append: the stable merge of the sorted runs A = (ar, arow)[0 .. na) and B = (br, brow)[0 .. nb) into (out_r, out_row)
+// [0 .. na + nb), an A entry before a B entry of the same r (index_math.hpp: index_merge_split).  Two launches: the
+// partition -- part[t] = the entries of A among the first min(t * INDEX_SORT_TILE, na + nb) outputs, t = 0 ..
+// index_sort_tiles(na + nb), by binary search in global memory -- and the merge, one workgroup per tile of INDEX_SORT_TILE
+// outputs.  na + nb <= 2^32 - 1.
+hipError_t launch_index_merge_partition(const u64 *ar, u64 na, const u64 *br, u64 nb, u32 *part, hipStream_t s);
+hipError_t launch_index_merge(const u64 *ar, const u32 *arow, u64 na, const u64 *br, const u32 *brow, u64 nb, const u32 *part,
+                              u64 *out_r, u32 *out_row, hipStream_t s);
+// The delete.  mark: bit ids[j] of bitmap (index_bitmap_words(n_bits) zeroed words) is set for every j < m with ids[j] <
+// n_bits.  The stable compaction of the entries whose row's bit is clear, in tiles of INDEX_SORT_TILE entries: count ->
+// tile_counts[tile]; write (tile_offsets = their exclusive scan) -> the kept entries in their order.  Every row[i] < n_bits.
+u64 index_bitmap_words(u64 n_bits);
+hipError_t launch_index_mark(const u64 *ids, u64 m, u64 n_bits, u32 *bitmap, hipStream_t s);
+hipError_t launch_index_compact_count(const u32 *row, u64 n, const u32 *bitmap, u32 *tile_counts, hipStream_t s);
+hipError_t launch_index_compact_write(const u64 *r, const u32 *row, u64 n, const u32 *bitmap, const u32 *tile_offsets, u64 *out_r,
+                                      u32 *out_row, u64 n_out, hipStream_t s);
 
 // ---------------------------------------------------------------- superkmer_kernels.hip
 // super-k-mer (minimizer) partitioning for long k-mers: the dna sweeps (level 0: records per coarse digit of every

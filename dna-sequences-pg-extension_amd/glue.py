@@ -118,6 +118,10 @@ def lib():
             f.argtypes = [vp, C.POINTER(_Kmer), C.POINTER(C.POINTER(C.c_int64))]
         L.kmer_index_scan_contains.restype = C.c_int64
         L.kmer_index_scan_contains.argtypes = [vp, C.POINTER(_Qkmer), C.POINTER(C.POINTER(C.c_int64))]
+        L.kmer_index_insert.restype = C.c_int64
+        L.kmer_index_insert.argtypes = [vp, C.POINTER(_Kmer), C.c_uint64]
+        L.kmer_index_delete.restype = C.c_int64
+        L.kmer_index_delete.argtypes = [vp, C.POINTER(C.c_int64), C.c_uint64]
         L.kmer_index_end.restype = None
         L.kmer_index_end.argtypes = [vp]
         _LIB = L
@@ -420,6 +424,24 @@ class kmer_index:
         if n:
             _libc.free(C.cast(rows, C.c_void_p))
         return out
+
+    def insert(self, rows):
+        """INSERT of a batch of kmer: they become rows first, first + 1, ... -> first"""
+        arr = (_Kmer * max(len(rows), 1))()
+        for i, x in enumerate(rows):
+            arr[i].length, arr[i].bit_sequence = x.c.length, x.c.bit_sequence
+        first = lib().kmer_index_insert(self.p, arr, len(rows))
+        if first < 0:
+            raise _err()
+        return int(first)
+
+    def delete(self, rows):
+        """VACUUM after DELETE: drops the entries of the listed row ids -> the entries removed"""
+        arr = (C.c_int64 * max(len(rows), 1))(*rows)
+        n = lib().kmer_index_delete(self.p, arr, len(rows))
+        if n < 0:
+            raise _err()
+        return int(n)
 
     def end(self):
         if self.p:

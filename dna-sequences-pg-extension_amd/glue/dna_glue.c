@@ -1182,6 +1182,52 @@ uint64_t kmer_index_rows(const KmerIndex *idx)
     return idx ? dnagpu_kmer_index_rows(idx->idx) : 0;
 }
 
+int64_t kmer_index_insert(KmerIndex *idx, const Kmer *rows, uint64_t n)
+{
+    if (!ctx())
+        return -1;
+    const int64_t first = (int64_t)dnagpu_kmer_index_next_row(idx->idx);
+    if (n == 0)
+        return first;
+    int k = idx->k;
+    if (first == 0)                                  /* created over an empty column: the first rows decide the length */
+        k = rows[0].length;
+    for (uint64_t i = 0; i < n; i++)
+        if (rows[i].length != k) {
+            ereport_error("kmer_index_create: the column holds kmers of %d and %d bases; an index covers one length", k,
+                          (int)rows[i].length);
+            return -1;
+        }
+    if (k != idx->k) {
+        dnagpu_kmer_index *empty = NULL;
+        if (!gpu_ok(dnagpu_kmer_index_build(g_ctx, NULL, 0, k, 0, &empty)))     /* a bad length: dna.c:773 */
+            return -1;
+        dnagpu_kmer_index_free(g_ctx, idx->idx);
+        idx->idx = empty;
+        idx->k = k;
+    }
+    uint64_t *keys = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)n);
+    if (!keys) {
+        ereport_error("out of memory");
+        return -1;
+    }
+    for (uint64_t i = 0; i < n; i++)
+        keys[i] = rows[i].bit_sequence;
+    const bool ok = gpu_ok(dnagpu_kmer_index_append(g_ctx, idx->idx, keys, n, 0));
+    free(keys);
+    return ok ? first : -1;
+}
+
+int64_t kmer_index_delete(KmerIndex *idx, const int64_t *rows, uint64_t n)
+{
+    if (!ctx())
+        return -1;
+    uint64_t gone = 0;                               /* a negative id reads as one above 2^32 - 1: ignored */
+    if (!gpu_ok(dnagpu_kmer_index_delete(g_ctx, idx->idx, (const uint64_t *)rows, n, 0, &gone)))
+        return -1;
+    return (int64_t)gone;
+}
+
 static int cmp_i64(const void *a, const void *b)
 {
     const int64_t x = *(const int64_t *)a, y = *(const int64_t *)b;

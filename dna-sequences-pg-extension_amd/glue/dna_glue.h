@@ -171,13 +171,22 @@ void table_kmers_end(TableKmers *t);
  * bitmap heap scan hands rows out in; the device answers in index order and the glue sorts on the host.  Returns the number
  * of rows and stores a malloc'd array in *rows (NULL when there are none); -1 + dna_glue_errmsg() on an ERROR: the reference's
  * own texts (dna.c:854-856, 1106-1108), raised only when the index has a row.  Exact, where the reference's index scans lose
- * rows (test.sql:191 against :208, :223 against :237) and its `@>` strategy does not work (dna--1.0.sql:308). */
+ * rows (test.sql:191 against :208, :223 against :237) and its `@>` strategy does not work (dna--1.0.sql:308).
+ * insert (aminsert; INSERT INTO kmer_data_t, test.sql:168-179): rows[j] becomes heap row first + j, first = the rows the index
+ * has ever been given; returns first, or -1 + message.  One call appends one BATCH (dnagpu_kmer_index_append: a sort of the
+ * batch and one merge with the index): the caller collects a statement's rows and inserts them together before the next scan.
+ * A kmer of another length is refused with kmer_index_create's message for mixed lengths; an index created over an empty
+ * column takes the length of its first rows.
+ * delete (ambulkdelete; VACUUM, test.sql:184): removes the entries of the listed heap rows; ids the index does not hold are
+ * ignored, ids are never reused.  Returns the entries removed, or -1 + message. */
 typedef struct KmerIndex KmerIndex;
 KmerIndex *kmer_index_create(const Kmer *column, uint64_t n);
 uint64_t kmer_index_rows(const KmerIndex *idx);
 int64_t kmer_index_scan_eq(KmerIndex *idx, const Kmer *rhs, int64_t **rows);
 int64_t kmer_index_scan_starts_with(KmerIndex *idx, const Kmer *prefix, int64_t **rows);
 int64_t kmer_index_scan_contains(KmerIndex *idx, const Qkmer *pattern, int64_t **rows);
+int64_t kmer_index_insert(KmerIndex *idx, const Kmer *rows, uint64_t n);
+int64_t kmer_index_delete(KmerIndex *idx, const int64_t *rows, uint64_t n);
 void kmer_index_end(KmerIndex *idx);
 
 #ifdef __cplusplus

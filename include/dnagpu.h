@@ -35,7 +35,8 @@ extern "C" {
  * bucket groups per owner -- dnagpu_hist_device_keys / _counts are NULL for those), the dnagpu_multi_* options, the
  * table-of-sequences count (dnagpu_count_kmers_batch, dnagpu_dna_set_sequences + dnagpu_count_kmers_table,
  * dnagpu_hist_merge), the rows of a table of sequences with the fused WHERE forms (dnagpu_generate_kmers_table), the index
- * over a stored kmer column (dnagpu_kmer_index_*: additions only, so the number stays) */
+ * over a stored kmer column (dnagpu_kmer_index_*) and its updates (dnagpu_kmer_index_append / _delete / _next_row):
+ * additions only, so the number stays */
 #define DNAGPU_ABI_VERSION 2
 
 /* ---- status codes ------------------------------------------------------------------------
@@ -574,14 +575,16 @@ int dnagpu_kmer_match(dnagpu_ctx *ctx, const uint64_t *keys, uint64_t n, int k,
  * 208, 4036 of 4044 at :223 / :237) and its `@>` strategy is marked "DOES NOT WORK" (dna--1.0.sql:308).
  * Order: entries are sorted by the key's TEXT under A < T < C < G (base 0 most significant), row ids ascending among equal
  *   keys: "index order".  The keys that start with a given prefix are one contiguous window of it.
- * Snapshot: an index of n rows owns 12 bytes per row from the context's pool (the stream rule below) and does not depend on
- *   the caller's key array afterwards; the build only reads that array (unlike dnagpu_count_keys).  No incremental insert.
+ * Storage: an index of n entries owns 12 bytes per entry from the context's pool (the stream rule below) and does not depend
+ *   on the caller's key array afterwards; the build only reads that array (unlike dnagpu_count_keys).  It is kept up to date
+ *   with dnagpu_kmer_index_append and dnagpu_kmer_index_delete (below) without a rebuild.  What it does not do: one k per
+ *   index; one GPU; row ids are not reused; no update in place -- a changed row is a delete plus an append.
  * dnagpu_kmer_index_build: keys = n keys of k bases, host memory, or device memory when on_device != 0; bits of a key above
  *   2k are masked off; row id = position in keys.  Checks, in order: k outside 1..32: DNAGPU_ERR_INVALID_K; NULL ctx / out,
  *   NULL keys with n > 0: DNAGPU_ERR_BAD_ARG; n > 2^32 - 1: DNAGPU_ERR_TOO_LARGE (before any device work).  n == 0: a valid
  *   index of 0 rows that holds no device memory; every scan of it returns 0 rows.  An allocation failure is DNAGPU_ERR_OOM
  *   with nothing leaked and *out = NULL.
- * dnagpu_kmer_index_rows / _distinct / _k: rows, distinct keys, k (0 for NULL).
+ * dnagpu_kmer_index_rows / _distinct / _k: entries now, distinct keys among them (exact after every update), k (0 for NULL).
  * dnagpu_kmer_index_scan: the rows that satisfy `filter`, in index order (NOT heap order: a caller that wants ascending row
  *   ids sorts the answer): row ids (as uint64) to out_rows and the keys to out_keys (either may be NULL), at most cap of
  *   each, host memory, or device memory when out_on_device != 0; *n_out = all matches even beyond cap; *visited (may be
@@ -598,7 +601,27 @@ int dnagpu_kmer_match(dnagpu_ctx *ctx, const uint64_t *keys, uint64_t n, int k,
  *   A query key with bits above 2k matches nothing.  keys / out_* all host, or all device when on_device != 0.
  * dnagpu_kmer_index_read: entries [first, first + count) of the index order (dnagpu_hist_download's window rule: first > rows
  *   or count > rows - first is DNAGPU_ERR_BAD_ARG; count == 0 or both outputs NULL is DNAGPU_OK).
- * dnagpu_kmer_index_free returns the arrays to ctx's pool (NULL idx: nothing). */
+ * dnagpu_kmer_index_free returns the arrays to ctx's pool (NULL idx: nothing).
+ * Updates (aminsert / ambulkdelete of the reference's operator class: spgist_kmer_choose / _picksplit, dna.c:1253-1502;
+ * test.sql:168-184):
+ * Row ids: dnagpu_kmer_index_next_row = the rows the index has ever been given, the build's n plus every append's m (0 for
+ *   NULL).  Appended key j gets row id next_row + j.  Ids are never reused after a delete; dnagpu_kmer_index_rows stays
+ *   "entries now".
+ * dnagpu_kmer_index_append: m keys of the index's k (bits above 2k are masked off), host memory, or device memory when
+ *   on_device != 0; only read.  The batch is sorted like a build and merged with the index in one stable pass, an old entry
+ *   before a new one of the same key -- every new id is larger than every old one, so the result is index order, and for an
+ *   index that has had no delete exactly what dnagpu_kmer_index_build gives over the concatenated column.  Checks, in order:
+ *   NULL ctx / idx, NULL keys with m > 0: DNAGPU_ERR_BAD_ARG; next_row + m > 2^32 - 1: DNAGPU_ERR_TOO_LARGE (before any
+ *   device work).  m == 0: DNAGPU_OK, nothing changes.  An index of 0 entries (built with n = 0, or emptied by deletes) takes
+ *   an append like any other.
+ * dnagpu_kmer_index_delete: rows = m row ids as uint64, in any order, host memory, or device memory when on_device != 0; only
+ *   read.  Ignored: ids that are not in the index (never given, already deleted, >= next_row), repeats within the list, ids
+ *   above 2^32 - 1.  *n_deleted (may be NULL) = the entries removed.  The remaining entries keep their ids and their order.
+ *   NULL ctx / idx, NULL rows with m > 0: DNAGPU_ERR_BAD_ARG; m > 2^32 - 1: DNAGPU_ERR_TOO_LARGE.  Deleting every entry
+ *   leaves a valid index of 0 entries that holds no device memory; next_row is unchanged.
+ * Both: the new arrays are built in new pool buffers and take over only when the call succeeds (dnagpu_acc_add's rule), so
+ *   every error -- DNAGPU_ERR_OOM, a HIP error -- leaves the index exactly as it was, with nothing leaked.  During the call the
+ *   pool holds the old and the new arrays.  The call waits for its work: a scan right after sees the new index. */
 typedef struct dnagpu_kmer_index dnagpu_kmer_index;
 #define DNAGPU_INDEX_MAX_RANGES 1024u
 int dnagpu_kmer_index_build(dnagpu_ctx *ctx, const uint64_t *keys, uint64_t n, int k, int on_device, dnagpu_kmer_index **out);
@@ -612,6 +635,10 @@ int dnagpu_kmer_index_lookup(dnagpu_ctx *ctx, const dnagpu_kmer_index *idx, cons
 int dnagpu_kmer_index_read(dnagpu_ctx *ctx, const dnagpu_kmer_index *idx, uint64_t first, uint64_t count, uint64_t *out_rows,
                            uint64_t *out_keys, int out_on_device);
 void dnagpu_kmer_index_free(dnagpu_ctx *ctx, dnagpu_kmer_index *idx);
+int dnagpu_kmer_index_append(dnagpu_ctx *ctx, dnagpu_kmer_index *idx, const uint64_t *keys, uint64_t m, int on_device);
+int dnagpu_kmer_index_delete(dnagpu_ctx *ctx, dnagpu_kmer_index *idx, const uint64_t *rows, uint64_t m, int on_device,
+                             uint64_t *n_deleted);
+uint64_t dnagpu_kmer_index_next_row(const dnagpu_kmer_index *idx);
 
 /* ---- debug aids (off by default) ---------------------------------------------------------------
  * DNAGPU_DEBUG_POISON_POOL: every work buffer the pool hands out -- fresh or recycled, internal or through
