@@ -14,6 +14,8 @@ from .binding import (  # noqa: F401
     DEBUG_FORCE_SUPERKMER,
     DEBUG_GUARD_POOL,
     DEBUG_HEAVY_EXPAND,
+    DEBUG_JOIN_DIRECT,
+    DEBUG_JOIN_PARTITION,
     DEBUG_NO_SLAB0,
     DEBUG_NO_SPEC1,
     DEBUG_POISON_POOL,
@@ -28,6 +30,10 @@ from .binding import (  # noqa: F401
     DnaGpuError,
     Filter,
     Hist,
+    JOIN_ANTI,
+    JOIN_INNER,
+    JOIN_LEFT,
+    JoinStats,
     KmerIndex,
     Records,
     SPECTRUM_MAX_BINS,

@@ -31,6 +31,11 @@ DEBUG_NO_SLAB0 = 128
 DEBUG_SLAB0_OVERFLOW = 256
 DEBUG_SAMPLE1 = 512                   # level 1: regions from a sampled histogram whatever the coarse buckets look like
 DEBUG_RANK_SMALL = 1024               # rank: a class limit of 4 counts and sort chunks of 2048 rows (the tail path at small sizes)
+DEBUG_JOIN_PARTITION = 2048           # dnagpu_acc_join: the partition path for any sizes
+DEBUG_JOIN_DIRECT = 4096              # dnagpu_acc_join: the direct path for any sizes
+JOIN_INNER = 0                        # JOIN .. ON a.kmer = b.kmer; INTERSECT
+JOIN_ANTI = 1                         # EXCEPT; NOT IN; NOT EXISTS
+JOIN_LEFT = 2                         # LEFT JOIN
 SPECTRUM_MAX_BINS = 1 << 20
 TOP_MAX = 1 << 20
 ORDER_COUNT_DESC = 0                  # ORDER BY count(*) DESC (test.sql:95)
@@ -61,6 +66,14 @@ u64p = C.POINTER(C.c_uint64)
 class _FilterC(C.Structure):
     _fields_ = [("kind", C.c_int32), ("length", C.c_int32), ("bits", C.c_uint64),
                 ("pattern", C.c_char * 36), ("reserved", C.c_int32)]
+
+
+class JoinStats(C.Structure):
+    """dnagpu_join_stats: the statistics of a join over all its result rows"""
+    _fields_ = [(n, C.c_uint64) for n in ("rows", "sum_left", "sum_right", "sum_min", "checksum_left", "checksum_right")]
+
+    def as_tuple(self):
+        return tuple(int(getattr(self, n)) for n, _ in self._fields_)
 
 
 class _PhaseTimes(C.Structure):
@@ -172,6 +185,9 @@ def lib():
     L.dnagpu_acc_download.argtypes = [vp, vp, C.c_uint64, C.c_uint64, u64p, u64p]
     L.dnagpu_acc_free.argtypes = [vp, vp]
     L.dnagpu_acc_free.restype = None
+    L.dnagpu_acc_join.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, C.c_uint64, u64p, C.POINTER(JoinStats), C.c_int]
+    L.dnagpu_acc_partitions.argtypes = [vp]
+    L.dnagpu_acc_partitions.restype = C.c_uint64
     for obj in ("hist", "acc"):
         getattr(L, f"dnagpu_{obj}_spectrum").argtypes = [vp, vp, C.c_uint64, u64p]
         getattr(L, f"dnagpu_{obj}_select").argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, u64p, C.c_int]
@@ -662,11 +678,40 @@ class Accumulator(_CountQueries):
     def total(self):
         return int(lib().dnagpu_acc_total(self.h))
 
+    @property
+    def partitions(self):
+        """partitions of the table, a power of two (0: no table yet)"""
+        return int(lib().dnagpu_acc_partitions(self.h))
+
     def summary(self):
         """(total, distinct, unique, checksum) -- same tuple as Hist.summary and the oracle's hist_summary"""
         t, u, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
         _chk(lib().dnagpu_acc_summary(self.ctx.h, self.h, C.byref(t), C.byref(u), C.byref(c)))
         return t.value, self.distinct, u.value, c.value
+
+    def join(self, other, kind=JOIN_INNER, cap=None, on_device=False, out=None, want_rows=True):
+        """the hash join with `other` on the k-mer (dnagpu_acc_join), self = the left side: JOIN_INNER the groups both hold,
+        JOIN_ANTI those only self holds, JOIN_LEFT every group of self; order unspecified -> (keys, left, right, stats):
+        at most cap rows (cap=None: all of them -- two calls, the first takes the statistics and sizes the arrays),
+        stats = JoinStats over ALL result rows.  want_rows=False: the statistics only, the arrays are None.
+        on_device: the rows go to device arrays of cap uint64 each -- out=(dev_keys, dev_left, dev_right) (any may be
+        None); without out they are allocated here (Context.buffer_free them)"""
+        n, st = C.c_uint64(), JoinStats()
+        fn = lib().dnagpu_acc_join
+        if not want_rows or cap is None:
+            _chk(fn(self.ctx.h, self.h, other.h, kind, None, None, None, 0, C.byref(n), C.byref(st), 0))
+            if not want_rows:
+                return None, None, None, st
+            cap = n.value
+        if on_device:
+            bufs = out if out is not None else tuple(self.ctx.buffer_alloc(8 * max(cap, 1)) for _ in range(3))
+            _chk(fn(self.ctx.h, self.h, other.h, kind, bufs[0], bufs[1], bufs[2], cap, C.byref(n), C.byref(st), 1))
+            return bufs[0], bufs[1], bufs[2], st
+        arrs = [np.empty(max(cap, 1), dtype=np.uint64) for _ in range(3)]
+        _chk(fn(self.ctx.h, self.h, other.h, kind, arrs[0].ctypes.data, arrs[1].ctypes.data, arrs[2].ctypes.data, cap,
+                C.byref(n), C.byref(st), 0))
+        m = min(n.value, cap)
+        return arrs[0][:m], arrs[1][:m], arrs[2][:m], st
 
     def download(self, first=0, count=None):
         """groups [first, first+count) as (keys, counts) uint64 arrays; order unspecified but fixed until the next add"""

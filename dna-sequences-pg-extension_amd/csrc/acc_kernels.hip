@@ -13,45 +13,16 @@
 // phase B claims empty slots for the rest by LDS compare-and-swap on the count.  No per-group global atomics in the merge.
 #include <hip/hip_runtime.h>
 
-#include "kernels.hpp"
+#include "acc_device.hpp"
 
 namespace dnagpu {
 
 namespace {
 
-constexpr int MERGE_NT = 512;                              // threads of a partition's workgroup
-constexpr int PER_T = ACC_SLOTS / MERGE_NT;                // slots (and at most bin entries) per thread: 8
+// (acc_home, ld_slot / st_slot and load_region: acc_device.hpp -- the join's partition path loads a partition the same way)
+constexpr int MERGE_NT = ACC_NT;                           // threads of a partition's workgroup
+constexpr int PER_T = ACC_PER_T;                           // slots (and at most bin entries) per thread: 8
 
-__device__ __forceinline__ u32 acc_home(u64 h) { return (u32)h & (ACC_SLOTS - 1); }
-
-// 16-byte slot load / store as one dwordx4
-__device__ __forceinline__ void ld_slot(const u64 *p, u64 &k, u64 &c)
-{
-    const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(p);
-    k = v.x;
-    c = v.y;
-}
-__device__ __forceinline__ void st_slot(u64 *p, u64 k, u64 c)
-{
-    ulonglong2 v;
-    v.x = k;
-    v.y = c;
-    *reinterpret_cast<ulonglong2 *>(p) = v;
-}
-
-// lds[2 s] = key, lds[2 s + 1] = count of slot s.  A partition that is occupied is loaded whole; else zeroed.
-__device__ __forceinline__ void load_region(u64 *lds, const u64 *__restrict__ region, bool occupied)
-{
-#pragma unroll
-    for (int j = 0; j < PER_T; j++) {
-        const int s = j * MERGE_NT + (int)threadIdx.x;
-        u64 k = 0, c = 0;
-        if (occupied)
-            ld_slot(region + 2 * (u64)s, k, c);
-        lds[2 * s] = k;
-        lds[2 * s + 1] = c;
-    }
-}
 __device__ __forceinline__ void store_region(const u64 *lds, u64 *__restrict__ region)
 {
 #pragma unroll

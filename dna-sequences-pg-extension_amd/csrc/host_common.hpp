@@ -1,5 +1,5 @@
 // host_common.hpp -- what the host files of the C-ABI (dnagpu_api.hip, count_host.hip, sk_host.hip, multi_host.hip, query_host.hip,
-// filter_host.hip, index_host.hip) share
+// filter_host.hip, index_host.hip, join_host.hip) share
 // (internal, like kernels.hpp): the error macros, the context / dna / histogram objects, the buffer pool, and the few
 // functions one of the files calls in another.  Declarations only, plus the templates and macros that must be visible;
 // the definitions are in dnagpu_api.hip unless a section says otherwise.
@@ -264,7 +264,7 @@ int count_sk_received(dnagpu_ctx *ctx, void *rec0, const std::vector<u64> &boff,
                       int k, dnagpu_hist *h, u64 rec0_cap = 0);
 }  // namespace dnagpu
 
-// the k-mer accumulator (dnagpu_api.hip: dnagpu_acc_*; query_host.hip reads the table)
+// the k-mer accumulator (dnagpu_api.hip: dnagpu_acc_*; query_host.hip and join_host.hip read the table)
 namespace dnagpu {
 struct AccTable {
     u64 *table = nullptr;     // 2^pbits * ACC_SLOTS * {key, count}

@@ -199,6 +199,32 @@ hipError_t launch_acc_summary(const u64 *table, const u32 *occ, u64 P, u64 *res3
 hipError_t launch_acc_gather(const u64 *table, const u32 *occ, const u64 *pre, u64 p_lo, u64 n_parts, u64 first, u64 count,
                              u64 *out_keys, u64 *out_counts, hipStream_t s);
 
+// ---- the join of two accumulators (join_kernels.hip).  For every group of the left table (2^s partitions)
+// the count of its key in the right table (2^t partitions; r_table == nullptr: right holds no table, t = 0, every row is a
+// miss) decides whether it is a result row of `kind`.  Result rows are ranked by one returning atomic per workgroup on
+// res[0]; row `at` is stored at out_*[at - out_base] when at < cap (any array may be null; out_base = what res[0] held
+// when the launch was queued: the host reads a result larger than its staging buffers chunk by chunk).  res[0] += the result
+// rows; res[1 ..] += sum_left, sum_right, sum_min, checksum_left, checksum_right over them (dnagpu_join_stats).
+// Both launchers cover left's partitions [p_lo, p_lo + n_parts):
+//   partition: one workgroup per partition of the finer side; right's partition in LDS, left's streamed past it
+//   direct:    one workgroup per 2048 slots of left; every group probes right's table in global memory
+constexpr int JOIN_KIND_INNER = 0, JOIN_KIND_ANTI = 1, JOIN_KIND_LEFT = 2;    // DNAGPU_JOIN_*
+constexpr int JOIN_RES_WORDS = 6;
+struct JoinArgs {
+    const u64 *l_table;
+    const u32 *l_occ;
+    int s;
+    const u64 *r_table;
+    const u32 *r_occ;
+    int t;
+    int kind;
+    u64 *out_keys, *out_left, *out_right;
+    u64 cap, out_base;
+    unsigned long long *res;
+};
+hipError_t launch_join_partition(const JoinArgs &a, u64 p_lo, u64 n_parts, hipStream_t st);
+hipError_t launch_join_direct(const JoinArgs &a, u64 p_lo, u64 n_parts, hipStream_t st);
+
 // ---- queries over counted groups (query_kernels.hip).  A group source is a histogram part (n slots of
 // keys / 32-bit counts, count 0 = padding) or the accumulator's table (n = P * ACC_SLOTS 16-byte slots, occ[p] == 0: the
 // partition is not read); both are cut into tiles of Q_TILE slots.

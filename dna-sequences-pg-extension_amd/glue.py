@@ -99,6 +99,16 @@ def lib():
         L.count_kmers_ordered_begin.argtypes = [vp, C.c_int, C.c_bool]
         L.count_kmers_agg_order.restype = C.c_bool
         L.count_kmers_agg_order.argtypes = [vp, C.c_bool]
+        L.count_kmers_join_begin.restype = vp
+        L.count_kmers_join_begin.argtypes = [vp, vp, C.c_char]
+        L.count_kmers_join_next.restype = C.c_bool
+        L.count_kmers_join_next.argtypes = [vp, C.POINTER(_Kmer), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.count_kmers_join_failed.restype = C.c_bool
+        L.count_kmers_join_failed.argtypes = [vp]
+        L.count_kmers_join_stats.restype = None
+        L.count_kmers_join_stats.argtypes = [vp] + [C.POINTER(C.c_int64)] * 4
+        L.count_kmers_join_end.restype = None
+        L.count_kmers_join_end.argtypes = [vp]
         L.table_kmers_begin.restype = vp
         L.table_kmers_begin.argtypes = [C.c_int, C.c_char, C.POINTER(_Kmer), C.POINTER(_Qkmer)]
         L.table_kmers_add.restype = C.c_bool
@@ -364,6 +374,66 @@ def count_kmers_agg(rows, k, _top=None, _order=None):
         return out, (t.value, dd.value, u.value)
     finally:
         lib().count_kmers_agg_end(a)
+
+
+class count_kmers_table_agg:
+    """one count_kmers_agg aggregate kept open (count_kmers_agg_begin .. _end): rows added with add(), the groups read
+    with groups(), two of them paired with count_kmers_join()"""
+
+    def __init__(self, k, rows=()):
+        self.a = lib().count_kmers_agg_begin(k)
+        if not self.a:
+            raise _err()
+        self.keep = []
+        for r in rows:
+            self.add(r)
+
+    def add(self, row):
+        row = row if isinstance(row, dna) else dna(row)
+        self.keep.append(row)
+        if not lib().count_kmers_agg_add(self.a, row.p):
+            raise _err()
+
+    def groups(self):
+        """the remaining FINALFUNC rows: [(kmer, count)]"""
+        out = []
+        km, cnt = _Kmer(), C.c_int64()
+        while lib().count_kmers_agg_next(self.a, C.byref(km), C.byref(cnt)):
+            out.append((kmer(c=_Kmer(km.length, km.bit_sequence)), cnt.value))
+        if lib().count_kmers_agg_failed(self.a):
+            raise _err()
+        return out
+
+    def end(self):
+        if self.a:
+            lib().count_kmers_agg_end(self.a)
+            self.a = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.end()
+
+
+def count_kmers_join(left, right, kind="i"):
+    """two count_kmers_table_agg paired on the k-mer: kind 'i' JOIN / INTERSECT, 'a' EXCEPT / NOT IN, 'l' LEFT JOIN ->
+    ([(kmer, count_left, count_right)], (rows, sum_left, sum_right, sum_min))"""
+    j = lib().count_kmers_join_begin(left.a, right.a, kind.encode()[:1] or b"\0")
+    if not j:
+        raise _err()
+    try:
+        out = []
+        km, cl, cr = _Kmer(), C.c_int64(), C.c_int64()
+        while lib().count_kmers_join_next(j, C.byref(km), C.byref(cl), C.byref(cr)):
+            out.append((kmer(c=_Kmer(km.length, km.bit_sequence)), cl.value, cr.value))
+        if lib().count_kmers_join_failed(j):
+            raise _err()
+        st = [C.c_int64() for _ in range(4)]
+        lib().count_kmers_join_stats(j, *[C.byref(x) for x in st])
+        return out, tuple(x.value for x in st)
+    finally:
+        lib().count_kmers_join_end(j)
 
 
 def table_kmers(rows, k, op=None, rhs=None):

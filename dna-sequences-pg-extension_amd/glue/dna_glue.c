@@ -960,6 +960,138 @@ void count_kmers_agg_end(CountKmersAgg *a)
     free(a);
 }
 
+/* ------------------------------------------------------------------ the join of two aggregates on the k-mer */
+
+#define CK_JOIN_WINDOW ((uint64_t)1 << 20)
+
+struct CountKmersJoin {
+    int k;
+    bool failed;
+    dnagpu_join_stats stats;
+    uint64_t rows;                               /* rows _next serves */
+    uint64_t *dev[3];                            /* keys, count_left, count_right: the whole result, on the device */
+    uint64_t *win[3];                            /* the window being served, on the host */
+    uint64_t next, win_first, win_count;
+};
+
+/* the aggregate's accumulator with every row so far in it (an aggregate that saw no row gets an empty one) */
+static dnagpu_acc *agg_flushed_acc(CountKmersAgg *a)
+{
+    if (a->failed) {
+        ereport_error("count_kmers_join: an aggregate has failed");
+        return NULL;
+    }
+    if (!agg_flush(a)) {
+        a->failed = true;
+        return NULL;
+    }
+    if (!a->acc && (!ctx() || !gpu_ok(dnagpu_acc_create(g_ctx, a->k, &a->acc))))
+        return NULL;
+    return a->acc;
+}
+
+CountKmersJoin *count_kmers_join_begin(CountKmersAgg *left, CountKmersAgg *right, char kind)
+{
+    const int kd = kind == 'i' ? DNAGPU_JOIN_INNER : kind == 'a' ? DNAGPU_JOIN_ANTI : kind == 'l' ? DNAGPU_JOIN_LEFT : -1;
+    if (kd < 0) {
+        ereport_error("count_kmers_join: unknown kind '%c' (expected 'i', 'a' or 'l')", kind);
+        return NULL;
+    }
+    if (!left || !right) {
+        ereport_error("count_kmers_join: an aggregate is missing");
+        return NULL;
+    }
+    if (left->k != right->k) {
+        ereport_error("count_kmers_join: the two sides count kmers of different lengths (%d and %d)", left->k, right->k);
+        return NULL;
+    }
+    dnagpu_acc *la = agg_flushed_acc(left);
+    dnagpu_acc *ra = la ? agg_flushed_acc(right) : NULL;
+    if (!la || !ra)
+        return NULL;
+    CountKmersJoin *j = (CountKmersJoin *)calloc(1, sizeof *j);
+    if (!j) {
+        ereport_error("out of memory");
+        return NULL;
+    }
+    j->k = left->k;
+    /* the statistics size the device buffers; the second call fills them */
+    uint64_t n = 0;
+    bool ok = gpu_ok(dnagpu_acc_join(g_ctx, la, ra, kd, NULL, NULL, NULL, 0, &n, &j->stats, 0));
+    if (ok && n > 0) {
+        for (int i = 0; ok && i < 3; i++) {
+            void *d = NULL;
+            ok = gpu_ok(dnagpu_buffer_alloc(g_ctx, n * sizeof(uint64_t), &d));
+            j->dev[i] = (uint64_t *)d;
+            if (ok) {
+                const uint64_t w = n < CK_JOIN_WINDOW ? n : CK_JOIN_WINDOW;
+                j->win[i] = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)w);
+                if (!j->win[i]) {
+                    ereport_error("out of memory");
+                    ok = false;
+                }
+            }
+        }
+        uint64_t got = 0;
+        ok = ok && gpu_ok(dnagpu_acc_join(g_ctx, la, ra, kd, j->dev[0], j->dev[1], j->dev[2], n, &got, NULL, 1));
+        if (ok && got != n) {
+            ereport_error("count_kmers_join: %llu rows, then %llu", (unsigned long long)n, (unsigned long long)got);
+            ok = false;
+        }
+    }
+    if (!ok) {
+        count_kmers_join_end(j);
+        return NULL;
+    }
+    j->rows = n;
+    return j;
+}
+
+bool count_kmers_join_next(CountKmersJoin *j, Kmer *kmer, int64_t *count_left, int64_t *count_right)
+{
+    if (j->failed || j->next >= j->rows)
+        return false;
+    if (j->next >= j->win_first + j->win_count) {
+        const uint64_t n = j->rows - j->next < CK_JOIN_WINDOW ? j->rows - j->next : CK_JOIN_WINDOW;
+        for (int i = 0; i < 3; i++)
+            if (!gpu_ok(dnagpu_buffer_download(g_ctx, j->dev[i] + j->next, n * sizeof(uint64_t), j->win[i]))) {
+                j->failed = true;
+                return false;
+            }
+        j->win_first = j->next;
+        j->win_count = n;
+    }
+    const uint64_t at = j->next - j->win_first;
+    kmer->length = j->k;
+    kmer->bit_sequence = j->win[0][at];
+    *count_left = (int64_t)j->win[1][at];
+    *count_right = (int64_t)j->win[2][at];
+    j->next++;
+    return true;
+}
+
+bool count_kmers_join_failed(const CountKmersJoin *j) { return j->failed; }
+
+void count_kmers_join_stats(const CountKmersJoin *j, int64_t *rows, int64_t *sum_left, int64_t *sum_right, int64_t *sum_min)
+{
+    if (rows) *rows = (int64_t)j->stats.rows;
+    if (sum_left) *sum_left = (int64_t)j->stats.sum_left;
+    if (sum_right) *sum_right = (int64_t)j->stats.sum_right;
+    if (sum_min) *sum_min = (int64_t)j->stats.sum_min;
+}
+
+void count_kmers_join_end(CountKmersJoin *j)
+{
+    if (!j)
+        return;
+    for (int i = 0; i < 3; i++) {
+        if (j->dev[i])
+            dnagpu_buffer_free(g_ctx, j->dev[i]);
+        free(j->win[i]);
+    }
+    free(j);
+}
+
 /* ------------------------------------------------------------------ the ROWS of a table: kmers_of_table */
 
 #define TK_WINDOW ((uint64_t)1 << 20)     /* stream rows per refill: a window never holds more table rows than stream rows */

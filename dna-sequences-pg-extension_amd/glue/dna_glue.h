@@ -143,6 +143,23 @@ bool count_kmers_agg_order(CountKmersAgg *a, bool descending);
 /* bases per batch (default 2^30); tests use small values to force many batches */
 void dna_glue_set_agg_flush_bases(uint64_t n);
 
+/* ---- two counted tables paired on the k-mer -- what the reference's kmer_hash_ops (dna--1.0.sql:204-212) gives the planner
+ * besides GROUP BY:
+ *   'i'  SELECT a.kmer, a.count, b.count FROM counts_a a JOIN counts_b b ON a.kmer = b.kmer;  ... INTERSECT ...
+ *   'a'  SELECT kmer FROM counts_a EXCEPT SELECT kmer FROM counts_b;  NOT IN;  NOT EXISTS      (count_right = 0)
+ *   'l'  ... FROM counts_a a LEFT JOIN counts_b b ON a.kmer = b.kmer                           (count_right = 0: no partner)
+ * over two count_kmers_agg aggregates.  begin flushes both (rows added so far are in; the aggregates stay usable afterwards:
+ * more rows, count_kmers_agg_next, further joins), joins their accumulators on the device (dnagpu_acc_join) into device
+ * buffers sized from the join's statistics, and next serves the rows, in unspecified order, from windows of at most 2^20
+ * rows.  NULL + dna_glue_errmsg(): an unknown kind, sides of different k (messages of the glue's own), a failed aggregate, a
+ * GPU error.  stats = count(*), sum(a.count), sum(b.count), sum(least(a.count, b.count)) over the result rows. */
+typedef struct CountKmersJoin CountKmersJoin;
+CountKmersJoin *count_kmers_join_begin(CountKmersAgg *left, CountKmersAgg *right, char kind);
+bool count_kmers_join_next(CountKmersJoin *j, Kmer *kmer, int64_t *count_left, int64_t *count_right);
+bool count_kmers_join_failed(const CountKmersJoin *j);
+void count_kmers_join_stats(const CountKmersJoin *j, int64_t *rows, int64_t *sum_left, int64_t *sum_right, int64_t *sum_min);
+void count_kmers_join_end(CountKmersJoin *j);
+
 
 /* ---- SELECT d.id, k.kmer FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS k(kmer) [WHERE <op>]: the ROWS of
  * a table (what test.sql:172-176 inserts into kmer_data_t, and the WHERE forms test.sql:187-262 asks of that column) as one

@@ -35,8 +35,8 @@ extern "C" {
  * bucket groups per owner -- dnagpu_hist_device_keys / _counts are NULL for those), the dnagpu_multi_* options, the
  * table-of-sequences count (dnagpu_count_kmers_batch, dnagpu_dna_set_sequences + dnagpu_count_kmers_table,
  * dnagpu_hist_merge), the rows of a table of sequences with the fused WHERE forms (dnagpu_generate_kmers_table), the index
- * over a stored kmer column (dnagpu_kmer_index_*) and its updates (dnagpu_kmer_index_append / _delete / _next_row):
- * additions only, so the number stays */
+ * over a stored kmer column (dnagpu_kmer_index_*) and its updates (dnagpu_kmer_index_append / _delete / _next_row), the
+ * join of two accumulators (dnagpu_acc_join, dnagpu_acc_partitions): additions only, so the number stays */
 #define DNAGPU_ABI_VERSION 2
 
 /* ---- status codes ------------------------------------------------------------------------
@@ -324,6 +324,50 @@ uint64_t dnagpu_acc_total(const dnagpu_acc *acc);
 int dnagpu_acc_summary(dnagpu_ctx *ctx, const dnagpu_acc *acc, uint64_t *total, uint64_t *unique, uint64_t *checksum);
 int dnagpu_acc_download(dnagpu_ctx *ctx, dnagpu_acc *acc, uint64_t first, uint64_t count, uint64_t *keys, uint64_t *counts);
 void dnagpu_acc_free(dnagpu_ctx *ctx, dnagpu_acc *acc);
+
+/* ---- hash join of two accumulators: what kmer_hash_ops (dna--1.0.sql:204-212) is for besides GROUP BY -- the plans that
+ * pair equal k-mers of two inputs, here over two counted sets that already sit in device memory:
+ *   SELECT a.kmer, a.count, b.count FROM counts_a a JOIN counts_b b ON a.kmer = b.kmer     (Hash Join)      DNAGPU_JOIN_INNER
+ *   SELECT kmer FROM counts_a INTERSECT SELECT kmer FROM counts_b                          (hashed SetOp)   DNAGPU_JOIN_INNER
+ *   SELECT kmer FROM counts_a EXCEPT SELECT kmer FROM counts_b; NOT IN; NOT EXISTS         (hashed SetOp)   DNAGPU_JOIN_ANTI
+ *   ... FROM counts_a a LEFT JOIN counts_b b ON a.kmer = b.kmer                                             DNAGPU_JOIN_LEFT
+ * The join runs on the device and hands out only the result rows and their statistics.
+ * Rows: keys are distinct inside an accumulator, so every kind yields at most one row per group of `left` (SEMI equals
+ *   INNER).  Rows come in unspecified order.  At most `cap` rows go to each of out_keys / out_left / out_right; any of them
+ *   may be NULL; they are host memory, or device memory when out_on_device != 0.  *n_out = ALL result rows, even beyond cap
+ *   (dnagpu_*_select's rule); which cap of them are written is then unspecified.  With cap == 0 or all three arrays NULL
+ *   nothing is stored: the statistics-only call.  stats may be NULL; when given it always covers all result rows, never only
+ *   those within cap.  All sums are exact 64-bit: sum_left <= dnagpu_acc_total(left).
+ * Derived figures: with the two dnagpu_acc_distinct values dL and dR, INNER's rows give Jaccard = rows / (dL + dR - rows) and
+ *   the containment rows / dL; with the two dnagpu_acc_total values, sum_min gives the weighted forms.
+ * Sources: both sides are read only -- the tables, the download order and the summaries stay as they were.  left == right is
+ *   allowed: INNER then returns every group with equal counts, ANTI nothing.  An empty side holds no table: an empty left
+ *   gives 0 rows; an empty right gives INNER 0 rows and ANTI / LEFT every group of left with count_right = 0.  The all-ones
+ *   key and key 0 are keys like any other.
+ * Checks, in order: a kind outside 0 .. 2 is DNAGPU_ERR_BAD_ARG (the range before the missing object, as elsewhere in this
+ *   header); a NULL ctx, left, right or n_out is DNAGPU_ERR_BAD_ARG; accumulators of different k are DNAGPU_ERR_BAD_ARG
+ *   (nothing is written); an allocation failure is DNAGPU_ERR_OOM with nothing leaked.
+ * Waiting: the call waits for its work, as select does: host and device outputs are complete when it returns.
+ * dnagpu_acc_partitions: the partitions of the accumulator's table, a power of two (0 for NULL or an accumulator that holds
+ *   no table yet).  The join picks its path from the two sides' partition counts alone.
+ * Out of scope: a histogram as a side (dnagpu_acc_create plus one dnagpu_acc_add puts it into an accumulator: the same bin
+ *   pass a native form would need); FULL OUTER (LEFT, plus ANTI the other way round); a result that is itself an accumulator;
+ *   more than one GPU. */
+#define DNAGPU_JOIN_INNER 0   /* rows of left that have a partner in right: key, count_left, count_right (JOIN .. ON a.kmer = b.kmer; INTERSECT) */
+#define DNAGPU_JOIN_ANTI  1   /* rows of left that have none: key, count_left, count_right = 0 (EXCEPT; NOT IN; NOT EXISTS)                 */
+#define DNAGPU_JOIN_LEFT  2   /* every row of left: count_right = the partner's count, 0 when there is none (LEFT JOIN)                      */
+typedef struct dnagpu_join_stats {
+    uint64_t rows;            /* result rows of `kind`                                              */
+    uint64_t sum_left;        /* sum of count_left over the result rows                             */
+    uint64_t sum_right;       /* sum of count_right over the result rows                            */
+    uint64_t sum_min;         /* sum of min(count_left, count_right) over the result rows           */
+    uint64_t checksum_left;   /* wrapping sum of the (key, count_left) digest of dnagpu_acc_summary */
+    uint64_t checksum_right;  /* the same over (key, count_right), rows with count_right > 0 only   */
+} dnagpu_join_stats;
+int dnagpu_acc_join(dnagpu_ctx *ctx, const dnagpu_acc *left, const dnagpu_acc *right, int kind,
+                    uint64_t *out_keys, uint64_t *out_left, uint64_t *out_right, uint64_t cap,
+                    uint64_t *n_out, dnagpu_join_stats *stats, int out_on_device);
+uint64_t dnagpu_acc_partitions(const dnagpu_acc *acc);
 
 /* ---- count-ordered queries over counted groups: the reference's first counting statement is not a bare GROUP BY but
  *   SELECT k.kmer, count(*) FROM generate_kmers(...) AS k(kmer) GROUP BY k.kmer ORDER BY count(*) DESC   (test.sql:95)
@@ -680,6 +724,11 @@ uint64_t dnagpu_kmer_index_next_row(const dnagpu_kmer_index *idx);
  * DNAGPU_DEBUG_RANK_SMALL shrinks both limits -- a class limit of 4 counts, a sort chunk of 2048 rows -- so that small inputs
  * take the tail path and several peels (tests). */
 #define DNAGPU_DEBUG_RANK_SMALL 1024u
+/* dnagpu_acc_join picks the partition path or the direct path from the two sides' partition counts.
+ * DNAGPU_DEBUG_JOIN_PARTITION takes the partition path for any sizes, DNAGPU_DEBUG_JOIN_DIRECT the direct path (tests, and
+ * the probe that times both); the first holds when both are set. */
+#define DNAGPU_DEBUG_JOIN_PARTITION 2048u
+#define DNAGPU_DEBUG_JOIN_DIRECT 4096u
 int dnagpu_set_debug(dnagpu_ctx *ctx, unsigned flags);
 
 /* ---- instrumentation ------------------------------------------------------------------------
