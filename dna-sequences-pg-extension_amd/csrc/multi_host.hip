@@ -15,6 +15,7 @@
 #include <thread>
 
 #include "host_common.hpp"
+#include "multi_math.hpp"
 
 using namespace dnagpu;
 
@@ -424,6 +425,58 @@ extern "C" int dnagpu_multi_dna_synth(dnagpu_multi *m, uint64_t seed, uint64_t n
 
 extern "C" uint64_t dnagpu_multi_dna_length(const dnagpu_multi_dna *d) { return d ? d->n_bases : 0; }
 
+// a copy between two ranks, queued on `st` (a stream of dst_rank's device): device-to-device when they share a device, a
+// peer copy otherwise
+static hipError_t rank_copy(const dnagpu_multi *m, int dst_rank, void *to, int src_rank, const void *from, size_t bytes, hipStream_t st)
+{
+    const int dd = m->dev[(size_t)dst_rank], sd = m->dev[(size_t)src_rank];
+    return dd == sd ? hipMemcpyAsync(to, from, bytes, hipMemcpyDeviceToDevice, st) : hipMemcpyPeerAsync(to, dd, from, sd, bytes, st);
+}
+
+// Rank r's rows of [first, first + count) and, where they reach into the next chunk, the neighbour's first word (its chunk
+// is resident since the upload; gather space on this rank), copied on the rank's stream
+static hipError_t rank_rows_with_halo(const dnagpu_multi *m, const dnagpu_multi_dna *d, int r, u64 first, u64 count, RankRows *rows)
+{
+    *rows = rank_rows(d->n_words, d->per, r, first, count);
+    if (!rows->halo)
+        return hipSuccess;
+    return rank_copy(m, r, d->full[(size_t)r] + rows->w_hi, r + 1, d->full[(size_t)r + 1] + rows->w_hi, 8, m->ctx[(size_t)r]->stream);
+}
+
+// Runs job(r) -> its code on every rank, each on its own host thread (MultiPool::run).  The error text is per thread: a
+// failing rank's is kept beside its code, and the first failing rank becomes the call's error, "rank R (what): text"
+// ("rank R: text" without a `what`).  On any failure every rank's histogram is freed.
+static int run_ranks(dnagpu_multi *m, const char *what, const char *threw, dnagpu_hist **hists, const std::function<int(int)> &job)
+{
+    std::vector<int> rcs((size_t)m->n, DNAGPU_OK);
+    std::vector<std::string> errs((size_t)m->n);
+    const std::function<void(int)> work = [&](int r) {
+        rcs[(size_t)r] = job(r);
+        if (rcs[(size_t)r] != DNAGPU_OK)
+            errs[(size_t)r] = dnagpu_last_error();
+    };
+    int rc = m->workers.run(m->n, work);
+    if (rc != DNAGPU_OK)
+        set_err("%s", threw);
+    for (int r = 0; r < m->n && rc == DNAGPU_OK; r++)
+        if (rcs[(size_t)r] != DNAGPU_OK) {
+            if (what)
+                set_err("rank %d (%s): %s", r, what, errs[(size_t)r].c_str());
+            else
+                set_err("rank %d: %s", r, errs[(size_t)r].c_str());
+            rc = rcs[(size_t)r];
+        }
+    if (rc == DNAGPU_OK)
+        return rc;
+    for (int r = 0; r < m->n; r++) {
+        (void)hipSetDevice(m->ctx[(size_t)r]->device);
+        dnagpu_hist_free(m->ctx[(size_t)r], hists[r]);
+        hists[r] = nullptr;
+    }
+    (void)hipSetDevice(m->ctx[0]->device);
+    return rc;
+}
+
 // every rank's buffer receives the other ranks' chunks, ordered on each rank's own stream
 static int multi_gather(dnagpu_multi *m, const dnagpu_multi_dna *d)
 {
@@ -449,10 +502,7 @@ static int multi_gather(dnagpu_multi *m, const dnagpu_multi_dna *d)
             const int src = (dst + q) % m->n;
             u64 *to = d->full[(size_t)dst] + (u64)src * d->per;
             const u64 *from = d->full[(size_t)src] + (u64)src * d->per;
-            if (m->dev[(size_t)src] == m->dev[(size_t)dst])
-                HIP_TRY(hipMemcpyAsync(to, from, per_bytes, hipMemcpyDeviceToDevice, c->stream));
-            else
-                HIP_TRY(hipMemcpyPeerAsync(to, m->dev[(size_t)dst], from, m->dev[(size_t)src], per_bytes, c->stream));
+            HIP_TRY(rank_copy(m, dst, to, src, from, per_bytes, c->stream));
         }
     }
     return DNAGPU_OK;
@@ -507,20 +557,10 @@ static int multi_count_dense(dnagpu_multi *m, const dnagpu_multi_dna *d, int k, 
         if (e == hipSuccess)
             rc = pool_alloc_t(c, n_bins, &table[(size_t)r]);
         if (e == hipSuccess && rc == DNAGPU_OK) {
-            const u64 w_lo = std::min((u64)r * d->per, d->n_words), w_hi = std::min((u64)(r + 1) * d->per, d->n_words);
-            const u64 row_lo = std::max(first, w_lo * 32), row_hi = std::min(first + count, w_hi * 32);
-            if (r + 1 < m->n && w_hi < d->n_words && row_hi > row_lo) {
-                // the neighbour's first word (its chunk is resident since the upload; gather space on this rank)
-                const int src = r + 1;
-                u64 *to = d->full[(size_t)r] + w_hi;
-                const u64 *from = d->full[(size_t)src] + w_hi;
-                e = m->dev[(size_t)src] == m->dev[(size_t)r]
-                        ? hipMemcpyAsync(to, from, 8, hipMemcpyDeviceToDevice, c->stream)
-                        : hipMemcpyPeerAsync(to, m->dev[(size_t)r], from, m->dev[(size_t)src], 8, c->stream);
-            }
+            RankRows rows;
+            e = rank_rows_with_halo(m, d, r, first, count, &rows);
             if (e == hipSuccess)
-                e = launch_dense_table(d->full[(size_t)r], d->n_words, row_lo, row_hi > row_lo ? row_hi - row_lo : 0, bits,
-                                       table[(size_t)r], c->stream);
+                e = launch_dense_table(d->full[(size_t)r], d->n_words, rows.row_lo, rows.n(), bits, table[(size_t)r], c->stream);
         }
         if (e != hipSuccess) {
             set_err("dense multi count (rank %d): %s", r, hipGetErrorString(e));
@@ -551,9 +591,7 @@ static int multi_count_dense(dnagpu_multi *m, const dnagpu_multi_dna *d, int k, 
             if (e == hipSuccess)
                 rc = pool_alloc_t(c0, n_bins, &scratch);
             for (int r = 1; r < m->n && e == hipSuccess && rc == DNAGPU_OK; r++) {
-                e = m->dev[(size_t)r] == m->dev[0]
-                        ? hipMemcpyAsync(scratch, table[(size_t)r], n_bins * 4, hipMemcpyDeviceToDevice, c0->stream)
-                        : hipMemcpyPeerAsync(scratch, m->dev[0], table[(size_t)r], m->dev[(size_t)r], n_bins * 4, c0->stream);
+                e = rank_copy(m, 0, scratch, r, table[(size_t)r], n_bins * 4, c0->stream);
                 if (e == hipSuccess)
                     e = launch_table_add(table[0], scratch, (u32)n_bins, c0->stream);
             }
@@ -591,33 +629,9 @@ extern "C" int dnagpu_count_multi(dnagpu_multi *m, const dnagpu_multi_dna *dna, 
     RC_TRY(multi_gather(m, dna));
     // one host thread per rank: the level loop of a count reads counters back between levels, so the ranks
     // only run concurrently when each is driven by its own thread (device selection is per thread)
-    std::vector<int> rcs((size_t)m->n, DNAGPU_OK);
-    std::vector<std::string> errs((size_t)m->n);
-    const std::function<void(int)> work = [&](int r) {
-        rcs[(size_t)r] = dnagpu_count_kmers_owned(m->ctx[(size_t)r], dna->view[(size_t)r], k, first, count, r, m->n,
-                                                 &hists[r]);
-        if (rcs[(size_t)r] != DNAGPU_OK)
-            errs[(size_t)r] = dnagpu_last_error();                // the error text is per thread
-    };
-    const int wrc = m->workers.run(m->n, work);
-    if (wrc != DNAGPU_OK) {
-        set_err("a rank's count ended in a C++ exception");
-        for (int q = 0; q < m->n; q++) {
-            dnagpu_hist_free(m->ctx[(size_t)q], hists[q]);
-            hists[q] = nullptr;
-        }
-        return wrc;
-    }
-    for (int r = 0; r < m->n; r++)
-        if (rcs[(size_t)r] != DNAGPU_OK) {
-            set_err("rank %d: %s", r, errs[(size_t)r].c_str());
-            for (int q = 0; q < m->n; q++) {
-                dnagpu_hist_free(m->ctx[(size_t)q], hists[q]);
-                hists[q] = nullptr;
-            }
-            return rcs[(size_t)r];
-        }
-    return DNAGPU_OK;
+    return run_ranks(m, nullptr, "a rank's count ended in a C++ exception", hists, [&](int r) {
+        return dnagpu_count_kmers_owned(m->ctx[(size_t)r], dna->view[(size_t)r], k, first, count, r, m->n, &hists[r]);
+    });
     });
 }
 
@@ -695,7 +709,333 @@ struct EventSet {                               // timing events of one owner, d
         return hipSuccess;
     }
 };
+
+// ---- the record exchange as stages: one Exchange per call, one Owner per owner's job, the stages in the order they run
+
+using Clock = std::chrono::steady_clock;
+
+// one dnagpu_count_multi_unordered call
+struct Exchange {
+    dnagpu_multi *m;
+    const dnagpu_multi_dna *dna;
+    int k;
+    u64 first, count;
+    dnagpu_hist **hists;
+    int W, P = 1;                                   // ranks; bucket groups per owner
+    std::vector<dnagpu_records *> recs;             // per rank: the records of its own rows, grouped by coarse bucket
+    std::vector<u64> wgt;                           // per bucket: its records on all ranks
+    std::vector<u32> cuts;                          // exchange_cuts: owner o's group p = buckets [cuts[o * P + p], cuts[o * P + p + 1])
+    SkGeom g{};
+    u32 n_coarse = 0;
+    bool via_rccl = false, rccl_self = false;       // pieces travel through ncclSend / ncclRecv; a rank's own pieces too
+    std::vector<double> t_rec, t_xfer, t_hidden;    // per rank: record pass (host clock); transfer, and its part beside the count (events)
+    std::vector<u64> moved;                         // per owner: bytes received from other ranks
+
+    Exchange(dnagpu_multi *m_, const dnagpu_multi_dna *dna_, int k_, u64 first_, u64 count_, dnagpu_hist **hists_)
+        : m(m_), dna(dna_), k(k_), first(first_), count(count_), hists(hists_), W(m_->n), recs((size_t)W, nullptr),
+          t_rec((size_t)W, 0.0), t_xfer((size_t)W, 0.0), t_hidden((size_t)W, 0.0), moved((size_t)W, 0)
+    {
+    }
+    ~Exchange()                                     // the records are freed on every exit, an exception's included
+    {
+        for (int r = 0; r < W; r++) {
+            (void)hipSetDevice(m->ctx[(size_t)r]->device);
+            dnagpu_records_free(m->ctx[(size_t)r], recs[(size_t)r]);
+        }
+        (void)hipSetDevice(m->ctx[0]->device);
+    }
+    u32 group_lo(int o, int p) const { return cuts[(size_t)o * P + p]; }
+    u32 group_hi(int o, int p) const { return std::max(cuts[(size_t)o * P + p + 1], group_lo(o, p)); }
+    u64 piece_len(int rank, u32 b) const { return recs[(size_t)rank]->off[b + 1] - recs[(size_t)rank]->off[b]; }
+    const char *piece(int rank, u32 b) const { return static_cast<const char *>(recs[(size_t)rank]->recs) + recs[(size_t)rank]->off[b] * 16; }
+};
+
+// One owner's pulls and counts.  The destructor is the error exit: whatever stage returns early, nothing of this owner's
+// buffers is in flight afterwards -- the transfer stream, then the context's stream are waited for before the landing
+// buffers the owner still holds go back to the pool.  (A buffer handed to count_sk_received has left bufs[]; after
+// owner_finish has waited for both streams there is nothing to wait for.)
+struct Owner {
+    const int o;
+    dnagpu_ctx *const c;
+    const hipStream_t xs;                           // the owner's transfer stream; the counting runs on c->stream
+    EventSet evs;
+    hipEvent_t ready = nullptr, x0 = nullptr, x1 = nullptr, c0 = nullptr;
+    std::vector<hipEvent_t> landed;                 // per group: its last piece has arrived
+    std::vector<void *> bufs;                       // per group: the landing buffer (null: the group holds no record)
+    std::vector<GroupLayout> lay;                   // per group: blen[] / boff[] of its landing buffer
+    dnagpu_hist *head = nullptr;                    // hists[o] owns it: freed with the others when a rank fails
+    bool drained = false;                           // both streams have been waited for behind everything this owner queued
+
+    Owner(const Exchange &x, int o_)
+        : o(o_), c(x.m->ctx[(size_t)o_]), xs(x.m->xfer[(size_t)o_]), landed((size_t)x.P, nullptr), bufs((size_t)x.P, nullptr), lay((size_t)x.P)
+    {
+    }
+    ~Owner()
+    {
+        if (!drained) {
+            (void)hipStreamSynchronize(xs);
+            (void)hipStreamSynchronize(c->stream);
+        }
+        for (void *b : bufs)
+            pool_free(c, b);
+    }
+};
 }  // namespace
+
+// a stage's error exit: the text becomes the thread's error (run_ranks reads it there)
+static int fail(int rc, const char *text)
+{
+    set_err("%s", text);
+    return rc;
+}
+static int fail(hipError_t e) { return fail(DNAGPU_ERR_HIP, hipGetErrorString(e)); }
+
+// stage 1, every rank: the records of the rows that start in its own chunk
+static int exchange_records(Exchange &x, int r)
+{
+    const auto t0 = Clock::now();
+    dnagpu_ctx *c = x.m->ctx[(size_t)r];
+    RankRows rows;
+    hipError_t e = hipSetDevice(c->device);
+    if (e == hipSuccess)
+        e = rank_rows_with_halo(x.m, x.dna, r, x.first, x.count, &rows);   // the k-1 <= 31 bases a row reaches into the next chunk
+    if (e != hipSuccess)
+        return fail(e);
+    const int rc = dnagpu_sk_records(c, x.dna->view[(size_t)r], x.k, rows.n() ? rows.row_lo : 0, rows.n(), x.count, &x.recs[(size_t)r]);
+    x.m->rec_phases[(size_t)r] = c->last_times;    // (the owner phase starts a new profiling session on this context)
+    x.t_rec[(size_t)r] = ms_since(t0);
+    return rc;
+}
+
+// stage 2, the caller's thread: who owns which buckets, in which groups, and how the pieces travel
+static void exchange_plan(Exchange &x)
+{
+    dnagpu_multi *m = x.m;
+    x.g = sk_geometry(m->ctx[0], x.count, x.k);
+    x.n_coarse = 1u << x.g.r0bits;
+    x.wgt.assign(dnagpu_records_buckets(x.recs[0]), 0);
+    for (int r = 0; r < x.W; r++)
+        for (u32 b = 0; b < x.wgt.size(); b++)
+            x.wgt[b] += x.piece_len(r, b);
+    x.P = std::max(1, std::min(m->parts, (int)DNAGPU_MULTI_MAX_PARTS));
+    x.cuts = exchange_cuts(x.wgt, x.W, x.P);
+    m->last.parts = x.P;
+    // How the remote pieces travel.  Default: the owner PULLS every piece with a peer copy on its transfer stream.
+    // DNAGPU_MULTI_OPT_EXCHANGE_RCCL: every piece is one ncclSend on its rank's transfer stream and one ncclRecv on its
+    // owner's, a group call per bucket group (round p: a rank sends what the other owners' groups p hold of its records
+    // and receives its own group p; between two ranks the pieces are issued in ascending bucket order on both sides).
+    // Needs every rank driven by its own thread (the ranks' group calls meet each other) and all owners active.
+    x.via_rccl = m->exchange_rccl > 0 && m->rccl && !m->workers.serial && m->probe_owner < 0;
+    x.rccl_self = x.via_rccl && m->exchange_rccl == 2;
+    m->last_exchange = x.via_rccl ? "rccl-sendrecv" : "peer-copy";
+}
+
+// Stage 3: everything of an owner that can fail without work in flight -- its histogram, EVERY event, EVERY group's landing
+// buffer and the too-large check -- before stage 4 queues the first copy.  An owner that returns from here with an error
+// has not touched its transfer stream.
+static int owner_setup(const Exchange &x, Owner &ow)
+{
+    ow.head = hist_new(0, false).release();
+    if (!ow.head)
+        return fail(DNAGPU_ERR_OOM, "host allocation failed");
+    x.hists[ow.o] = ow.head;
+    hipError_t e = ow.evs.make(&ow.x0);
+    if (e == hipSuccess) e = ow.evs.make(&ow.x1);
+    if (e == hipSuccess) e = ow.evs.make(&ow.c0);
+    if (e == hipSuccess) e = ow.evs.make(&ow.ready);
+    for (int p = 0; p < x.P && e == hipSuccess; p++)
+        e = ow.evs.make(&ow.landed[(size_t)p]);
+    if (e != hipSuccess)
+        return fail(e);
+    for (int p = 0; p < x.P; p++) {
+        GroupLayout &l = ow.lay[(size_t)p];
+        l = group_layout(x.wgt, x.group_lo(ow.o, p), x.group_hi(ow.o, p), x.n_coarse);
+        if (l.n_recs > 0xFFFFFFFFull)
+            return fail(DNAGPU_ERR_TOO_LARGE, "too many records for one owner");
+        if (l.n_recs)
+            RC_TRY(pool_alloc(ow.c, (size_t)sk_received_cap(l.blen, x.n_coarse, x.g) * 16, &ow.bufs[(size_t)p]));
+    }
+    return DNAGPU_OK;
+}
+
+// The pieces of the owner's group p in the order they are queued and laid out: bucket ascending; within a bucket the owner's
+// own piece first, then round the ranks, (o + q) % W (spreads the link load); empty pieces skipped.  fn(src, b, n_b, to):
+// n_b records of rank src's bucket b land at `to`; false from fn ends the walk.
+template <typename Fn>
+static void for_each_piece(const Exchange &x, const Owner &ow, int p, Fn &&fn)
+{
+    for (u32 b = x.group_lo(ow.o, p); b < x.group_hi(ow.o, p); b++) {
+        u64 at = ow.lay[(size_t)p].boff[b];
+        for (int q = 0; q < x.W; q++) {
+            const int src = (ow.o + q) % x.W;
+            const u64 n_b = x.piece_len(src, b);
+            if (!n_b)
+                continue;
+            if (!fn(src, b, n_b, static_cast<char *>(ow.bufs[(size_t)p]) + at * 16))
+                return;
+            at += n_b;
+        }
+    }
+}
+
+// stage 4 (copy transport): the owner pulls group p's pieces; in the rehearsal the emulated link's delay follows them
+static int owner_pull_group(Exchange &x, Owner &ow, int p)
+{
+    if (!ow.bufs[(size_t)p])
+        return DNAGPU_OK;
+    hipError_t e = hipSuccess;
+    u64 inbound = 0;
+    for_each_piece(x, ow, p, [&](int src, u32 b, u64 n_b, char *to) {
+        e = rank_copy(x.m, ow.o, to, src, x.piece(src, b), (size_t)n_b * 16, ow.xs);
+        if (src != ow.o)
+            inbound += n_b * 16;
+        return e == hipSuccess;
+    });
+    if (e != hipSuccess)
+        return fail(e);
+    x.moved[(size_t)ow.o] += inbound;
+    if (x.m->emulate_gbs > 0 && inbound) {
+        // rehearsal on one device: the group's inbound bytes at the emulated rate, on the transfer stream
+        const double us = (double)inbound / (x.m->emulate_gbs * 1e3);
+        const unsigned long long ticks = (unsigned long long)std::min(us, 50000.0) * 100ull;
+        hipLaunchKernelGGL(link_delay_kernel, dim3(1), dim3(64), 0, ow.xs, ticks);
+    }
+    return DNAGPU_OK;
+}
+
+// stage 5 (RCCL transport): one group call -- the sends of this rank's records of every owner's group p, then the
+// receives of its own group p
+static int owner_rccl_group(Exchange &x, Owner &ow, int p)
+{
+    const RcclApi &api = x.m->api;
+    const ncclComm_t comm = x.m->comms[(size_t)ow.o];
+    ncclResult_t nr = api.GroupStart();
+    // this rank's records of the other owners' groups p (its own pieces too when asked: one-rank tests)
+    for (int q = 0; q < x.W && nr == ncclSuccess; q++) {
+        const int dst = (ow.o + q) % x.W;
+        if (dst == ow.o && !x.rccl_self)
+            continue;
+        for (u32 b = x.group_lo(dst, p); b < x.group_hi(dst, p) && nr == ncclSuccess; b++)
+            if (const u64 n_b = x.piece_len(ow.o, b))
+                nr = api.Send(x.piece(ow.o, b), (size_t)n_b * 2, ncclUint64, dst, comm, ow.xs);
+    }
+    if (nr == ncclSuccess && ow.bufs[(size_t)p])
+        for_each_piece(x, ow, p, [&](int src, u32 b, u64 n_b, char *to) {
+            if (src == ow.o && !x.rccl_self) {
+                if (hipMemcpyAsync(to, x.piece(src, b), (size_t)n_b * 16, hipMemcpyDeviceToDevice, ow.xs) != hipSuccess)
+                    nr = ncclUnhandledCudaError;
+            } else {
+                nr = api.Recv(to, (size_t)n_b * 2, ncclUint64, src, comm, ow.xs);
+                if (src != ow.o)
+                    x.moved[(size_t)ow.o] += n_b * 16;
+            }
+            return nr == ncclSuccess;
+        });
+    const ncclResult_t ne = api.GroupEnd();
+    if (nr != ncclSuccess || ne != ncclSuccess) {
+        (void)hipGetLastError();
+        return fail(DNAGPU_ERR_HIP, api.GetErrorString(nr != ncclSuccess ? nr : ne));
+    }
+    return DNAGPU_OK;
+}
+
+// stages 4 / 5: all transfers of the owner at once on its transfer stream, group after group, an event behind each group
+static int owner_queue_transfers(Exchange &x, Owner &ow)
+{
+    // The pool orders reuse on the context's stream only (and poisons there when asked to): the transfer stream
+    // starts behind everything queued on it so far -- the owner's own record pass included, whose pieces are read
+    // from this device; the other ranks' passes were synchronised by dnagpu_sk_records.
+    hipError_t e = hipEventRecord(ow.ready, ow.c->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(ow.xs, ow.ready, 0);
+    if (e == hipSuccess) e = hipEventRecord(ow.x0, ow.xs);
+    for (int p = 0; p < x.P && e == hipSuccess; p++) {
+        RC_TRY(x.via_rccl ? owner_rccl_group(x, ow, p) : owner_pull_group(x, ow, p));
+        e = hipEventRecord(ow.landed[(size_t)p], ow.xs);
+    }
+    if (e == hipSuccess) e = hipEventRecord(ow.x1, ow.xs);
+    if (e == hipSuccess) e = hipEventRecord(ow.c0, ow.c->stream);
+    return e == hipSuccess ? DNAGPU_OK : fail(e);
+}
+
+// stage 6: group p is counted on the context's stream behind its event, into a part of the owner's histogram
+static int owner_count_groups(const Exchange &x, Owner &ow)
+{
+    prof_begin(ow.c);
+    for (int p = 0; p < x.P; p++) {
+        if (!ow.bufs[(size_t)p])
+            continue;
+        const hipError_t e = hipStreamWaitEvent(ow.c->stream, ow.landed[(size_t)p], 0);
+        if (e != hipSuccess)
+            return fail(e);
+        HistPtr part = hist_new(0, false);
+        if (!part)
+            return fail(DNAGPU_ERR_OOM, "host allocation failed");
+        void *buf = ow.bufs[(size_t)p];
+        ow.bufs[(size_t)p] = nullptr;               // (count_sk_received takes the buffer over)
+        const GroupLayout &l = ow.lay[(size_t)p];
+        RC_TRY(count_sk_received(ow.c, buf, l.boff, l.blen, x.g, x.k, part.get(), sk_received_cap(l.blen, x.n_coarse, x.g)));
+        ow.head->parts.push_back(part.get());
+        ow.head->n_distinct += part->n_distinct;
+        ow.head->total += part->total;
+        ow.head->extent += part->extent ? part->extent : part->n_distinct;
+        part.release();                             // (the head owns it now)
+    }
+    prof_end(ow.c);
+    return DNAGPU_OK;
+}
+
+// stage 7: both streams drained; the owner's times, and a head of one part becomes a plain histogram
+static int owner_finish(Exchange &x, Owner &ow)
+{
+    hipError_t e = hipStreamSynchronize(ow.xs);
+    if (e == hipSuccess) e = hipStreamSynchronize(ow.c->stream);
+    if (e != hipSuccess)
+        return fail(e);
+    ow.drained = true;
+    float x_ms = 0, c_at = 0, first_ms = 0;
+    (void)hipEventElapsedTime(&x_ms, ow.x0, ow.x1);             // first copy queued -> last piece landed
+    (void)hipEventElapsedTime(&c_at, ow.x0, ow.c0);             // ... -> the owner's stream was free to count
+    (void)hipEventElapsedTime(&first_ms, ow.x0, ow.landed[0]);
+    x.t_xfer[(size_t)ow.o] = x_ms;
+    // the counting starts when the first group has landed; what the transfer stream did after that ran beside it
+    x.t_hidden[(size_t)ow.o] = std::max(0.0f, x_ms - std::max(first_ms, c_at));
+    if (ow.head->parts.size() == 1) {                           // one group: a plain histogram, no head
+        x.hists[ow.o] = ow.head->parts[0];
+        ow.head->parts.clear();
+        dnagpu_hist_free(ow.c, ow.head);                        // (it owns no arrays)
+        ow.head = nullptr;
+    }
+    return DNAGPU_OK;
+}
+
+// stages 3 - 7, every owner on its own thread: its buckets' pieces from all ranks, group by group, counted as they land
+static int exchange_owner(Exchange &x, int o)
+{
+    if (x.m->probe_owner >= 0 && o != x.m->probe_owner) {       // rehearsal probe: this owner's buckets are not counted
+        x.hists[o] = hist_new(0, false).release();
+        return x.hists[o] ? DNAGPU_OK : fail(DNAGPU_ERR_OOM, "host allocation failed");
+    }
+    const hipError_t e = hipSetDevice(x.m->ctx[(size_t)o]->device);
+    if (e != hipSuccess)
+        return fail(e);
+    Owner ow(x, o);
+    RC_TRY(owner_setup(x, ow));
+    RC_TRY(owner_queue_transfers(x, ow));
+    RC_TRY(owner_count_groups(x, ow));
+    return owner_finish(x, ow);
+}
+
+// stage 8: the call's times, from the ranks'
+static void exchange_times(const Exchange &x, Clock::time_point t_own)
+{
+    dnagpu_multi_times &t = x.m->last;
+    t.records_ms = *std::max_element(x.t_rec.begin(), x.t_rec.end());
+    t.exchange_ms = *std::max_element(x.t_xfer.begin(), x.t_xfer.end());
+    t.hidden_ms = x.m->probe_owner >= 0 ? x.t_hidden[(size_t)x.m->probe_owner] : *std::min_element(x.t_hidden.begin(), x.t_hidden.end());
+    t.count_ms = ms_since(t_own);
+    for (u64 b : x.moved)
+        t.bytes_moved += b;
+}
 
 extern "C" int dnagpu_count_multi_unordered(dnagpu_multi *m, const dnagpu_multi_dna *dna, int k, uint64_t first, uint64_t count,
                                             dnagpu_hist **hists)
@@ -709,352 +1049,20 @@ extern "C" int dnagpu_count_multi_unordered(dnagpu_multi *m, const dnagpu_multi_
     RC_TRY(check_range(dna->view[0], k, first, count));
     if (k < sk_min_k() || count == 0)
         return dnagpu_count_multi(m, dna, k, first, count, hists);         // (short k-mers: the ordered paths)
-    const auto t_call = std::chrono::steady_clock::now();
-    const int W = m->n;
-    std::vector<dnagpu_records *> recs((size_t)W, nullptr);
-    std::vector<int> rcs((size_t)W, DNAGPU_OK);
-    std::vector<std::string> errs((size_t)W);
-    std::vector<double> t_rec((size_t)W, 0.0), t_cnt((size_t)W, 0.0), t_xfer((size_t)W, 0.0), t_hidden((size_t)W, 0.0);
-    std::vector<u64> moved((size_t)W, 0);
-    auto fail = [&](int r, int rc, const char *what) {
-        rcs[(size_t)r] = rc;
-        errs[(size_t)r] = what;
-    };
-    // ---- every rank: the records of its own rows
-    const std::function<void(int)> cut = [&](int r) {
-        const auto t0 = std::chrono::steady_clock::now();
-        dnagpu_ctx *c = m->ctx[(size_t)r];
-        const u64 w_lo = std::min((u64)r * dna->per, dna->n_words), w_hi = std::min((u64)(r + 1) * dna->per, dna->n_words);
-        const u64 row_lo = std::max<u64>(first, w_lo * 32), row_hi = std::min<u64>(first + count, w_hi * 32);
-        hipError_t e = hipSetDevice(c->device);
-        if (e == hipSuccess && r + 1 < W && w_hi < dna->n_words && row_hi > row_lo) {
-            const int src = r + 1;                 // the k-1 <= 31 bases a row reaches into the next chunk: one word
-            u64 *to = dna->full[(size_t)r] + w_hi;
-            const u64 *from = dna->full[(size_t)src] + w_hi;
-            e = m->dev[(size_t)src] == m->dev[(size_t)r] ? hipMemcpyAsync(to, from, 8, hipMemcpyDeviceToDevice, c->stream)
-                                                        : hipMemcpyPeerAsync(to, m->dev[(size_t)r], from, m->dev[(size_t)src], 8, c->stream);
+    const auto t_call = Clock::now();
+    int rc;
+    {
+        Exchange x(m, dna, k, first, count, hists);
+        m->rec_phases.assign((size_t)m->n, dnagpu_phase_times{});
+        rc = run_ranks(m, "records", "a rank's record pass ended in a C++ exception", hists, [&](int r) { return exchange_records(x, r); });
+        if (rc == DNAGPU_OK) {
+            exchange_plan(x);
+            const auto t_own = Clock::now();
+            rc = run_ranks(m, "count", "an owner's count ended in a C++ exception", hists, [&](int o) { return exchange_owner(x, o); });
+            exchange_times(x, t_own);
         }
-        if (e != hipSuccess)
-            return fail(r, DNAGPU_ERR_HIP, hipGetErrorString(e));
-        rcs[(size_t)r] = dnagpu_sk_records(c, dna->view[(size_t)r], k, row_hi > row_lo ? row_lo : 0, row_hi > row_lo ? row_hi - row_lo : 0,
-                                           count, &recs[(size_t)r]);
-        if (rcs[(size_t)r] != DNAGPU_OK)
-            errs[(size_t)r] = dnagpu_last_error();
-        m->rec_phases[(size_t)r] = c->last_times;  // (the owner phase below starts a new profiling session on this context)
-        t_rec[(size_t)r] = ms_since(t0);
-    };
-    m->rec_phases.assign((size_t)W, dnagpu_phase_times{});
-    int rc = m->workers.run(W, cut);
-    if (rc != DNAGPU_OK)
-        set_err("a rank's record pass ended in a C++ exception");
-    for (int r = 0; r < W && rc == DNAGPU_OK; r++)
-        if (rcs[(size_t)r] != DNAGPU_OK) {
-            set_err("rank %d (records): %s", r, errs[(size_t)r].c_str());
-            rc = rcs[(size_t)r];
-        }
-    // ---- every owner: its buckets' pieces from all ranks, group by group, counted as they land
-    if (rc == DNAGPU_OK) {
-        const SkGeom g = sk_geometry(m->ctx[0], count, k);
-        const u32 nb = dnagpu_records_buckets(recs[0]);
-        const u32 n_coarse = 1u << g.r0bits;
-        // owners: contiguous bucket ranges balanced by the records the buckets hold on all ranks (shard_math.py:
-        // bucket_owner_ranges_weighted -- a bucket goes to the side its middle falls on)
-        std::vector<u64> wgt(nb, 0);
-        u64 wtotal = 0;
-        for (int r = 0; r < W; r++)
-            for (u32 b = 0; b < nb; b++) {
-                wgt[b] += recs[(size_t)r]->off[b + 1] - recs[(size_t)r]->off[b];
-                wtotal += recs[(size_t)r]->off[b + 1] - recs[(size_t)r]->off[b];
-            }
-        // cuts[j] for j = 0 .. W * P: owner o's group p = buckets [cuts[o * P + p], cuts[o * P + p + 1])
-        const int P = std::max(1, std::min(m->parts, (int)DNAGPU_MULTI_MAX_PARTS));
-        const int WP = W * P;
-        std::vector<u32> cuts((size_t)WP + 1, 0);
-        cuts[(size_t)WP] = nb;
-        if (wtotal == 0) {
-            for (int j = 1; j < WP; j++)
-                cuts[(size_t)j] = (u32)(((u64)j * nb + (u64)WP - 1) / (u64)WP);
-        } else {
-            // owners first (the rule the process-per-GPU path uses), then every owner's range into P groups the same way
-            std::vector<u32> ocut((size_t)W + 1, 0);
-            ocut[(size_t)W] = nb;
-            auto split = [&](u32 lo, u32 hi, int ways, u32 *out /* ways + 1 entries, out[0] = lo, out[ways] = hi */) {
-                u64 tot = 0;
-                for (u32 b = lo; b < hi; b++)
-                    tot += wgt[b];
-                out[0] = lo;
-                out[ways] = hi;
-                u64 run = 0;
-                u32 b = lo;
-                for (int j = 1; j < ways; j++) {
-                    const double target = (double)tot * j / ways;
-                    while (b < hi && (double)run + (double)wgt[b] / 2 <= target) {
-                        run += wgt[b];
-                        b++;
-                    }
-                    out[j] = b;
-                }
-            };
-            split(0, nb, W, ocut.data());
-            // An owner's groups grow geometrically (1 : 3 : 9 ...): the first one lands -- and its counting starts --
-            // after a small share of the transfer, and every later group is still in flight while a group a third of its
-            // size is being counted.
-            for (int o = 0; o < W; o++) {
-                const u32 lo = ocut[(size_t)o], hi = std::max(ocut[(size_t)o + 1], ocut[(size_t)o]);
-                u64 tot = 0;
-                for (u32 b = lo; b < hi; b++)
-                    tot += wgt[b];
-                double wsum = 0, acc = 0, wp = 1;
-                for (int p = 0; p < P; p++, wp *= 3)
-                    wsum += wp;
-                u32 *out = &cuts[(size_t)o * P];
-                out[0] = lo;
-                u64 run = 0;
-                u32 b = lo;
-                wp = 1;
-                for (int p = 1; p < P; p++, wp *= 3) {
-                    acc += wp;
-                    const double target = (double)tot * acc / wsum;
-                    while (b < hi && (double)run + (double)wgt[b] / 2 <= target) {
-                        run += wgt[b];
-                        b++;
-                    }
-                    out[p] = b;
-                }
-                cuts[(size_t)(o + 1) * P] = hi;
-            }
-        }
-        m->last.parts = P;
-        // How the remote pieces travel.  Default: the owner PULLS every piece with a peer copy on its transfer stream.
-        // DNAGPU_MULTI_OPT_EXCHANGE_RCCL: every piece is one ncclSend on its rank's transfer stream and one ncclRecv on its
-        // owner's, a group call per bucket group (round p: a rank sends what the other owners' groups p hold of its records
-        // and receives its own group p; between two ranks the pieces are issued in ascending bucket order on both sides).
-        // Needs every rank driven by its own thread (the ranks' group calls meet each other) and all owners active.
-        const bool via_rccl = m->exchange_rccl > 0 && m->rccl && !m->workers.serial && m->probe_owner < 0;
-        const bool rccl_self = via_rccl && m->exchange_rccl == 2;
-        m->last_exchange = via_rccl ? "rccl-sendrecv" : "peer-copy";
-        const std::function<void(int)> own = [&](int o) {
-            const auto t0 = std::chrono::steady_clock::now();
-            dnagpu_ctx *c = m->ctx[(size_t)o];
-            if (m->probe_owner >= 0 && o != m->probe_owner) {     // rehearsal probe: this owner's buckets are not counted
-                hists[o] = hist_new(0, false).release();
-                if (!hists[o])
-                    fail(o, DNAGPU_ERR_OOM, "host allocation failed");
-                return;
-            }
-            hipStream_t xs = m->xfer[(size_t)o];
-            hipError_t e = hipSetDevice(c->device);
-            if (e != hipSuccess)
-                return fail(o, DNAGPU_ERR_HIP, hipGetErrorString(e));
-            dnagpu_hist *head = hist_new(0, false).release();      // (hists[] owns it: freed with the others when a rank fails)
-            if (!head)
-                return fail(o, DNAGPU_ERR_OOM, "host allocation failed");
-            hists[o] = head;
-            EventSet evs;
-            hipEvent_t x0 = nullptr, x1 = nullptr, c0 = nullptr;
-            std::vector<hipEvent_t> landed((size_t)P, nullptr);
-            std::vector<void *> bufs((size_t)P, nullptr);
-            std::vector<std::vector<u64>> boffs((size_t)P), blens((size_t)P);
-            auto drop = [&](int rc_, const char *what) {          // error exit: nothing of this owner's buffers is in flight afterwards
-                (void)hipStreamSynchronize(xs);
-                (void)hipStreamSynchronize(c->stream);
-                for (void *b : bufs)
-                    pool_free(c, b);
-                fail(o, rc_, what);
-            };
-            hipEvent_t ready = nullptr;
-            e = evs.make(&x0);
-            if (e == hipSuccess) e = evs.make(&x1);
-            if (e == hipSuccess) e = evs.make(&c0);
-            if (e == hipSuccess) e = evs.make(&ready);
-            for (int p = 0; p < P && e == hipSuccess; p++)
-                e = evs.make(&landed[(size_t)p]);
-            if (e != hipSuccess)
-                return drop(DNAGPU_ERR_HIP, hipGetErrorString(e));
-            // ---- every group's landing buffer
-            for (int p = 0; p < P; p++) {
-                const u32 b_lo = cuts[(size_t)o * P + p], b_hi = std::max(cuts[(size_t)o * P + p + 1], b_lo);
-                std::vector<u64> &blen = blens[(size_t)p], &boff = boffs[(size_t)p];
-                blen.assign(n_coarse, 0);
-                boff.assign((size_t)n_coarse + 1, 0);
-                for (u32 b = b_lo; b < b_hi; b++)
-                    blen[b] = wgt[b];
-                for (u32 d = 0; d < n_coarse; d++)
-                    boff[d + 1] = boff[d] + blen[d];
-                const u64 n_recs = boff[n_coarse];
-                if (n_recs > 0xFFFFFFFFull)
-                    return drop(DNAGPU_ERR_TOO_LARGE, "too many records for one owner");
-                if (n_recs) {
-                    const int arc = pool_alloc(c, (size_t)sk_received_cap(blen, n_coarse, g) * 16, &bufs[(size_t)p]);
-                    if (arc != DNAGPU_OK)
-                        return drop(arc, dnagpu_last_error());
-                }
-            }
-            // The pool orders reuse on the context's stream only (and poisons there when asked to): the transfer stream
-            // starts behind everything queued on it so far -- the owner's own record pass included, whose pieces are read
-            // from this device; the other ranks' passes were synchronised by dnagpu_sk_records.
-            e = hipEventRecord(ready, c->stream);
-            if (e == hipSuccess) e = hipStreamWaitEvent(xs, ready, 0);
-            if (e == hipSuccess) e = hipEventRecord(x0, xs);
-            if (e != hipSuccess)
-                return drop(DNAGPU_ERR_HIP, hipGetErrorString(e));
-            // ---- all copies, group after group, an event behind each group
-            for (int p = 0; p < P; p++) {
-                const u32 b_lo = cuts[(size_t)o * P + p], b_hi = std::max(cuts[(size_t)o * P + p + 1], b_lo);
-                const std::vector<u64> &boff = boffs[(size_t)p];
-                if (via_rccl) {
-                    ncclResult_t nr = m->api.GroupStart();
-                    // this rank's records of the other owners' groups p (its own pieces too when asked: one-rank tests)
-                    const dnagpu_records *mine = recs[(size_t)o];
-                    for (int q = 0; q < W && nr == ncclSuccess; q++) {
-                        const int dst = (o + q) % W;
-                        if (dst == o && !rccl_self)
-                            continue;
-                        const u32 d_lo = cuts[(size_t)dst * P + p], d_hi = std::max(cuts[(size_t)dst * P + p + 1], d_lo);
-                        for (u32 b = d_lo; b < d_hi && nr == ncclSuccess; b++) {
-                            const u64 n_b = mine->off[b + 1] - mine->off[b];
-                            if (n_b)
-                                nr = m->api.Send(static_cast<const char *>(mine->recs) + mine->off[b] * 16, (size_t)n_b * 2, ncclUint64,
-                                                 dst, m->comms[(size_t)o], xs);
-                        }
-                    }
-                    for (u32 b = b_lo; b < b_hi && nr == ncclSuccess && bufs[(size_t)p]; b++) {
-                        u64 at = boff[b];
-                        for (int q = 0; q < W && nr == ncclSuccess; q++) {
-                            const int src = (o + q) % W;
-                            const dnagpu_records *rr = recs[(size_t)src];
-                            const u64 n_b = rr->off[b + 1] - rr->off[b];
-                            if (!n_b)
-                                continue;
-                            char *to = static_cast<char *>(bufs[(size_t)p]) + at * 16;
-                            if (src == o && !rccl_self) {
-                                if (hipMemcpyAsync(to, static_cast<const char *>(rr->recs) + rr->off[b] * 16, (size_t)n_b * 16,
-                                                   hipMemcpyDeviceToDevice, xs) != hipSuccess)
-                                    nr = ncclUnhandledCudaError;
-                            } else {
-                                nr = m->api.Recv(to, (size_t)n_b * 2, ncclUint64, src, m->comms[(size_t)o], xs);
-                                if (src != o)
-                                    moved[(size_t)o] += n_b * 16;
-                            }
-                            at += n_b;
-                        }
-                    }
-                    const ncclResult_t ne = m->api.GroupEnd();
-                    if (nr != ncclSuccess || ne != ncclSuccess) {
-                        (void)hipGetLastError();
-                        return drop(DNAGPU_ERR_HIP, m->api.GetErrorString(nr != ncclSuccess ? nr : ne));
-                    }
-                } else if (bufs[(size_t)p]) {
-                    u64 delay_bytes = 0;
-                    for (u32 b = b_lo; b < b_hi; b++) {
-                        u64 at = boff[b];
-                        for (int q = 0; q < W; q++) {
-                            const int src = (o + q) % W;             // own pieces first, then round the ranks: spreads the link load
-                            const dnagpu_records *rr = recs[(size_t)src];
-                            const u64 n_b = rr->off[b + 1] - rr->off[b];
-                            if (!n_b)
-                                continue;
-                            char *to = static_cast<char *>(bufs[(size_t)p]) + at * 16;
-                            const char *from = static_cast<const char *>(rr->recs) + rr->off[b] * 16;
-                            if (m->dev[(size_t)src] == m->dev[(size_t)o])
-                                e = hipMemcpyAsync(to, from, (size_t)n_b * 16, hipMemcpyDeviceToDevice, xs);
-                            else
-                                e = hipMemcpyPeerAsync(to, m->dev[(size_t)o], from, m->dev[(size_t)src], (size_t)n_b * 16, xs);
-                            if (e != hipSuccess)
-                                return drop(DNAGPU_ERR_HIP, hipGetErrorString(e));
-                            if (src != o) {
-                                moved[(size_t)o] += n_b * 16;
-                                delay_bytes += n_b * 16;
-                            }
-                            at += n_b;
-                        }
-                    }
-                    if (m->emulate_gbs > 0 && delay_bytes) {
-                        // rehearsal on one device: the group's inbound bytes at the emulated rate, on the transfer stream
-                        const double us = (double)delay_bytes / (m->emulate_gbs * 1e3);
-                        const unsigned long long ticks = (unsigned long long)std::min(us, 50000.0) * 100ull;
-                        hipLaunchKernelGGL(link_delay_kernel, dim3(1), dim3(64), 0, xs, ticks);
-                    }
-                }
-                e = hipEventRecord(landed[(size_t)p], xs);
-                if (e != hipSuccess)
-                    return drop(DNAGPU_ERR_HIP, hipGetErrorString(e));
-            }
-            e = hipEventRecord(x1, xs);
-            if (e == hipSuccess) e = hipEventRecord(c0, c->stream);
-            if (e != hipSuccess)
-                return drop(DNAGPU_ERR_HIP, hipGetErrorString(e));
-            // ---- count group p behind its event
-            prof_begin(c);
-            for (int p = 0; p < P; p++) {
-                if (!bufs[(size_t)p])
-                    continue;
-                e = hipStreamWaitEvent(c->stream, landed[(size_t)p], 0);
-                if (e != hipSuccess)
-                    return drop(DNAGPU_ERR_HIP, hipGetErrorString(e));
-                HistPtr part = hist_new(0, false);
-                if (!part)
-                    return drop(DNAGPU_ERR_OOM, "host allocation failed");
-                void *buf = bufs[(size_t)p];
-                bufs[(size_t)p] = nullptr;                        // (count_sk_received takes the buffer over)
-                const int crc = count_sk_received(c, buf, boffs[(size_t)p], blens[(size_t)p], g, k, part.get(),
-                                                  sk_received_cap(blens[(size_t)p], n_coarse, g));
-                if (crc != DNAGPU_OK)
-                    return drop(crc, dnagpu_last_error());
-                head->parts.push_back(part.get());
-                head->n_distinct += part->n_distinct;
-                head->total += part->total;
-                head->extent += part->extent ? part->extent : part->n_distinct;
-                part.release();                                   // (the head owns it now)
-            }
-            prof_end(c);
-            e = hipStreamSynchronize(xs);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            if (e != hipSuccess)
-                return drop(DNAGPU_ERR_HIP, hipGetErrorString(e));
-            float x_ms = 0, c_at = 0;
-            (void)hipEventElapsedTime(&x_ms, x0, x1);             // first copy queued -> last piece landed
-            (void)hipEventElapsedTime(&c_at, x0, c0);             // ... -> the owner's stream was free to count
-            t_xfer[(size_t)o] = x_ms;
-            // the counting starts when the first group has landed; what the transfer stream did after that ran beside it
-            float first_ms = 0;
-            (void)hipEventElapsedTime(&first_ms, x0, landed[0]);
-            t_hidden[(size_t)o] = std::max(0.0f, x_ms - std::max(first_ms, c_at));
-            if (head->parts.size() == 1) {                        // one group: a plain histogram, no head
-                dnagpu_hist *only = head->parts[0];
-                head->parts.clear();
-                dnagpu_hist_free(c, head);                        // (it owns no arrays)
-                hists[o] = only;
-            }
-            t_cnt[(size_t)o] = ms_since(t0);
-        };
-        const auto t_own = std::chrono::steady_clock::now();
-        rc = m->workers.run(W, own);
-        if (rc != DNAGPU_OK)
-            set_err("an owner's count ended in a C++ exception");
-        for (int r = 0; r < W && rc == DNAGPU_OK; r++)
-            if (rcs[(size_t)r] != DNAGPU_OK) {
-                set_err("rank %d (count): %s", r, errs[(size_t)r].c_str());
-                rc = rcs[(size_t)r];
-            }
-        m->last.records_ms = *std::max_element(t_rec.begin(), t_rec.end());
-        m->last.exchange_ms = *std::max_element(t_xfer.begin(), t_xfer.end());
-        m->last.hidden_ms = m->probe_owner >= 0 ? t_hidden[(size_t)m->probe_owner] : *std::min_element(t_hidden.begin(), t_hidden.end());
-        m->last.count_ms = ms_since(t_own);
-        for (int r = 0; r < W; r++)
-            m->last.bytes_moved += moved[(size_t)r];
-    }
-    for (int r = 0; r < W; r++) {
-        (void)hipSetDevice(m->ctx[(size_t)r]->device);
-        dnagpu_records_free(m->ctx[(size_t)r], recs[(size_t)r]);
-        if (rc != DNAGPU_OK) {
-            dnagpu_hist_free(m->ctx[(size_t)r], hists[r]);
-            hists[r] = nullptr;
-        }
-    }
-    (void)hipSetDevice(m->ctx[0]->device);
+    }       // (the records are freed here; the histograms were freed by run_ranks if a rank failed)
     m->last.total_ms = ms_since(t_call);
     return rc;
     });
 }
-

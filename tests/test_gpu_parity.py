@@ -1954,6 +1954,47 @@ def _count_multi_unordered_case(pkg, n_ranks, parts, devices, where, via_rccl, n
             m.dna_free(d)
 
 
+def test_count_multi_unordered_small_edges(pkg):
+    """The record exchange's edges that the 3 Mbase inputs never reach: 8 ranks x 8 groups over 200 and 2000 bases.  At 200
+    bases the sequence is 7 words, so the last rank holds no rows; most groups of most owners hold no record (no landing
+    buffer, nothing to count); a window inside one rank's chunk leaves every other rank without rows.  Nothing travels for
+    that window: so few rows have ONE coarse bucket, the weighted rule gives a lone bucket to owner 3 of 8 (half the weight
+    is first reached by the target 4 / 8), and the window lies in rank 3's chunk."""
+    n_ranks, parts, seed = 8, 8, 0xD2A0004
+    with pkg.Multi([0] * n_ranks, pkg.MULTI_COPY) as m:
+        m.set_parts(parts)
+        for n in (200, 2_000):
+            words = orc.synth_words(seed, n)
+            per_bases = -(-((n + 31) // 32) // n_ranks) * 32          # bases per rank chunk
+            lo = 3 * per_bases + per_bases // 8                       # a window inside rank 3's chunk
+            d = m.upload(words, n)
+            for k in (31, 21):
+                for first, count in ((0, None), (lo, per_bases // 2)):
+                    assert count is None or 3 * per_bases <= first and first + count <= min(4 * per_bases, n - k + 1)
+                    what = f"multi unordered small: n={n} k={k} rows [{first}, {'end' if count is None else first + count})"
+                    ok, oc = orc.count_keys(orc.generate_kmers(words, n, k, faithful=False)[first:None if count is None else first + count])
+                    hs = m.count_unordered(d, k, first, count)
+                    lt = m.last_times()
+                    print(what, "parts", lt["parts"], "bytes_moved", lt["bytes_moved"], "n_parts", [h.n_parts for h in hs])
+                    gk = np.concatenate([h.download()[0] for h in hs])
+                    gc = np.concatenate([h.download()[1] for h in hs])
+                    assert sum(h.total for h in hs) == int(oc.sum()), what
+                    order = np.argsort(gk, kind="stable")
+                    assert_same(gk[order], ok, what + " keys")
+                    assert_same(gc[order], oc, what + " counts")
+                    t = [0, 0, 0, 0]
+                    for h in hs:
+                        t = [(a + b) & ((1 << 64) - 1) for a, b in zip(t, h.summary())]
+                    assert tuple(t) == orc.hist_summary(ok, oc), what
+                    assert lt["parts"] == parts, what
+                    assert m.exchange_transport == "peer-copy", what
+                    if count is not None:
+                        assert lt["bytes_moved"] == 0, what
+                    for h in hs:
+                        h.free()
+            m.dna_free(d)
+
+
 def test_bench_gpus2_one_process_rehearsal():
     """`python bench.py --gpus 2` started the way the driver starts it (a plain command, no torchrun): on a one-GPU box
     the two ranks share device 0 (copy transport, "rehearsal": true); the line keeps the contract's fields."""

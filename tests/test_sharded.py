@@ -3,6 +3,8 @@ and checks the host logic; GPU: the product engine, all ranks on the box's one G
 import importlib
 import json
 import os
+import random
+import shutil
 import subprocess
 import sys
 
@@ -98,6 +100,144 @@ def test_bucket_owner_ranges_weighted():
                 share = [sum(weights[lo:hi]) for lo, hi in r]
                 assert max(share) <= tot / w + max(weights), (nb, w, share)     # within one bucket of the even share
     assert sh.bucket_owner_ranges_weighted([0] * 10, 3) == sh.bucket_owner_ranges(10, 3)
+
+
+# ------------------------------------------------------------------ multi_math.hpp (the one-process path's arithmetic) on the host
+
+def build_plan_check(tmp_path, name, extra):
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    exe = str(tmp_path / name)
+    subprocess.check_call([hipcc, "-O1", "-std=c++17", "--offload-arch=gfx950", *extra, "-I",
+                           os.path.join(ROOT, "dna-sequences-pg-extension_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "host", "multi_plan_check.cpp"), "-o", exe])
+    return exe
+
+
+SANITIZERS = ["-g", "-Xarch_host", "-fsanitize=address,undefined"]
+
+
+@pytest.fixture(scope="module", params=[[], SANITIZERS], ids=["plain", "sanitizers"])
+def plan_check(request, tmp_path_factory):
+    """tests/host/multi_plan_check.cpp as a stand-alone host program; the second build has AddressSanitizer and
+    UndefinedBehaviorSanitizer on its host code.  -> run(mode_args, text_in) -> the lines it printed"""
+    exe = build_plan_check(tmp_path_factory.mktemp("multi_plan"), "multi_plan_check", request.param)
+
+    def run(args, text_in):
+        r = subprocess.run([exe, *args], input=text_in, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0 and not r.stderr, r.stderr[-2000:]
+        return r.stdout.splitlines()
+    return run
+
+
+PLAN_KINDS = ("uniform", "sparse", "ones", "spike", "wide")
+
+
+def plan_weights(kind, nb, rnd):
+    """weights below 2^40 (1024 of them sum below 2^50): every number the two rules compare is exact in a double"""
+    if kind == "uniform":
+        w = [rnd.randint(1, 1000) for _ in range(nb)]
+    elif kind == "sparse":
+        w = [rnd.randint(1, 1000) if rnd.random() < 0.1 else 0 for _ in range(nb)]
+        w[rnd.randrange(nb)] = rnd.randint(1, 1000)             # never all zero
+    elif kind == "ones":
+        w = [1] * nb
+    elif kind == "spike":
+        w = [1] * nb
+        w[rnd.randrange(nb)] = 1000 * nb
+    else:
+        w = [rnd.randrange(1 << 40) for _ in range(nb)]
+    return w
+
+
+def plan_sweep():
+    """(W, P, weights): the five kinds at every W, P and bucket count, then nothing to weigh at every W, P and bucket count"""
+    rnd = random.Random(0x6D706C616E)
+    cases = [(W, P, plan_weights(kind, nb, rnd)) for W in (1, 2, 3, 8) for P in (1, 2, 3, 8) for nb in (1, 2, 5, 17, 136, 1024)
+             for kind in PLAN_KINDS]
+    assert all(sum(w) > 0 for _, _, w in cases)
+    return cases + [(W, P, [0] * nb) for W in (1, 2, 3, 8) for P in (1, 2, 3, 8) for nb in (1, 2, 5, 17, 136, 1024)]
+
+
+def test_exchange_plan_matches_shard_math(plan_check):
+    """exchange_cuts of multi_math.hpp (what dnagpu_count_multi_unordered plans its record exchange with) against
+    shard_math.py (what the process-per-GPU path plans with): bucket_owner_ranges_weighted, then bucket_group_cuts on every
+    owner's range -- one rule, cut for cut.  With nothing to weigh: the even W * P split.  And the landing layout of every
+    group: its record total, boff[] the exclusive prefix of blen[], blen[] the weights of its buckets and 0 elsewhere."""
+    pkg = load_package()
+    sh = importlib.import_module(pkg.__name__ + ".shard_math")
+    cases = plan_sweep()
+    out = plan_check([], "".join(f"{W} {P} {len(w)} {' '.join(map(str, w))}\n" for W, P, w in cases))
+    assert len(out) == 3 * len(cases)
+    for i, (W, P, w) in enumerate(cases):
+        nb, what = len(w), f"W={W} P={P} nb={len(w)} case {i}"
+        tag, *cuts = out[3 * i].split()
+        cuts = [int(c) for c in cuts]
+        assert tag == "cuts" and len(cuts) == W * P + 1, what
+        if sum(w):
+            want = []
+            owners = sh.bucket_owner_ranges_weighted(w, W)
+            for o, (lo, hi) in enumerate(owners):
+                g = sh.bucket_group_cuts(w, lo, hi, P)
+                assert len(g) == P + 1 and g[0] == lo and g[-1] == hi == (owners[o + 1][0] if o + 1 < W else nb), what
+                want += g[:-1]
+            want.append(nb)
+        else:
+            want = [-(-j * nb // (W * P)) for j in range(W * P)] + [nb]
+        assert cuts == want, what
+        assert cuts[0] == 0 and cuts[-1] == nb and all(a <= b for a, b in zip(cuts, cuts[1:])), what
+        tag, *groups = out[3 * i + 1].split()
+        groups = [tuple(int(v) for v in g.split(":")) for g in groups]
+        assert tag == "groups" and len(groups) == W * P, what
+        assert groups == [(sum(w[a:b]),) * 2 for a, b in zip(cuts, cuts[1:])], what
+        assert sum(g[0] for g in groups) == sum(w), what
+        tag, *layout, rest = out[3 * i + 2].split()
+        assert tag == "layout" and rest == "rest=0" and len(layout) == nb, what
+        want_layout = [f"{w[b]}:{sum(w[a:b])}" for a, e in zip(cuts, cuts[1:]) for b in range(a, e)]
+        assert layout == want_layout, what
+
+
+def test_rank_rows_tile_the_window(plan_check):
+    """rank_rows of multi_math.hpp (the rows a rank sweeps in dnagpu_count_multi's table path and in the record exchange)
+    against word_chunks: the ranks' rows tile the window exactly once, a rank's rows are the window's rows that start in its
+    chunk, and the neighbour's first word is needed exactly when a rank with rows has a chunk that ends before the sequence"""
+    pkg = load_package()
+    sh = importlib.import_module(pkg.__name__ + ".shard_math")
+    cases = []
+    for n in (1, 31, 32, 33, 200, 100_001):
+        for W in (1, 2, 3, 8):
+            per, chunks = sh.word_chunks(n, W)
+            for k in (21, 31):
+                rows = max(n - k + 1, 0)
+                windows = {(0, rows), (rows // 3, rows // 3), (min(1, rows), max(rows - 2, 0)), (rows, 0)}
+                for r in range(W):                          # inside one rank's chunk; up to its last row; across its end
+                    lo = chunks[r][0] * 32
+                    for first, count in ((lo + 3, 10), (lo + 3, per * 32 - 3), (lo + per * 16, per * 32)):
+                        if first + count <= rows:
+                            windows.add((first, count))
+                cases += [(n, W, per, chunks, first, count) for first, count in sorted(windows)]
+    out = plan_check(["rows"], "".join(f"{(n + 31) // 32} {per} {W} {first} {count}\n" for n, W, per, _, first, count in cases))
+    assert len(out) == len(cases)
+    some_halo = some_empty = False
+    for line, (n, W, per, chunks, first, count) in zip(out, cases):
+        what = f"n={n} W={W} rows [{first}, {first + count})"
+        got = [tuple(int(v) for v in f.split(":")) for f in line.split()]
+        assert len(got) == W, what
+        pos = first
+        for (w_hi, row_lo, row_hi, halo), (w_lo, nbases) in zip(got, chunks):
+            chunk_end = w_lo * 32 + nbases                  # first base behind the chunk
+            assert w_hi == (chunk_end + 31) // 32, what
+            if row_hi > row_lo:
+                assert row_lo == pos == max(first, w_lo * 32) and row_hi == min(first + count, w_hi * 32), what
+                pos = row_hi
+            else:
+                assert min(first + count, w_hi * 32) <= max(first, w_lo * 32), what     # no row of the window starts here
+                some_empty = True
+            assert halo == (1 if row_hi > row_lo and chunk_end < n else 0), what
+            some_halo |= bool(halo)
+        assert pos == first + count, what
+    assert some_halo and some_empty
 
 
 @pytest.mark.parametrize("world,n_bases,k,parts", [(2, 200_000, 31, 3), (3, 100_001, 25, 3), (2, 5000, 23, 2), (3, 100_001, 25, 1),
