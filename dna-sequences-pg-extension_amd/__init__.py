@@ -37,6 +37,8 @@ from .binding import (  # noqa: F401
     KmerIndex,
     Records,
     SPECTRUM_MAX_BINS,
+    STRAND_CANONICAL,
+    STRAND_REVCOMP,
     TOP_MAX,
     MULTI_AUTO,
     MULTI_COPY,

@@ -36,6 +36,8 @@ DEBUG_JOIN_DIRECT = 4096              # dnagpu_acc_join: the direct path for any
 JOIN_INNER = 0                        # JOIN .. ON a.kmer = b.kmer; INTERSECT
 JOIN_ANTI = 1                         # EXCEPT; NOT IN; NOT EXISTS
 JOIN_LEFT = 2                         # LEFT JOIN
+STRAND_REVCOMP = 0                    # dnagpu_kmer_strand: out = rc(key)
+STRAND_CANONICAL = 1                  # ... out = whichever of key and rc(key) comes first under A < T < C < G
 SPECTRUM_MAX_BINS = 1 << 20
 TOP_MAX = 1 << 20
 ORDER_COUNT_DESC = 0                  # ORDER BY count(*) DESC (test.sql:95)
@@ -120,6 +122,7 @@ def lib():
     L.dnagpu_dna_download.argtypes = [vp, vp, u64p]
     L.dnagpu_dna_pack.argtypes = [vp, C.c_char_p, C.c_uint64, C.c_int, C.POINTER(vp), u64p, C.c_char_p]
     L.dnagpu_dna_unpack.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_int]
+    L.dnagpu_dna_revcomp.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(vp)]
     L.dnagpu_kmers_to_text.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, C.c_int]
     L.dnagpu_dna_wire_size.argtypes = [C.c_uint64]
     L.dnagpu_dna_wire_size.restype = C.c_uint64
@@ -177,6 +180,7 @@ def lib():
     L.dnagpu_hist_free.restype = None
     L.dnagpu_acc_create.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.dnagpu_acc_add.argtypes = [vp, vp, vp]
+    L.dnagpu_acc_add_canonical.argtypes = [vp, vp, vp]
     L.dnagpu_acc_distinct.argtypes = [vp]
     L.dnagpu_acc_distinct.restype = C.c_uint64
     L.dnagpu_acc_total.argtypes = [vp]
@@ -210,6 +214,7 @@ def lib():
     L.dnagpu_buffer_download.argtypes = [vp, vp, C.c_uint64, vp]
     L.dnagpu_buffer_upload.argtypes = [vp, vp, vp, C.c_uint64]
     L.dnagpu_kmer_hash.argtypes = [vp, vp, C.c_uint64, vp, C.c_int]
+    L.dnagpu_kmer_strand.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, vp, vp, C.c_int]
     L.dnagpu_kmer_match.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(_FilterC), vp, C.c_int]
     L.dnagpu_kmer_index_build.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(vp)]
     for f in ("rows", "distinct", "next_row"):
@@ -667,8 +672,11 @@ class Accumulator(_CountQueries):
         self.ctx, self.h = ctx, C.c_void_p()
         _chk(lib().dnagpu_acc_create(ctx.h, k, C.byref(self.h)))
 
-    def add(self, hist):
-        _chk(lib().dnagpu_acc_add(self.ctx.h, self.h, hist.h))
+    def add(self, hist, canonical=False):
+        """adds the groups of hist; canonical=True: under the canonical form of every key (dnagpu_acc_add_canonical), so
+        that a k-mer and its reverse complement are one group"""
+        fn = lib().dnagpu_acc_add_canonical if canonical else lib().dnagpu_acc_add
+        _chk(fn(self.ctx.h, self.h, hist.h))
 
     @property
     def distinct(self):
@@ -830,6 +838,14 @@ class Context:
     def unpack_device(self, dna, first, count, dev_text):
         """bases [first, first+count) as `count` characters into device memory (any byte alignment)"""
         _chk(lib().dnagpu_dna_unpack(self.h, dna.h, first, count, dev_text, 1))
+
+    def dna_revcomp(self, dna, first=0, count=None):
+        """bases [first, first+count) of dna reverse-complemented -> a new Dna"""
+        if count is None:
+            count = dna.n_bases - first
+        h = C.c_void_p()
+        _chk(lib().dnagpu_dna_revcomp(self.h, dna.h, first, count, C.byref(h)))
+        return Dna(self, h)
 
     def from_wire_device(self, dev_wire, wire_bytes):
         """dna_recv from a wire image in device memory (8-byte aligned) -> Dna"""
@@ -1050,6 +1066,19 @@ class Context:
     def kmer_hash_device(self, dev_keys, n, dev_out):
         """n keys in device memory -> n uint32 hashes in device memory"""
         _chk(lib().dnagpu_kmer_hash(self.h, dev_keys, n, dev_out, 1))
+
+    def kmer_strand(self, keys, k, mode=STRAND_CANONICAL, want_flipped=True):
+        """rc (STRAND_REVCOMP) or the canonical form (STRAND_CANONICAL) of every key -> (out uint64[], flipped bool[] or None)"""
+        a = np.ascontiguousarray(keys, dtype=np.uint64)
+        out = np.empty(max(a.size, 1), dtype=np.uint64)
+        fl = np.empty(max(a.size, 1), dtype=np.uint8) if want_flipped else None
+        _chk(lib().dnagpu_kmer_strand(self.h, a.ctypes.data, a.size, k, mode, out.ctypes.data,
+                                      fl.ctypes.data if want_flipped else None, 0))
+        return out[:a.size], (fl[:a.size].astype(bool) if want_flipped else None)
+
+    def kmer_strand_device(self, dev_keys, n, k, mode, dev_out, dev_flipped=None):
+        """n keys in device memory -> n keys in device memory (dev_out may be dev_keys), n uint8 flags if dev_flipped"""
+        _chk(lib().dnagpu_kmer_strand(self.h, dev_keys, n, k, mode, dev_out, dev_flipped, 1))
 
     def kmer_match_device(self, dev_keys, n, k, flt, dev_flags):
         """n keys in device memory -> n uint8 flags in device memory"""

@@ -11,9 +11,15 @@
 // into LDS, adds the bin there and writes the partition back whole.  Keys inside one histogram are distinct, so two
 // groups of one bin never meet: phase A adds to the keys already present (read-only probes of slots occupied at load),
 // phase B claims empty slots for the rest by LDS compare-and-swap on the count.  No per-group global atomics in the merge.
+//
+// The canonical add folds a histogram strand-neutrally: the bin stores the canonical form of every key, so
+// x and rc(x) of one histogram arrive as the SAME key and the sentence above no longer holds.  What still holds: the
+// arrivals that were not flipped are distinct among themselves, and so are the flipped ones (bit 63 of the bin's count
+// word tells them apart).  The CANON instantiation of the merge therefore runs phase B class by class; see there.
 #include <hip/hip_runtime.h>
 
 #include "acc_device.hpp"
+#include "strand_math.hpp"
 
 namespace dnagpu {
 
@@ -22,6 +28,7 @@ namespace {
 // (acc_home, ld_slot / st_slot and load_region: acc_device.hpp -- the join's partition path loads a partition the same way)
 constexpr int MERGE_NT = ACC_NT;                           // threads of a partition's workgroup
 constexpr int PER_T = ACC_PER_T;                           // slots (and at most bin entries) per thread: 8
+constexpr u64 FLIPPED = (u64)1 << 63;                      // canonical bins: the entry's key is rc of the histogram's key
 
 __device__ __forceinline__ void store_region(const u64 *lds, u64 *__restrict__ region)
 {
@@ -62,9 +69,12 @@ __device__ __forceinline__ u32 block_sum_u32(u32 v, u32 *wtmp)
 
 }  // namespace
 
-// one thread per histogram slot: padding (count 0) skipped, everything else to its partition's bin
-__global__ __launch_bounds__(256) void acc_bin_kernel(const u64 *__restrict__ keys, const u32 *__restrict__ counts, u64 n,
-                                                      int pbits, u32 *__restrict__ cursor, u64 *__restrict__ bins, u32 bin_cap)
+// one thread per histogram slot: padding (count 0) skipped, everything else to its partition's bin.  CANON: the canonical
+// form of the key (k bases) goes to the partition of that form; a flipped key is marked in the count word (counts arrive
+// as 32 bits, so bit 63 is free)
+template <bool CANON>
+__device__ __forceinline__ void acc_bin(const u64 *__restrict__ keys, const u32 *__restrict__ counts, u64 n, int pbits,
+                                        u32 *__restrict__ cursor, u64 *__restrict__ bins, u32 bin_cap, int k)
 {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n)
@@ -72,11 +82,27 @@ __global__ __launch_bounds__(256) void acc_bin_kernel(const u64 *__restrict__ ke
     const u32 c = counts[i];
     if (c == 0)
         return;
-    const u64 key = keys[i];
+    u64 key = keys[i], word = c;
+    if constexpr (CANON) {
+        bool flipped;
+        key = kmer_canonical(key, k, &flipped);
+        word |= flipped ? FLIPPED : 0;
+    }
     const u64 p = splitmix64(key) >> (64 - pbits);
     const u32 at = atomicAdd(&cursor[p], 1u);
     if (at < bin_cap)
-        st_slot(bins + 2 * (p * bin_cap + at), key, c);
+        st_slot(bins + 2 * (p * bin_cap + at), key, word);
+}
+__global__ __launch_bounds__(256) void acc_bin_kernel(const u64 *__restrict__ keys, const u32 *__restrict__ counts, u64 n,
+                                                      int pbits, u32 *__restrict__ cursor, u64 *__restrict__ bins, u32 bin_cap)
+{
+    acc_bin<false>(keys, counts, n, pbits, cursor, bins, bin_cap, 0);
+}
+__global__ __launch_bounds__(256) void acc_bin_canonical_kernel(const u64 *__restrict__ keys, const u32 *__restrict__ counts,
+                                                                u64 n, int pbits, u32 *__restrict__ cursor,
+                                                                u64 *__restrict__ bins, u32 bin_cap, int k)
+{
+    acc_bin<true>(keys, counts, n, pbits, cursor, bins, bin_cap, k);
 }
 
 // stats[0] = max over partitions of occ + arrivals, stats[1] = max arrivals
@@ -108,6 +134,21 @@ __global__ __launch_bounds__(256) void acc_bin_stats_kernel(const u32 *__restric
 // One workgroup per partition with arrivals.  commit == 0: a dry run that only counts the arrivals whose key is new
 // (stats: [0] max of occ + new as u32, [2..3] the sum of new as u64).  commit == 1: the merge itself; occ[p] grows by
 // the new keys, stats[2..3] receives their sum, stats[1] is set if a partition ran full (never, under the host's bound).
+//
+// CANON (a bin of acc_bin_canonical_kernel): a key may arrive twice, unflipped and flipped.  Phase A is unchanged -- two
+// arrivals for one resident key are two atomic adds.  Phase B runs class by class, each step closed by a barrier:
+//   B1   the pending unflipped arrivals claim slots (distinct among themselves and from the resident keys);
+//   B2a  every pending flipped arrival probes again, read-only as phase A: if B1 brought its key in, it adds and is done;
+//   B2b  the flipped arrivals still pending claim slots (distinct among themselves and, now, from everything present).
+// B2a and B2b are two steps because a claim publishes the slot's count before its key: a probe that ran beside the claims
+// could compare against a key not yet written, and the key a fresh slot holds, 0, is a canonical key (T x k folds into it).
+// Only the keys that are really new are counted: the unflipped pending and the flipped ones still pending after B2a.  The
+// dry run needs that same number, so it performs B1 and B2a in LDS and skips only B2b, the store back and occ.
+// One exception: a dry run can meet occ + the new unflipped keys > ACC_SLOTS (occ <= ACC_BOUND, arrivals <= ACC_SLOTS).  B1 then
+// fills LDS, the claims that find no slot give up after ACC_SLOTS probes, and a flipped arrival whose partner found none
+// counts as new.  The number is then too high, never too low, and it belongs to a partition whose occ + new is past the
+// bound anyway: the host grows the table, from a bound that is still an upper one.
+template <bool CANON>
 __global__ __launch_bounds__(MERGE_NT) void acc_merge_kernel(u64 *__restrict__ table, u32 *__restrict__ occ,
                                                              const u32 *__restrict__ cursor, const u64 *__restrict__ bins,
                                                              u32 bin_cap, int commit, u32 *__restrict__ stats)
@@ -125,7 +166,7 @@ __global__ __launch_bounds__(MERGE_NT) void acc_merge_kernel(u64 *__restrict__ t
     const u64 *bin = bins + 2 * p * bin_cap;
     // phase A: keys already present (slots occupied at load never change key, so the probes need no ordering)
     u64 key[PER_T], cnt[PER_T];
-    u32 pending = 0;
+    u32 pending = 0, flipped = 0;
 #pragma unroll
     for (int j = 0; j < PER_T; j++) {
         const u32 e = (u32)j * MERGE_NT + threadIdx.x;
@@ -134,6 +175,10 @@ __global__ __launch_bounds__(MERGE_NT) void acc_merge_kernel(u64 *__restrict__ t
         if (e >= n_arr)
             continue;
         ld_slot(bin + 2 * (u64)e, key[j], cnt[j]);
+        if constexpr (CANON) {
+            flipped |= cnt[j] & FLIPPED ? 1u << j : 0u;
+            cnt[j] &= ~FLIPPED;
+        }
         u32 s = acc_home(splitmix64(key[j]));
         bool found = false;
         for (int probe = 0; probe < ACC_SLOTS; probe++) {
@@ -150,7 +195,36 @@ __global__ __launch_bounds__(MERGE_NT) void acc_merge_kernel(u64 *__restrict__ t
         if (!found)
             pending |= 1u << j;
     }
-    const u32 n_new = block_sum_u32((u32)__builtin_popcount(pending), wtmp);
+    u32 n_mine = 0;                                // new keys of this thread that already hold a slot (CANON: B1's)
+    bool full = false;
+    if constexpr (CANON) {
+        __syncthreads();                           // (phase A's probes are over before a claim changes a slot)
+        const u32 first_class = pending & ~flipped;
+#pragma unroll
+        for (int j = 0; j < PER_T; j++)            // B1
+            if (first_class & (1u << j))
+                full |= !lds_claim(lds, key[j], cnt[j], acc_home(splitmix64(key[j])));
+        n_mine = (u32)__builtin_popcount(first_class);
+        pending &= flipped;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < PER_T; j++) {          // B2a
+            if (!(pending & (1u << j)))
+                continue;
+            u32 s = acc_home(splitmix64(key[j]));
+            for (int probe = 0; probe < ACC_SLOTS; probe++) {
+                if (lds[2 * s + 1] == 0)
+                    break;
+                if (lds[2 * s] == key[j]) {
+                    atomicAdd(reinterpret_cast<unsigned long long *>(&lds[2 * s + 1]), (unsigned long long)cnt[j]);
+                    pending &= ~(1u << j);
+                    break;
+                }
+                s = (s + 1) & (ACC_SLOTS - 1);
+            }
+        }
+    }
+    const u32 n_new = block_sum_u32(n_mine + (u32)__builtin_popcount(pending), wtmp);
     if (!commit) {
         if (threadIdx.x == 0) {
             atomicMax(&stats[0], o + n_new);
@@ -159,8 +233,7 @@ __global__ __launch_bounds__(MERGE_NT) void acc_merge_kernel(u64 *__restrict__ t
         }
         return;
     }
-    // phase B: new keys claim empty slots
-    bool full = false;
+    // phase B (CANON: B2b): new keys claim empty slots
 #pragma unroll
     for (int j = 0; j < PER_T; j++)
         if (pending & (1u << j))
@@ -290,13 +363,16 @@ __global__ __launch_bounds__(MERGE_NT) void acc_gather_kernel(const u64 *__restr
     }
 }
 
-hipError_t launch_acc_bin(const u64 *keys, const u32 *counts, u64 n, int pbits, u32 *cursor, u64 *bins, u32 bin_cap,
+hipError_t launch_acc_bin(const u64 *keys, const u32 *counts, u64 n, int pbits, u32 *cursor, u64 *bins, u32 bin_cap, int canon_k,
                           hipStream_t s)
 {
     if (n == 0)
         return hipSuccess;
-    hipLaunchKernelGGL(acc_bin_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, keys, counts, n, pbits, cursor, bins,
-                       bin_cap);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (canon_k)
+        hipLaunchKernelGGL(acc_bin_canonical_kernel, grid, dim3(256), 0, s, keys, counts, n, pbits, cursor, bins, bin_cap, canon_k);
+    else
+        hipLaunchKernelGGL(acc_bin_kernel, grid, dim3(256), 0, s, keys, counts, n, pbits, cursor, bins, bin_cap);
     return hipGetLastError();
 }
 
@@ -307,10 +383,15 @@ hipError_t launch_acc_bin_stats(const u32 *occ, const u32 *cursor, u64 P, u32 *s
     return hipGetLastError();
 }
 
-hipError_t launch_acc_merge(u64 *table, u32 *occ, u64 P, const u32 *cursor, const u64 *bins, u32 bin_cap, int commit, u32 *stats,
-                            hipStream_t s)
+hipError_t launch_acc_merge(u64 *table, u32 *occ, u64 P, const u32 *cursor, const u64 *bins, u32 bin_cap, int commit, int canonical,
+                            u32 *stats, hipStream_t s)
 {
-    hipLaunchKernelGGL(acc_merge_kernel, dim3((unsigned)P), dim3(MERGE_NT), 0, s, table, occ, cursor, bins, bin_cap, commit, stats);
+    if (canonical)
+        hipLaunchKernelGGL(acc_merge_kernel<true>, dim3((unsigned)P), dim3(MERGE_NT), 0, s, table, occ, cursor, bins, bin_cap, commit,
+                           stats);
+    else
+        hipLaunchKernelGGL(acc_merge_kernel<false>, dim3((unsigned)P), dim3(MERGE_NT), 0, s, table, occ, cursor, bins, bin_cap, commit,
+                           stats);
     return hipGetLastError();
 }
 

@@ -646,6 +646,32 @@ extern "C" int dnagpu_dna_unpack(dnagpu_ctx *ctx, const dnagpu_dna *dna, uint64_
     });
 }
 
+// bases [first, first+count) reverse-complemented as a new dna (strand_kernels.hip)
+extern "C" int dnagpu_dna_revcomp(dnagpu_ctx *ctx, const dnagpu_dna *dna, uint64_t first, uint64_t count, dnagpu_dna **out)
+{
+    return guarded([&]() -> int {
+    if (!ctx || !dna || !out)
+        return DNAGPU_ERR_BAD_ARG;
+    if (first > dna->n_bases || count > dna->n_bases - first)
+        return DNAGPU_ERR_BAD_ARG;
+    if (count == 0)
+        return DNAGPU_ERR_DNA_EMPTY;               // (the type has no empty value: dna.c:160-161)
+    HIP_TRY(hipSetDevice(ctx->device));
+    PoolScope ps(ctx);
+    const u64 nw = words_for(count);
+    u64 *words = nullptr;
+    RC_TRY(ps.alloc((size_t)nw, &words));
+    HIP_TRY(launch_dna_revcomp(dna->words, first, count, words, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    dnagpu_dna *h = new (std::nothrow) dnagpu_dna{words, nw, count, true};
+    if (!h)
+        return DNAGPU_ERR_OOM;
+    ps.release(words);
+    *out = h;
+    return DNAGPU_OK;
+    });
+}
+
 extern "C" uint64_t dnagpu_dna_wire_size(uint64_t n_bases) { return 8 + 8 * words_for(n_bases); }
 
 extern "C" int dnagpu_dna_from_wire(dnagpu_ctx *ctx, const void *wire, uint64_t wire_bytes, int wire_on_device,
@@ -866,6 +892,42 @@ extern "C" int dnagpu_kmer_hash(dnagpu_ctx *ctx, const uint64_t *keys, uint64_t 
     HIP_TRY(hipMemcpyAsync(dk, keys, n * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(launch_hash_batch(dk, n, dh, ctx->stream));
     HIP_TRY(hipMemcpyAsync(out, dh, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DNAGPU_OK;
+    });
+}
+
+extern "C" int dnagpu_kmer_strand(dnagpu_ctx *ctx, const uint64_t *keys, uint64_t n, int k, int mode, uint64_t *out,
+                                  uint8_t *flipped, int on_device)
+{
+    return guarded([&]() -> int {
+    if (mode != DNAGPU_STRAND_REVCOMP && mode != DNAGPU_STRAND_CANONICAL)
+        return DNAGPU_ERR_BAD_ARG;
+    if (k < 1 || k > 32)
+        return DNAGPU_ERR_INVALID_K;
+    if (!ctx || (n && (!keys || !out)))
+        return DNAGPU_ERR_BAD_ARG;
+    if (n == 0)
+        return DNAGPU_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int canonical = mode == DNAGPU_STRAND_CANONICAL;
+    if (on_device) {
+        HIP_TRY(launch_kmer_strand(keys, n, k, canonical, out, flipped, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return DNAGPU_OK;
+    }
+    PoolScope ps(ctx);
+    u64 *dk = nullptr;
+    uint8_t *df = nullptr;
+    RC_TRY(ps.alloc((size_t)n, &dk));
+    if (flipped)
+        RC_TRY(ps.alloc((size_t)n, &df));
+    HIP_TRY(hipMemcpyAsync(dk, keys, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(launch_kmer_strand(dk, n, k, canonical, dk, df, ctx->stream));      // (in place on the staging copy)
+    HIP_TRY(hipStreamSynchronize(ctx->stream));    // (out may be keys: the upload has read them before the download writes)
+    HIP_TRY(hipMemcpyAsync(out, dk, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (flipped)
+        HIP_TRY(hipMemcpyAsync(flipped, df, n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return DNAGPU_OK;
     });
@@ -1153,7 +1215,9 @@ extern "C" int dnagpu_acc_create(dnagpu_ctx *ctx, int k, dnagpu_acc **out)
 extern "C" uint64_t dnagpu_acc_distinct(const dnagpu_acc *acc) { return acc ? acc->distinct : 0; }
 extern "C" uint64_t dnagpu_acc_total(const dnagpu_acc *acc) { return acc ? acc->total : 0; }
 
-extern "C" int dnagpu_acc_add(dnagpu_ctx *ctx, dnagpu_acc *acc, const dnagpu_hist *h)
+// canonical != 0: every key is folded into its canonical form on the way into the bins; the bins, the
+// growth and the take-over are the same
+static int acc_add(dnagpu_ctx *ctx, dnagpu_acc *acc, const dnagpu_hist *h, int canonical)
 {
     return guarded([&]() -> int {
     if (!ctx || !acc || !h)
@@ -1210,7 +1274,8 @@ extern "C" int dnagpu_acc_add(dnagpu_ctx *ctx, dnagpu_acc *acc, const dnagpu_his
         HIP_TRY(hipMemsetAsync(stats, 0, 16, st));
         for (size_t i = 0; i < n_parts; i++) {
             const dnagpu_hist *q = parts[i];
-            HIP_TRY(launch_acc_bin(q->keys, q->counts, q->extent ? q->extent : q->n_distinct, cur.pbits, cursor, bins, (u32)cap, st));
+            HIP_TRY(launch_acc_bin(q->keys, q->counts, q->extent ? q->extent : q->n_distinct, cur.pbits, cursor, bins, (u32)cap,
+                                   canonical ? acc->k : 0, st));
         }
         HIP_TRY(launch_acc_bin_stats(cur.occ, cursor, P, stats, st));
         u32 m[4] = {0, 0, 0, 0};
@@ -1225,7 +1290,7 @@ extern "C" int dnagpu_acc_add(dnagpu_ctx *ctx, dnagpu_acc *acc, const dnagpu_his
         }
         if (!commit && m[1] <= cap) {              // dry run: how many arrivals are new keys (the rest only add counts)
             HIP_TRY(hipMemsetAsync(stats, 0, 16, st));
-            HIP_TRY(launch_acc_merge(cur.table, cur.occ, P, cursor, bins, (u32)cap, 0, stats, st));
+            HIP_TRY(launch_acc_merge(cur.table, cur.occ, P, cursor, bins, (u32)cap, 0, canonical, stats, st));
             RC_TRY(read_back(ctx, m, stats, 16));
             commit = m[0] <= ACC_BOUND;
             grow_for = acc->distinct + ((u64)m[2] | (u64)m[3] << 32);
@@ -1261,7 +1326,7 @@ extern "C" int dnagpu_acc_add(dnagpu_ctx *ctx, dnagpu_acc *acc, const dnagpu_his
             continue;
         }
         HIP_TRY(hipMemsetAsync(stats, 0, 16, st));
-        HIP_TRY(launch_acc_merge(cur.table, cur.occ, P, cursor, bins, (u32)cap, 1, stats, st));
+        HIP_TRY(launch_acc_merge(cur.table, cur.occ, P, cursor, bins, (u32)cap, 1, canonical, stats, st));
         RC_TRY(read_back(ctx, m, stats, 16));
         if (m[1]) {
             set_err("accumulator merge: a partition ran full");
@@ -1281,6 +1346,9 @@ extern "C" int dnagpu_acc_add(dnagpu_ctx *ctx, dnagpu_acc *acc, const dnagpu_his
     return DNAGPU_OK;
     });
 }
+
+extern "C" int dnagpu_acc_add(dnagpu_ctx *ctx, dnagpu_acc *acc, const dnagpu_hist *h) { return acc_add(ctx, acc, h, 0); }
+extern "C" int dnagpu_acc_add_canonical(dnagpu_ctx *ctx, dnagpu_acc *acc, const dnagpu_hist *h) { return acc_add(ctx, acc, h, 1); }
 
 extern "C" int dnagpu_acc_summary(dnagpu_ctx *ctx, const dnagpu_acc *acc, uint64_t *total, uint64_t *unique, uint64_t *checksum)
 {

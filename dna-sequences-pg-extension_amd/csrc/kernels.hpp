@@ -51,6 +51,14 @@ hipError_t launch_kmers_to_text(const u64 *keys, u64 n, int k, unsigned char *te
 // dst[i] = bswap64(src[i]); the last word is ANDed with last_mask (wire <-> packed words)
 hipError_t launch_wire_swap(const u64 *src, u64 *dst, u64 n_words, u64 last_mask, hipStream_t s);
 
+// ---------------------------------------------------------------- strand_kernels.hip
+// out[0 .. ceil(count / 32)) = bases [first, first + count) of words, reverse-complemented; bits behind the last base zero;
+// no word outside [first / 32, ceil((first + count) / 32)) is read
+hipError_t launch_dna_revcomp(const u64 *words, u64 first, u64 count, u64 *out, hipStream_t s);
+// out[i] = rc(keys[i]) (canonical == 0) or the canonical form of keys[i], bits above 2k dropped; flipped (may be null):
+// flipped[i] = out[i] != the masked key.  out == keys allowed.
+hipError_t launch_kmer_strand(const u64 *keys, u64 n, int k, int canonical, u64 *out, uint8_t *flipped, hipStream_t s);
+
 // exclusive scan of n u32 values (in != out allowed, in == out allowed); *total receives the sum.
 // tmp must hold scan_tmp_words(n) u32 values.
 u64 scan_tmp_words(u64 n);
@@ -186,12 +194,16 @@ hipError_t launch_merge_compact(const u64 *tkeys, const u32 *tcnt, u64 t_slots, 
 // u64), commit = 1 adds the bins in LDS and writes the partitions back (stats[2..3] = new keys; stats[1] != 0: a partition
 // ran full).  split: the table of 2^old_bits partitions into one of 2^new_bits.  gather: groups [first, first + count) of
 // the partition-order view (pre[p] = groups before partition p) of partitions p_lo .. p_lo + n_parts - 1.
+// The canonical add: canon_k != 0 makes bin store the canonical form of every key (strand_math.hpp, k =
+// canon_k), in the partition of that form, with bit 63 of the entry's count word set when the key was flipped; merge with
+// canonical != 0 takes such bins -- a key may then arrive twice, once from either strand -- and counts a pair that is new
+// as ONE new key, in the dry run too.
 constexpr int ACC_SLOTS = 4096;
-hipError_t launch_acc_bin(const u64 *keys, const u32 *counts, u64 n, int pbits, u32 *cursor, u64 *bins, u32 bin_cap,
+hipError_t launch_acc_bin(const u64 *keys, const u32 *counts, u64 n, int pbits, u32 *cursor, u64 *bins, u32 bin_cap, int canon_k,
                           hipStream_t s);
 hipError_t launch_acc_bin_stats(const u32 *occ, const u32 *cursor, u64 P, u32 *stats, hipStream_t s);
-hipError_t launch_acc_merge(u64 *table, u32 *occ, u64 P, const u32 *cursor, const u64 *bins, u32 bin_cap, int commit, u32 *stats,
-                            hipStream_t s);
+hipError_t launch_acc_merge(u64 *table, u32 *occ, u64 P, const u32 *cursor, const u64 *bins, u32 bin_cap, int commit, int canonical,
+                            u32 *stats, hipStream_t s);
 hipError_t launch_acc_split(const u64 *old_table, const u32 *old_occ, int old_bits, u64 *new_table, u32 *new_occ, int new_bits,
                             u32 *stats, hipStream_t s);
 // res3[0] += sum(count), res3[1] += #(count == 1), res3[2] += sum(pair_mix(key, count)); zero it first

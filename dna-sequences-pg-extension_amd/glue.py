@@ -77,6 +77,14 @@ def lib():
         L.dna_glue_set_gpus.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_int]
         L.count_kmers_agg_begin.restype = vp
         L.count_kmers_agg_begin.argtypes = [C.c_int]
+        L.count_kmers_agg_begin_canonical.restype = vp
+        L.count_kmers_agg_begin_canonical.argtypes = [C.c_int]
+        L.reverse_complement.restype = vp
+        L.reverse_complement.argtypes = [vp]
+        L.kmer_reverse_complement.restype = None
+        L.kmer_reverse_complement.argtypes = [C.POINTER(_Kmer)] * 2
+        L.kmer_canonical.restype = None
+        L.kmer_canonical.argtypes = [C.POINTER(_Kmer)] * 2
         L.count_kmers_agg_add.restype = C.c_bool
         L.count_kmers_agg_add.argtypes = [vp, vp]
         L.count_kmers_agg_next.restype = C.c_bool
@@ -238,6 +246,25 @@ def kmer_hash(k):
     return int(lib().kmer_hash(C.byref(k.c)))
 
 
+def reverse_complement(x):
+    """reverse_complement(dna) -> dna, reverse_complement(kmer) -> kmer"""
+    if isinstance(x, dna):
+        p = lib().reverse_complement(x.p)
+        if not p:
+            raise _err()
+        return dna(p=p)
+    out = _Kmer()
+    lib().kmer_reverse_complement(C.byref(x.c), C.byref(out))
+    return kmer(c=out)
+
+
+def canonical(k):
+    """canonical(kmer): whichever of k and its reverse complement comes first as text under A < T < C < G"""
+    out = _Kmer()
+    lib().kmer_canonical(C.byref(k.c), C.byref(out))
+    return kmer(c=out)
+
+
 def starts_with(k, prefix):                        # k ^@ prefix
     r = lib().starts_with(C.byref(k.c), C.byref(prefix.c))
     if r < 0:
@@ -347,11 +374,16 @@ def count_kmers_agg_ordered(rows, k, descending=True):
     return count_kmers_agg(rows, k, _order=descending)
 
 
-def count_kmers_agg(rows, k, _top=None, _order=None):
+def count_kmers_agg_canonical(rows, k):
+    """count_kmers_agg with a kmer and its reverse complement as one group (count_kmers_agg_begin_canonical)"""
+    return count_kmers_agg(rows, k, _canonical=True)
+
+
+def count_kmers_agg(rows, k, _top=None, _order=None, _canonical=False):
     """SELECT k.kmer, count(*) FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS k(kmer) GROUP BY k.kmer
     (test.sql:140-150) through the aggregate: rows = the table's `dna` values (or their text)
     -> ([(kmer, count)...], (total, distinct, unique))"""
-    a = lib().count_kmers_agg_begin(k)
+    a = (lib().count_kmers_agg_begin_canonical if _canonical else lib().count_kmers_agg_begin)(k)
     if not a:
         raise _err()
     try:
@@ -380,8 +412,8 @@ class count_kmers_table_agg:
     """one count_kmers_agg aggregate kept open (count_kmers_agg_begin .. _end): rows added with add(), the groups read
     with groups(), two of them paired with count_kmers_join()"""
 
-    def __init__(self, k, rows=()):
-        self.a = lib().count_kmers_agg_begin(k)
+    def __init__(self, k, rows=(), canonical=False):
+        self.a = (lib().count_kmers_agg_begin_canonical if canonical else lib().count_kmers_agg_begin)(k)
         if not self.a:
             raise _err()
         self.keep = []

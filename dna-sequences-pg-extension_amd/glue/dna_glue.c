@@ -297,6 +297,57 @@ bool kmer_eq(const Kmer *a, const Kmer *b)                                /* kme
 
 bool kmer_ne(const Kmer *a, const Kmer *b) { return !kmer_eq(a, b); }
 
+/* ---- strand forms of ONE value (host loops, like every per-datum operator here; bulk: dnagpu_dna_revcomp, dnagpu_kmer_strand).
+ * The complement of a base is code ^ 1 (A=00 <-> T=01, C=10 <-> G=11). */
+Dna *reverse_complement(const Dna *dna)
+{
+    uint64_t n_words = (dna->length + 31) / 32;
+    Dna *out = (Dna *)calloc(1, sizeof(Dna));
+    uint64_t *w = (uint64_t *)calloc(n_words ? n_words : 1, sizeof(uint64_t));
+    if (!out || !w) {
+        free(out);
+        free(w);
+        ereport_error("out of memory");
+        return NULL;
+    }
+    for (uint64_t j = 0; j < dna->length; j++) {
+        uint64_t i = dna->length - 1 - j;
+        uint64_t code = ((dna->bit_sequence[i / 32] >> ((i * 2) % 64)) & 3) ^ 1;
+        w[j / 32] |= code << ((j * 2) % 64);
+    }
+    out->length = dna->length;
+    out->bit_sequence = w;
+    return out;
+}
+
+void kmer_reverse_complement(const Kmer *kmer, Kmer *out)
+{
+    uint64_t bits = 0;
+    for (int i = 0; i < kmer->length; i++)
+        bits |= (((kmer->bit_sequence >> (2 * (kmer->length - 1 - i))) & 3) ^ 1) << (2 * i);
+    out->length = kmer->length;
+    out->bit_sequence = bits;
+}
+
+/* whichever of kmer and its reverse complement comes first as text under A < T < C < G (the codes' own order, base 0 first:
+ * the order of the kmer index) */
+void kmer_canonical(const Kmer *kmer, Kmer *out)
+{
+    Kmer rc;
+    kmer_reverse_complement(kmer, &rc);
+    uint64_t own = kmer->length >= 32 ? kmer->bit_sequence : kmer->bit_sequence & (((uint64_t)1 << (2 * kmer->length)) - 1);
+    bool take_rc = false;
+    for (int i = 0; i < kmer->length; i++) {
+        uint64_t a = (own >> (2 * i)) & 3, b = (rc.bit_sequence >> (2 * i)) & 3;
+        if (a != b) {
+            take_rc = b < a;
+            break;
+        }
+    }
+    out->length = kmer->length;
+    out->bit_sequence = take_rc ? rc.bit_sequence : own;
+}
+
 /* dna.c:722-735: hash_any over the 8 bytes of bit_sequence (PostgreSQL hash_bytes, lookup3). */
 int32_t kmer_hash(const Kmer *kmer)
 {
@@ -724,6 +775,7 @@ void dna_glue_set_agg_flush_bases(uint64_t n) { g_agg_flush_bases = n ? n : 1; }
 
 struct CountKmersAgg {
     int k;
+    bool canonical;                              /* count_kmers_agg_begin_canonical: the flush is dnagpu_acc_add_canonical */
     dnagpu_acc *acc;                             /* created on the first flush (the GPU context is lazy) */
     uint64_t *words, n_bases, cap_words;         /* the batch: rows back to back as one packed stream */
     uint64_t *starts, n_seqs, cap_seqs;          /* starts[0 .. n_seqs] */
@@ -749,6 +801,14 @@ CountKmersAgg *count_kmers_agg_begin(int k)
         return NULL;
     }
     a->k = k;
+    return a;
+}
+
+CountKmersAgg *count_kmers_agg_begin_canonical(int k)
+{
+    CountKmersAgg *a = count_kmers_agg_begin(k);
+    if (a)
+        a->canonical = true;
     return a;
 }
 
@@ -798,7 +858,7 @@ static bool agg_flush(CountKmersAgg *a)
         ok = ctx() != NULL && (a->acc || gpu_ok(dnagpu_acc_create(g_ctx, a->k, &a->acc))) &&
              gpu_ok(dnagpu_dna_upload(g_ctx, a->words, a->n_bases, &d)) &&
              gpu_ok(dnagpu_count_kmers_batch(g_ctx, d, a->starts, a->n_seqs, a->k, &h)) &&
-             gpu_ok(dnagpu_acc_add(g_ctx, a->acc, h));
+             gpu_ok(a->canonical ? dnagpu_acc_add_canonical(g_ctx, a->acc, h) : dnagpu_acc_add(g_ctx, a->acc, h));
         if (h)
             dnagpu_hist_free(g_ctx, h);
         if (d)

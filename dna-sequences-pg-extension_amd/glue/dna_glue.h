@@ -79,6 +79,14 @@ int32_t kmer_hash(const Kmer *kmer);                                /* dna.c:722
 int starts_with(const Kmer *kmer, const Kmer *prefix);              /* dna.c:842-866  `^@`: 1/0, -1 = ERROR */
 int contains(const Qkmer *pattern, const Kmer *kmer);               /* dna.c:1091-1135 `@>`: 1/0, -1 = ERROR */
 
+/* ---- strand forms of one value (no counterpart in the reference): reverse_complement(dna) (malloc'd like
+ * dna_in's; NULL + dna_glue_errmsg() when out of memory), reverse_complement(kmer), canonical(kmer) = whichever of the kmer and
+ * its reverse complement comes first as text under A < T < C < G, the order of the kmer index (NOT A < C < G < T).  Host loops
+ * over one value; the bulk forms are dnagpu_dna_revcomp and dnagpu_kmer_strand.  out may be the input. */
+Dna *reverse_complement(const Dna *dna);
+void kmer_reverse_complement(const Kmer *kmer, Kmer *out);
+void kmer_canonical(const Kmer *kmer, Kmer *out);
+
 /* ---- generate_kmers(dna, k) RETURNS SETOF kmer (dna.c:743-837) ----
  * begin = the SRF_IS_FIRSTCALL block (validates k, dna.c:771-773); next = one SRF_RETURN_NEXT
  * (false = SRF_RETURN_DONE).  Rows are produced on the GPU in windows and served from a host
@@ -128,6 +136,10 @@ bool count_kmers_spectrum(const CountKmers *c, int64_t *bins, int n_bins);
  * valid once next has been called.  No limit on the table's size: 2^32 - 1 bases apply per batch only. */
 typedef struct CountKmersAgg CountKmersAgg;
 CountKmersAgg *count_kmers_agg_begin(int k);
+/* the strand-neutral aggregate, count_kmers_canonical: a kmer and its reverse complement are one group, served under its
+ * canonical form (above) -- every flush is dnagpu_acc_add_canonical.  Everything else (add, next, totals, _top, _order,
+ * count_kmers_join_*) is the aggregate's as it is. */
+CountKmersAgg *count_kmers_agg_begin_canonical(int k);
 bool count_kmers_agg_add(CountKmersAgg *a, const Dna *row);
 bool count_kmers_agg_next(CountKmersAgg *a, Kmer *kmer, int64_t *count);
 bool count_kmers_agg_failed(const CountKmersAgg *a);

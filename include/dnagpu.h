@@ -36,7 +36,8 @@ extern "C" {
  * table-of-sequences count (dnagpu_count_kmers_batch, dnagpu_dna_set_sequences + dnagpu_count_kmers_table,
  * dnagpu_hist_merge), the rows of a table of sequences with the fused WHERE forms (dnagpu_generate_kmers_table), the index
  * over a stored kmer column (dnagpu_kmer_index_*) and its updates (dnagpu_kmer_index_append / _delete / _next_row), the
- * join of two accumulators (dnagpu_acc_join, dnagpu_acc_partitions): additions only, so the number stays */
+ * join of two accumulators (dnagpu_acc_join, dnagpu_acc_partitions), the strand-neutral forms (dnagpu_dna_revcomp,
+ * dnagpu_kmer_strand, dnagpu_acc_add_canonical): additions only, so the number stays */
 #define DNAGPU_ABI_VERSION 2
 
 /* ---- status codes ------------------------------------------------------------------------
@@ -114,6 +115,13 @@ int dnagpu_dna_pack(dnagpu_ctx *ctx, const char *text, uint64_t n_bases, int tex
 /* decode_dna (dna.c:135-152): bases [first, first+count) as `count` characters (no NUL). */
 int dnagpu_dna_unpack(dnagpu_ctx *ctx, const dnagpu_dna *dna, uint64_t first, uint64_t count,
                       char *out_text, int out_on_device);
+/* bases [first, first+count) of dna, reverse-complemented, as a new device-resident dna (a sequence set is not carried):
+ * base j of the result is the complement (A <-> T, C <-> G: code ^ 1) of base first + count - 1 - j.  The window follows
+ * dnagpu_dna_unpack's range rule: one that leaves the sequence is DNAGPU_ERR_BAD_ARG; count == 0 is DNAGPU_ERR_DNA_EMPTY,
+ * because the type has no empty value.  The bits behind the result's last base are zero (dnagpu_dna_upload's rule); no word
+ * of dna outside [first/32, ceil((first+count)/32)) is read and the result never depends on bits behind dna's last base
+ * (dnagpu_dna_wrap's rule).  Free the result with dnagpu_dna_free. */
+int dnagpu_dna_revcomp(dnagpu_ctx *ctx, const dnagpu_dna *dna, uint64_t first, uint64_t count, dnagpu_dna **out);
 /* ---- binary wire image: dna_recv / dna_send (dna.c:244-268, 270-291) ---------------------------
  * Wire image of a dna: int64 length in bases, then ceil(length/32) packed words, every field in
  * network byte order (what pq_sendint64 writes and pq_getmsgint64 reads).  The reference moves its
@@ -319,6 +327,17 @@ void dnagpu_hist_free(dnagpu_ctx *ctx, dnagpu_hist *h);
 typedef struct dnagpu_acc dnagpu_acc;
 int dnagpu_acc_create(dnagpu_ctx *ctx, int k, dnagpu_acc **out);
 int dnagpu_acc_add(dnagpu_ctx *ctx, dnagpu_acc *acc, const dnagpu_hist *h);
+/* The strand-neutral add: every group of h is added under the CANONICAL form of its key (dnagpu_kmer_strand below, k = the
+ * accumulator's), so a k-mer and its reverse complement are one group: its count is count(x) + count(rc(x)), or count(x)
+ * alone when x is its own reverse complement (even k only; such a key is not doubled).  Every rule of dnagpu_acc_add holds:
+ * any histogram, padding slots skipped, a histogram that records no k accepted, and every error leaves the accumulator as
+ * it was.  total grows by the histogram's total; distinct grows by the canonical keys that are new.  The all-ones key (32
+ * G's) folds into 0xAAAA... (32 C's); key 0 (32 A's) stays, and 32 T's fold into it.  The accumulator holds canonical groups
+ * only if EVERY add into it is this one; the library does not track that -- a plain dnagpu_acc_add of a key that is not
+ * canonical simply makes a group of its own.  spectrum, select, top, rank, download and dnagpu_acc_join read such an
+ * accumulator like any other, so Jaccard and containment of two canonical sets are strand-neutral.  Cost: the same passes
+ * as dnagpu_acc_add. */
+int dnagpu_acc_add_canonical(dnagpu_ctx *ctx, dnagpu_acc *acc, const dnagpu_hist *h);
 uint64_t dnagpu_acc_distinct(const dnagpu_acc *acc);
 uint64_t dnagpu_acc_total(const dnagpu_acc *acc);
 int dnagpu_acc_summary(dnagpu_ctx *ctx, const dnagpu_acc *acc, uint64_t *total, uint64_t *unique, uint64_t *checksum);
@@ -604,6 +623,22 @@ int dnagpu_multi_last_times(const dnagpu_multi *m, dnagpu_multi_times *out);
 /* kmer_hash (dna.c:722-735): PostgreSQL hash_any over the 8 bytes of bit_sequence. n keys in,
  * n uint32 out; both host, or both device when on_device != 0. */
 int dnagpu_kmer_hash(dnagpu_ctx *ctx, const uint64_t *keys, uint64_t n, uint32_t *out, int on_device);
+/* The strand forms of n keys of k bases.  Codes are the reference's, A=00 T=01 C=10 G=11, so the complement of a base is
+ * code ^ 1 and, with rev2 = the 32 two-bit fields of a word in reverse order and mask = the low 2k bits,
+ *   rc(key, k) = (rev2(key & mask) >> (64 - 2k)) ^ (0x5555555555555555 & mask).
+ * The canonical form of a k-mer is whichever of key and rc(key) comes FIRST IN THIS LIBRARY'S INDEX ORDER: text order under
+ * A < T < C < G with base 0 most significant (dnagpu_kmer_index_*).  That is not the conventional A < C < G < T: canonical
+ * keys of another tool are a different choice of strand for about half the k-mers, though the groups are the same.
+ * key == rc(key) happens only at even k (16 such keys at k = 4, none at k = 5); such a key is canonical.
+ * out[i] = rc(keys[i]) (DNAGPU_STRAND_REVCOMP) or canonical(keys[i]) (DNAGPU_STRAND_CANONICAL); flipped[i] (may be NULL) = 1
+ * when out[i] != (keys[i] & mask), else 0.  Bits of a key above 2k are masked off (the index build's rule).  out may equal
+ * keys.  All arrays host, or all device when on_device != 0.  Checks, in order: a mode other than the two is
+ * DNAGPU_ERR_BAD_ARG; k outside 1 .. 32 is DNAGPU_ERR_INVALID_K; a NULL ctx, or NULL keys / out with n > 0, is
+ * DNAGPU_ERR_BAD_ARG; n == 0 is DNAGPU_OK. */
+#define DNAGPU_STRAND_REVCOMP   0
+#define DNAGPU_STRAND_CANONICAL 1
+int dnagpu_kmer_strand(dnagpu_ctx *ctx, const uint64_t *keys, uint64_t n, int k, int mode,
+                       uint64_t *out, uint8_t *flipped, int on_device);
 /* flags[i] = 1 when keys[i] (a kmer of k bases) satisfies `filter`, else 0.  Same error rules as
  * dnagpu_generate_kmers_filtered. */
 int dnagpu_kmer_match(dnagpu_ctx *ctx, const uint64_t *keys, uint64_t n, int k,

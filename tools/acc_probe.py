@@ -5,8 +5,10 @@
   cfg6        config 6's table (10^7 reads of 150 bases, k = 31) counted in 8 batches; the batches added up through the
               accumulator against the same batches through the dnagpu_hist_merge chain (which still fits under 2^32 there)
   cfg4x2      config 4's histogram (3 * 10^9 bases) added twice: total 2 * 2999999970, past 2^32
+  strand      config 4's histogram (k = 31, the largest size here) through add and through add_canonical,
+              each into an empty accumulator and into one that already holds it; the two alternate inside one run
 
-usage: python tools/acc_probe.py [cfg3] [cfg6] [cfg4x2] [--reps N]     (default: all three)
+usage: python tools/acc_probe.py [cfg3] [cfg6] [cfg4x2] [strand] [--reps N]     (default: the first three)
 Prints one JSON line per measurement.  Times are host clocks around calls that end in a device synchronise (every add
 reads its result back), after one warm-up of the same shapes."""
 import json
@@ -119,6 +121,34 @@ def cfg4x2(pkg, ctx, reps):
         raise SystemExit(3)
 
 
+def strand(pkg, ctx, reps):
+    want = DIGESTS["4"]
+    d = ctx.synth(want["seed"], want["n_bases"])
+    h = ctx.count_kmers_unordered(d, want["k"])
+    d.free()
+    ms = {(c, w): [] for c in (False, True) for w in ("empty", "resident")}
+    distinct = {}
+    for r in range(reps + 1):                      # (rep 0: warm-up -- the pool's first hipMallocs)
+        for canonical in (False, True):
+            acc = ctx.accumulator(want["k"])
+            t1, _ = timed(lambda: acc.add(h, canonical=canonical))
+            t2, _ = timed(lambda: acc.add(h, canonical=canonical))
+            if r:
+                ms[(canonical, "empty")].append(t1)
+                ms[(canonical, "resident")].append(t2)
+            assert acc.total == 2 * want["total"]
+            distinct[canonical] = acc.distinct
+            acc.free()                             # (back to the pool: the next accumulator takes the same buffers)
+    assert distinct[False] == want["distinct"] and distinct[True] <= distinct[False]
+    best = {key: min(v) for key, v in ms.items()}
+    emit(probe="strand", groups=h.distinct, canonical_groups=distinct[True],
+         add_empty_ms=ms[(False, "empty")], add_canonical_empty_ms=ms[(True, "empty")],
+         add_resident_ms=ms[(False, "resident")], add_canonical_resident_ms=ms[(True, "resident")],
+         ratio_empty=best[(True, "empty")] / best[(False, "empty")],
+         ratio_resident=best[(True, "resident")] / best[(False, "resident")])
+    h.free()
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     reps = 3
@@ -128,7 +158,7 @@ def main():
     pkg = load_package()
     with pkg.Context(0) as ctx:
         for name in args or ["cfg3", "cfg6", "cfg4x2"]:
-            {"cfg3": cfg3, "cfg6": cfg6, "cfg4x2": cfg4x2}[name](pkg, ctx, reps)
+            {"cfg3": cfg3, "cfg6": cfg6, "cfg4x2": cfg4x2, "strand": strand}[name](pkg, ctx, reps)
             ctx.trim()
 
 
