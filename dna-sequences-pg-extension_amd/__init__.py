@@ -29,6 +29,7 @@ from .binding import (  # noqa: F401
     Dna,
     DnaGpuError,
     Filter,
+    HITS_CANONICAL,
     Hist,
     JOIN_ANTI,
     JOIN_INNER,
@@ -39,6 +40,7 @@ from .binding import (  # noqa: F401
     SPECTRUM_MAX_BINS,
     STRAND_CANONICAL,
     STRAND_REVCOMP,
+    SeqHits,
     TOP_MAX,
     MULTI_AUTO,
     MULTI_COPY,

@@ -36,6 +36,7 @@ DEBUG_JOIN_DIRECT = 4096              # dnagpu_acc_join: the direct path for any
 JOIN_INNER = 0                        # JOIN .. ON a.kmer = b.kmer; INTERSECT
 JOIN_ANTI = 1                         # EXCEPT; NOT IN; NOT EXISTS
 JOIN_LEFT = 2                         # LEFT JOIN
+HITS_CANONICAL = 1                    # dnagpu_table_hits: probe with the canonical form of the row's key
 STRAND_REVCOMP = 0                    # dnagpu_kmer_strand: out = rc(key)
 STRAND_CANONICAL = 1                  # ... out = whichever of key and rc(key) comes first under A < T < C < G
 SPECTRUM_MAX_BINS = 1 << 20
@@ -192,6 +193,20 @@ def lib():
     L.dnagpu_acc_join.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, C.c_uint64, u64p, C.POINTER(JoinStats), C.c_int]
     L.dnagpu_acc_partitions.argtypes = [vp]
     L.dnagpu_acc_partitions.restype = C.c_uint64
+    L.dnagpu_table_hits.argtypes = [vp, vp, vp, C.c_uint, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(vp)]
+    for f in ("sequences", "first"):
+        getattr(L, f"dnagpu_seq_hits_{f}").argtypes = [vp]
+        getattr(L, f"dnagpu_seq_hits_{f}").restype = C.c_uint64
+    L.dnagpu_seq_hits_k.argtypes = [vp]
+    L.dnagpu_seq_hits_totals.argtypes = [vp, u64p, u64p, u64p]
+    for f in ("rows", "hits"):
+        getattr(L, f"dnagpu_seq_hits_device_{f}").argtypes = [vp]
+        getattr(L, f"dnagpu_seq_hits_device_{f}").restype = vp
+    L.dnagpu_seq_hits_read.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_int]
+    L.dnagpu_seq_hits_select.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, vp, vp, vp, C.c_uint64, u64p,
+                                         C.c_int]
+    L.dnagpu_seq_hits_free.argtypes = [vp, vp]
+    L.dnagpu_seq_hits_free.restype = None
     for obj in ("hist", "acc"):
         getattr(L, f"dnagpu_{obj}_spectrum").argtypes = [vp, vp, C.c_uint64, u64p]
         getattr(L, f"dnagpu_{obj}_select").argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, u64p, C.c_int]
@@ -413,6 +428,102 @@ class Ranking:
             if self.ctx._base_debug & DEBUG_GUARD_POOL:
                 self.ctx.synchronize()          # raises if a kernel wrote past the end of a work buffer
             lib().dnagpu_ranking_free(self.ctx.h, self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
+class SeqHits:
+    """dnagpu_seq_hits: for every sequence of a window of a table, its rows and how many of them occur in a counted set; a
+    snapshot in device memory (Context.table_hits)"""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+
+    @property
+    def sequences(self):
+        return int(lib().dnagpu_seq_hits_sequences(self.h))
+
+    @property
+    def first(self):
+        return int(lib().dnagpu_seq_hits_first(self.h))
+
+    @property
+    def k(self):
+        return int(lib().dnagpu_seq_hits_k(self.h))
+
+    @property
+    def device_rows(self):
+        """device pointer of `sequences` uint32 (None for a window of 0 sequences)"""
+        return lib().dnagpu_seq_hits_device_rows(self.h)
+
+    @property
+    def device_hits(self):
+        return lib().dnagpu_seq_hits_device_hits(self.h)
+
+    def totals(self):
+        """-> (rows, hits, sequences with at least one hit) over the window"""
+        r, h, s = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _chk(lib().dnagpu_seq_hits_totals(self.h, C.byref(r), C.byref(h), C.byref(s)))
+        return r.value, h.value, s.value
+
+    def read(self, first=0, count=None, on_device=False, out=None):
+        """entries [first, first + count) of the window (count=None: all from first on), as uint64.  host: -> (rows, hits).
+        on_device: into out=(dev_rows, dev_hits) of count uint64 each (either may be None) -> count; without out the arrays
+        are allocated here (Context.buffer_free them) -> (dev_rows, dev_hits, count)"""
+        if count is None:
+            count = self.sequences - first
+        fn = lib().dnagpu_seq_hits_read
+        if on_device:
+            if out is not None:
+                _chk(fn(self.ctx.h, self.h, first, count, out[0], out[1], 1))
+                return count
+            dr = self.ctx.buffer_alloc(8 * max(count, 1))
+            dh = None
+            try:
+                dh = self.ctx.buffer_alloc(8 * max(count, 1))
+                _chk(fn(self.ctx.h, self.h, first, count, dr, dh, 1))
+            except Exception:
+                self.ctx.buffer_free(dr)
+                if dh is not None:
+                    self.ctx.buffer_free(dh)
+                raise
+            return dr, dh, count
+        rows = np.empty(max(count, 1), dtype=np.uint64)
+        hits = np.empty(max(count, 1), dtype=np.uint64)
+        _chk(fn(self.ctx.h, self.h, first, count, rows.ctypes.data, hits.ctypes.data, 0))
+        return rows[:count], hits[:count]
+
+    def select(self, min_hits=0, max_hits=U64_MAX, frac=(0, 1), cap=None, on_device=False, out=None, want=(True, True, True)):
+        """the sequences with min_hits <= hits <= max_hits and hits / rows >= frac[0] / frac[1], in ascending sequence id.
+        host: -> (seq, rows, hits, n_matches): at most cap rows (cap=None: all of them -- two calls); an array `want` turns
+        off comes back as None.  on_device: into out=(dev_seq, dev_rows, dev_hits) of cap uint64 each (any may be None) ->
+        n_matches"""
+        n = C.c_uint64()
+        fn = lib().dnagpu_seq_hits_select
+        num, den = frac
+        if cap is None:
+            _chk(fn(self.ctx.h, self.h, min_hits, max_hits, num, den, None, None, None, 0, C.byref(n), 0))
+            cap = n.value
+        if on_device:
+            ds, dr, dh = out
+            _chk(fn(self.ctx.h, self.h, min_hits, max_hits, num, den, ds, dr, dh, cap, C.byref(n), 1))
+            return n.value
+        arrs = [np.empty(max(cap, 1), dtype=np.uint64) if w else None for w in want]
+        ptrs = [a.ctypes.data if a is not None else None for a in arrs]
+        _chk(fn(self.ctx.h, self.h, min_hits, max_hits, num, den, ptrs[0], ptrs[1], ptrs[2], cap, C.byref(n), 0))
+        m = min(n.value, cap)
+        return tuple(a[:m] if a is not None else None for a in arrs) + (n.value,)
+
+    def free(self):
+        if self.h:
+            if self.ctx._base_debug & DEBUG_GUARD_POOL:
+                self.ctx.synchronize()          # raises if a kernel wrote past the end of a work buffer
+            lib().dnagpu_seq_hits_free(self.ctx.h, self.h)
             self.h = None
 
     def __enter__(self):
@@ -978,6 +1089,17 @@ class Context:
         h = C.c_void_p()
         _chk(lib().dnagpu_count_kmers_table(self.h, dna.h, k, C.byref(h)))
         return Hist(self, h)
+
+    def table_hits(self, dna, acc, canonical=False, min_count=1, max_count=U64_MAX, seq_first=0, seq_count=None):
+        """for every sequence of [seq_first, seq_first + seq_count) of the resident table dna (seq_count=None: all from
+        seq_first on): its rows and how many of them are groups of the Accumulator acc with min_count <= count <= max_count
+        (canonical: looked up by the canonical form of the key) -> SeqHits (free it)"""
+        if seq_count is None:
+            seq_count = dna.n_sequences - seq_first
+        out = C.c_void_p()
+        _chk(lib().dnagpu_table_hits(self.h, dna.h, acc.h, HITS_CANONICAL if canonical else 0, min_count, max_count, seq_first,
+                                     seq_count, C.byref(out)))
+        return SeqHits(self, out)
 
     def accumulator(self, k):
         """an empty k-mer accumulator on this context (dnagpu_acc_create): add histograms batch by batch, 64-bit counts"""

@@ -1,5 +1,5 @@
 // host_common.hpp -- what the host files of the C-ABI (dnagpu_api.hip, count_host.hip, sk_host.hip, multi_host.hip, query_host.hip,
-// filter_host.hip, index_host.hip, join_host.hip) share
+// filter_host.hip, index_host.hip, join_host.hip, hits_host.hip) share
 // (internal, like kernels.hpp): the error macros, the context / dna / histogram objects, the buffer pool, and the few
 // functions one of the files calls in another.  Declarations only, plus the templates and macros that must be visible;
 // the definitions are in dnagpu_api.hip unless a section says otherwise.
@@ -279,6 +279,15 @@ struct dnagpu_acc {
     u64 distinct = 0, total = 0;
     std::vector<u64> pre;     // groups before each partition (+ the total): the download order, built after an add
     u64 *dev_pre = nullptr;
+};
+
+// per-sequence hits of a window of a table (hits_host.hip): a snapshot that depends on neither of its sources
+struct dnagpu_seq_hits {
+    u64 n = 0, first = 0;       // sequences of the window, and the first of them
+    int k = 0;
+    u32 *rows = nullptr;        // pool memory, n entries each (null when n == 0)
+    u32 *hits = nullptr;
+    u64 tot_rows = 0, tot_hits = 0, tot_seqs_hit = 0;
 };
 
 struct dnagpu_records {

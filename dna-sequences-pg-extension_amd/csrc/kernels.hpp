@@ -237,6 +237,45 @@ struct JoinArgs {
 hipError_t launch_join_partition(const JoinArgs &a, u64 p_lo, u64 n_parts, hipStream_t st);
 hipError_t launch_join_direct(const JoinArgs &a, u64 p_lo, u64 n_parts, hipStream_t st);
 
+// ---- per-sequence hits of a table's k-mers in an accumulator (hits_kernels.hip; the layout of the scratch
+// arrays is hits_math.hpp's).  The window is the stream bases [a0, a0 + n), n <= 2^32 - 1; row r is the k-mer at a0 + r.
+struct HitsWindow {
+    const u64 *words;
+    u64 n_words;
+    const u32 *marks;
+    u64 n_mark_words;
+    u64 a0, n;
+    int k;
+    int canonical;                    // probe with the canonical form of the row's key (strand_math.hpp)
+};
+struct HitsSet {                      // the accumulator's table (it must hold one) and the count bounds, lo >= 1
+    const u64 *table;
+    const u32 *occ;
+    int pbits;
+    u64 lo, hi;
+    const u64 *idle;                  // 16 readable, 16-byte aligned bytes of no meaning: what a row that is not probed loads
+};
+struct HitsPredicate {
+    u64 min_hits, max_hits, frac_num, frac_den;
+};
+// sweep: mask / word_pre (hits_mask_words(n) words each) and tile_tot (hits_tiles(n) words); a row that reaches across a mark
+// is not probed and has no bit.  The caller scans tile_tot into tile_base (launch_scan_u32).
+hipError_t launch_hits_sweep(const HitsWindow &w, const HitsSet &set, u32 *mask, u32 *word_pre, u32 *tile_tot, hipStream_t s);
+// out2[0] = seq_starts[seq_first], out2[1] = seq_starts[seq_first + seq_count]
+hipError_t launch_hits_bounds(const u64 *seq_starts, u64 seq_first, u64 seq_count, u64 *out2, hipStream_t s);
+// starts = seq_starts + seq_first; out_rows / out_hits[i] for the window's sequence i; totals3 (zeroed by the caller) += the
+// sums of rows, of hits, and the sequences with a hit.  mask == nullptr: nothing was swept, every sequence has 0 hits.
+hipError_t launch_hits_gather(const u64 *starts, u64 seq_count, u64 a0, int k, const u32 *mask, const u32 *word_pre,
+                              const u32 *tile_base, u32 *out_rows, u32 *out_hits, unsigned long long *totals3, hipStream_t s);
+// the stable selection of the sequences that pass p (hits_math.hpp: hits_selected): count -> tile_counts[tile]
+// (hits_select_tiles(n) tiles); write (tile_offsets = their exclusive scan) -> the matches in ascending sequence order,
+// entries from cap on not stored, any array may be null; out_seq = seq_first + index
+u32 hits_select_tiles(u64 n);
+hipError_t launch_hits_select_count(const u32 *rows, const u32 *hits, u64 n, const HitsPredicate &p, u32 *tile_counts, hipStream_t s);
+hipError_t launch_hits_select_write(const u32 *rows, const u32 *hits, u64 n, const HitsPredicate &p, const u32 *tile_offsets,
+                                    u64 seq_first, u64 *out_seq, u64 *out_rows, u64 *out_hits, u64 cap, hipStream_t s);
+hipError_t launch_hits_widen(const u32 *in, u64 *out, u64 n, hipStream_t s);
+
 // ---- queries over counted groups (query_kernels.hip).  A group source is a histogram part (n slots of
 // keys / 32-bit counts, count 0 = padding) or the accumulator's table (n = P * ACC_SLOTS 16-byte slots, occ[p] == 0: the
 // partition is not read); both are cut into tiles of Q_TILE slots.

@@ -127,6 +127,18 @@ def lib():
         L.table_kmers_failed.argtypes = [vp]
         L.table_kmers_end.restype = None
         L.table_kmers_end.argtypes = [vp]
+        L.table_hits_begin.restype = vp
+        L.table_hits_begin.argtypes = [vp, C.c_bool, C.c_int64, C.c_int64]
+        L.table_hits_add.restype = C.c_bool
+        L.table_hits_add.argtypes = [vp, vp]
+        L.table_hits_next.restype = C.c_bool
+        L.table_hits_next.argtypes = [vp] + [C.POINTER(C.c_int64)] * 3
+        L.table_hits_totals.restype = None
+        L.table_hits_totals.argtypes = [vp] + [C.POINTER(C.c_int64)] * 3
+        L.table_hits_failed.restype = C.c_bool
+        L.table_hits_failed.argtypes = [vp]
+        L.table_hits_end.restype = None
+        L.table_hits_end.argtypes = [vp]
         L.kmer_index_create.restype = vp
         L.kmer_index_create.argtypes = [C.POINTER(_Kmer), C.c_uint64]
         L.kmer_index_rows.restype = C.c_uint64
@@ -498,6 +510,38 @@ def table_kmers(rows, k, op=None, rhs=None):
         return np.array(seq, dtype=np.int64), np.array(pos, dtype=np.int64), np.array(keys, dtype=np.uint64)
     finally:
         lib().table_kmers_end(t)
+
+
+def table_hits(rows, set_agg, canonical=False, min_count=1, max_count=None):
+    """SELECT <row ordinal>, count(*) FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) g JOIN counts_b b ON g.kmer =
+    b.kmer WHERE b.count BETWEEN min_count AND max_count GROUP BY 1, with the rows that have no hit too: rows = the table's
+    `dna` values (or their text), set_agg = a count_kmers_table_agg (None: the NULL aggregate's ERROR) -> (seq int64[],
+    rows int64[], hits int64[], (sum rows, sum hits, rows with a hit)) in table order"""
+    import numpy as np
+    t = lib().table_hits_begin(set_agg.a if set_agg is not None else None, bool(canonical), int(min_count),
+                               -1 if max_count is None else int(max_count))
+    if not t:
+        raise _err()
+    try:
+        for r in rows:
+            if isinstance(r, str):
+                r = dna(r)
+            if not lib().table_hits_add(t, r.p):
+                raise _err()
+        seq, nrows, hits = [], [], []
+        sq, nr, nh = C.c_int64(), C.c_int64(), C.c_int64()
+        while lib().table_hits_next(t, C.byref(sq), C.byref(nr), C.byref(nh)):
+            seq.append(sq.value)
+            nrows.append(nr.value)
+            hits.append(nh.value)
+        if lib().table_hits_failed(t):
+            raise _err()
+        tot = [C.c_int64() for _ in range(3)]
+        lib().table_hits_totals(t, *[C.byref(x) for x in tot])
+        return (np.array(seq, dtype=np.int64), np.array(nrows, dtype=np.int64), np.array(hits, dtype=np.int64),
+                tuple(x.value for x in tot))
+    finally:
+        lib().table_hits_end(t)
 
 
 class kmer_index:

@@ -1035,10 +1035,10 @@ struct CountKmersJoin {
 };
 
 /* the aggregate's accumulator with every row so far in it (an aggregate that saw no row gets an empty one) */
-static dnagpu_acc *agg_flushed_acc(CountKmersAgg *a)
+static dnagpu_acc *agg_flushed_acc(CountKmersAgg *a, const char *who)
 {
     if (a->failed) {
-        ereport_error("count_kmers_join: an aggregate has failed");
+        ereport_error("%s: an aggregate has failed", who);
         return NULL;
     }
     if (!agg_flush(a)) {
@@ -1065,8 +1065,8 @@ CountKmersJoin *count_kmers_join_begin(CountKmersAgg *left, CountKmersAgg *right
         ereport_error("count_kmers_join: the two sides count kmers of different lengths (%d and %d)", left->k, right->k);
         return NULL;
     }
-    dnagpu_acc *la = agg_flushed_acc(left);
-    dnagpu_acc *ra = la ? agg_flushed_acc(right) : NULL;
+    dnagpu_acc *la = agg_flushed_acc(left, "count_kmers_join");
+    dnagpu_acc *ra = la ? agg_flushed_acc(right, "count_kmers_join") : NULL;
     if (!la || !ra)
         return NULL;
     CountKmersJoin *j = (CountKmersJoin *)calloc(1, sizeof *j);
@@ -1330,6 +1330,143 @@ void table_kmers_end(TableKmers *t)
     free(t->keys);
     free(t->seq);
     free(t->pos);
+    free(t);
+}
+
+/* ------------------------------------------------------------------ per-row hits of a table in a counted set: table_hits */
+
+struct TableHits {
+    dnagpu_acc *set;                             /* the aggregate's accumulator (the aggregate outlives this object) */
+    unsigned flags;
+    uint64_t min_count, max_count;
+    bool started, failed;
+    uint64_t *words, n_bases, cap_words;         /* the open batch, packed as table_kmers_add packs its batches */
+    uint64_t *starts, n_seqs, cap_seqs;
+    uint64_t *rows, *hits, n_done, cap_rows, cap_hits;      /* the answers of the rows of the batches looked up so far */
+    uint64_t next;
+    uint64_t tot_rows, tot_hits, tot_seqs_hit;
+};
+
+TableHits *table_hits_begin(CountKmersAgg *set, bool canonical, int64_t min_count, int64_t max_count)
+{
+    if (!set) {
+        ereport_error("table_hits: the aggregate is missing");
+        return NULL;
+    }
+    dnagpu_acc *acc = agg_flushed_acc(set, "table_hits");
+    if (!acc)
+        return NULL;
+    TableHits *t = (TableHits *)calloc(1, sizeof *t);
+    if (!t) {
+        ereport_error("out of memory");
+        return NULL;
+    }
+    t->set = acc;
+    t->flags = canonical ? DNAGPU_HITS_CANONICAL : 0u;
+    t->min_count = min_count > 0 ? (uint64_t)min_count : 1;
+    t->max_count = max_count < 0 ? UINT64_MAX : (uint64_t)max_count;
+    return t;
+}
+
+/* the open batch: looked up on the device, its answers appended, emptied */
+static bool th_flush(TableHits *t)
+{
+    const uint64_t n = t->n_seqs;
+    if (n == 0)
+        return true;
+    if (!agg_grow((void **)&t->rows, &t->cap_rows, t->n_done + n) || !agg_grow((void **)&t->hits, &t->cap_hits, t->n_done + n))
+        return false;
+    bool ok = true;
+    if (t->n_bases == 0) {                                                /* empty rows only: nothing to upload */
+        memset(t->rows + t->n_done, 0, (size_t)n * sizeof(uint64_t));
+        memset(t->hits + t->n_done, 0, (size_t)n * sizeof(uint64_t));
+    } else {
+        dnagpu_dna *d = NULL;
+        dnagpu_seq_hits *h = NULL;
+        uint64_t r = 0, c = 0, s = 0;
+        ok = ctx() != NULL && gpu_ok(dnagpu_dna_upload(g_ctx, t->words, t->n_bases, &d)) &&
+             gpu_ok(dnagpu_dna_set_sequences(g_ctx, d, t->starts, n)) &&
+             gpu_ok(dnagpu_table_hits(g_ctx, d, t->set, t->flags, t->min_count, t->max_count, 0, n, &h)) &&
+             gpu_ok(dnagpu_seq_hits_read(g_ctx, h, 0, n, t->rows + t->n_done, t->hits + t->n_done, 0)) &&
+             gpu_ok(dnagpu_seq_hits_totals(h, &r, &c, &s));
+        if (ok) {
+            t->tot_rows += r;
+            t->tot_hits += c;
+            t->tot_seqs_hit += s;
+        }
+        if (h)
+            dnagpu_seq_hits_free(g_ctx, h);
+        if (d)
+            dnagpu_dna_free(g_ctx, d);
+    }
+    if (ok)
+        t->n_done += n;
+    t->n_bases = 0;
+    t->n_seqs = 0;
+    return ok;
+}
+
+bool table_hits_add(TableHits *t, const Dna *row)
+{
+    if (t->started || t->failed) {
+        ereport_error("table_hits: row added after the first row was served or the scan failed");
+        return false;
+    }
+    if (t->n_seqs > 0 && t->n_bases + row->length > g_agg_flush_bases && !th_flush(t)) {     /* a long row: a batch of its own */
+        t->failed = true;
+        return false;
+    }
+    if (!batch_append(&t->words, &t->n_bases, &t->cap_words, &t->starts, &t->n_seqs, &t->cap_seqs, row)) {
+        t->failed = true;
+        return false;
+    }
+    if (t->n_bases >= g_agg_flush_bases && !th_flush(t)) {
+        t->failed = true;
+        return false;
+    }
+    return true;
+}
+
+bool table_hits_next(TableHits *t, int64_t *seq, int64_t *rows, int64_t *hits)
+{
+    if (t->failed)
+        return false;
+    if (!t->started) {
+        t->started = true;
+        if (!th_flush(t)) {                                               /* the last batch */
+            t->failed = true;
+            return false;
+        }
+    }
+    if (t->next >= t->n_done)
+        return false;
+    const uint64_t i = t->next++;
+    if (seq)
+        *seq = (int64_t)i;
+    if (rows)
+        *rows = (int64_t)t->rows[i];
+    if (hits)
+        *hits = (int64_t)t->hits[i];
+    return true;
+}
+
+void table_hits_totals(const TableHits *t, int64_t *rows, int64_t *hits, int64_t *seqs_hit)
+{
+    if (rows) *rows = (int64_t)t->tot_rows;
+    if (hits) *hits = (int64_t)t->tot_hits;
+    if (seqs_hit) *seqs_hit = (int64_t)t->tot_seqs_hit;
+}
+
+bool table_hits_failed(const TableHits *t) { return t->failed; }
+
+void table_hits_end(TableHits *t)
+{
+    if (!t)
+        return;
+    free(t->words);
+    free(t->starts);
+    free(t->rows);
+    free(t->hits);
     free(t);
 }
 

@@ -191,6 +191,26 @@ bool table_kmers_next(TableKmers *t, int64_t *seq, int64_t *pos, Kmer *out);
 bool table_kmers_failed(const TableKmers *t);
 void table_kmers_end(TableKmers *t);
 
+/* ---- SELECT d.id, count(*) FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS g(kmer) JOIN counts_b b ON g.kmer =
+ * b.kmer WHERE b.count BETWEEN min_count AND max_count GROUP BY d.id: per ROW of a table, how many of its k-mers occur in a
+ * counted set -- the Hash Join through kmer_hash_ops folded by sequence on the device ----
+ * begin: the set is a count_kmers_agg aggregate (k is the aggregate's); begin flushes it, as count_kmers_join_begin does, and
+ * the aggregate stays usable afterwards but must outlive this object.  canonical = look the canonical form of every k-mer up
+ * (for an aggregate begun with count_kmers_agg_begin_canonical).  min_count <= 0 means 1, max_count < 0 no upper bound.
+ * NULL + dna_glue_errmsg() for a NULL or failed aggregate or a GPU error.
+ * add = one call per row, in order, packed and batched exactly as table_kmers_add does (the aggregate's flush size; a longer
+ * row is a batch of its own); a batch that is full is looked up at once (dnagpu_dna_upload + dnagpu_dna_set_sequences +
+ * dnagpu_table_hits) and only its 16 bytes per row are kept.  next = one row of the answer, in table order: seq = the 0-based
+ * ordinal of the add call, rows = its generate_kmers rows, hits = those found in the set; the first next looks the last batch
+ * up, and add is refused from then on.  totals (complete from the first next on) = sum(rows), sum(hits), rows with hits > 0. */
+typedef struct TableHits TableHits;
+TableHits *table_hits_begin(CountKmersAgg *set, bool canonical, int64_t min_count, int64_t max_count);
+bool table_hits_add(TableHits *t, const Dna *row);
+bool table_hits_next(TableHits *t, int64_t *seq, int64_t *rows, int64_t *hits);
+void table_hits_totals(const TableHits *t, int64_t *rows, int64_t *hits, int64_t *seqs_hit);
+bool table_hits_failed(const TableHits *t);
+void table_hits_end(TableHits *t);
+
 /* ---- CREATE INDEX ... ON kmer_data_t USING spgist (kmer_sequence spgist_kmer_ops) and the index scans of `=`, `^@` and `@>`
  * over the stored column (dna--1.0.sql:304-314; test.sql:156-270) ----
  * create: column[i] = the kmer of heap row i; the keys go to the device once and are sorted there (dnagpu_kmer_index_build).

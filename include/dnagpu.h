@@ -37,7 +37,8 @@ extern "C" {
  * dnagpu_hist_merge), the rows of a table of sequences with the fused WHERE forms (dnagpu_generate_kmers_table), the index
  * over a stored kmer column (dnagpu_kmer_index_*) and its updates (dnagpu_kmer_index_append / _delete / _next_row), the
  * join of two accumulators (dnagpu_acc_join, dnagpu_acc_partitions), the strand-neutral forms (dnagpu_dna_revcomp,
- * dnagpu_kmer_strand, dnagpu_acc_add_canonical): additions only, so the number stays */
+ * dnagpu_kmer_strand, dnagpu_acc_add_canonical), the per-sequence hits of a table in a counted set (dnagpu_table_hits,
+ * dnagpu_seq_hits_*): additions only, so the number stays */
 #define DNAGPU_ABI_VERSION 2
 
 /* ---- status codes ------------------------------------------------------------------------
@@ -387,6 +388,67 @@ int dnagpu_acc_join(dnagpu_ctx *ctx, const dnagpu_acc *left, const dnagpu_acc *r
                     uint64_t *out_keys, uint64_t *out_left, uint64_t *out_right, uint64_t cap,
                     uint64_t *n_out, dnagpu_join_stats *stats, int out_on_device);
 uint64_t dnagpu_acc_partitions(const dnagpu_acc *acc);
+
+/* ---- per-sequence hits of a table's k-mers in a counted set: the other plan kmer_hash_ops (dna--1.0.sql:204-212) makes
+ * possible -- the rows of a table of sequences hash-joined to a counted set and folded BY SEQUENCE:
+ *   SELECT d.id, count(*) AS hits
+ *   FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS g(kmer) JOIN counts_b b ON g.kmer = b.kmer
+ *   WHERE b.count BETWEEN min_count AND max_count GROUP BY d.id           [HAVING count(*) >= m, or hits / rows >= f]
+ * (read screening, host depletion, containment of a read in a reference).  It runs on the device and hands
+ * back 8 bytes per SEQUENCE, or with a threshold only the sequences that pass.
+ * Input: dna is a table made resident with dnagpu_dna_set_sequences; set is any accumulator of the same context; k is the
+ *   accumulator's.  Both are only read: the set's summary and download order and the table's sequence set stay as they were.
+ * Meaning: for every sequence s of [seq_first, seq_first + seq_count): rows[s] = the rows of its own generate_kmers, len - k + 1,
+ *   0 when len < k (the 64-bit restatement of dna.c:781; empty sequences have 0); hits[s] = those rows whose key is a group of
+ *   set with min_count <= count <= max_count.  With DNAGPU_HITS_CANONICAL the canonical form of the row's key
+ *   (dnagpu_kmer_strand's) is looked up instead: the form for a set made with dnagpu_acc_add_canonical.  min_count == 0 means
+ *   1; min_count > max_count matches nothing (DNAGPU_OK).  Key 0 and the all-ones key are keys like any other; a partition
+ *   that holds nothing is never read; a set without a table gives hits of 0 and the true rows.
+ * Snapshot: a dnagpu_seq_hits owns two dense uint32 device arrays of seq_count entries from the context's pool (the stream
+ *   rule above) -- what dnagpu_seq_hits_device_rows / _hits return, entry i belonging to sequence seq_first + i -- and does
+ *   not depend on dna or set afterwards.  seq_count == 0 gives a valid object of 0 sequences that holds no device memory
+ *   (both accessors NULL).
+ * Limit: the window's bases, seq_starts[seq_first + seq_count] - seq_starts[seq_first], may be at most 2^32 - 1, else
+ *   DNAGPU_ERR_TOO_LARGE (dnagpu_generate_kmers_table's per-call rule: it is what makes the 32-bit arrays exact); larger tables
+ *   are paged by sequence window, and windows tile.  (More than 2^32 - 1 sequences in one window: DNAGPU_ERR_TOO_LARGE too.)
+ *   Today dnagpu_dna_set_sequences itself refuses a stream of more than 2^32 - 1 bases, so no resident table reaches either
+ *   limit: they are stated, and checked, for the day that rule is lifted.
+ * Checks, in order: flags outside 0 .. 1 is DNAGPU_ERR_BAD_ARG (the range before the missing object); a NULL ctx, dna, set or
+ *   out is DNAGPU_ERR_BAD_ARG; a non-empty stream without a sequence set is DNAGPU_ERR_BAD_ARG; seq_first > the table's
+ *   sequences or seq_count > sequences - seq_first is DNAGPU_ERR_BAD_ARG; the limit above; an allocation failure is
+ *   DNAGPU_ERR_OOM with nothing leaked and *out = NULL.  The call waits for its work.
+ * dnagpu_seq_hits_sequences / _first / _k: seq_count, seq_first, k; 0 for NULL.
+ * dnagpu_seq_hits_totals: the sums of rows and of hits over the window and the sequences with at least one hit, exact 64-bit
+ *   sums made on the device when the object is built (any output may be NULL; a NULL h is DNAGPU_ERR_BAD_ARG).
+ * dnagpu_seq_hits_read: entries [first, first + count) of the window widened to uint64, to out_rows / out_hits (either may be
+ *   NULL; host memory, or device memory when out_on_device != 0), by dnagpu_ranking_read's window rule: first > sequences or
+ *   count > sequences - first is DNAGPU_ERR_BAD_ARG; count == 0 or both outputs NULL is DNAGPU_OK.  Waits for the copy.
+ * dnagpu_seq_hits_select: the sequences with min_hits <= hits <= max_hits and hits * frac_den >= frac_num * rows (the HAVING
+ *   forms; 0 / 1 asks nothing of the fraction).  frac_den == 0, or frac_num or frac_den above 2^32 - 1 (the products must stay
+ *   exact in 64 bits), is DNAGPU_ERR_BAD_ARG and is checked first; then a NULL ctx, h or n_out.  Rows come in ASCENDING
+ *   SEQUENCE ID: out_seq holds global ids, seq_first + i; at most cap rows go to each of out_seq / out_rows / out_hits (any
+ *   may be NULL); *n_out = ALL matches, and when it exceeds cap the FIRST cap of that order are written -- deterministic,
+ *   unlike the count selects, because a caller pages on it.  min_hits = 0, max_hits = 0 is the depletion query: the
+ *   sequences with no hit.  Waits for its work.
+ * dnagpu_seq_hits_free returns the arrays to ctx's pool (NULL h: nothing).
+ * Out of scope: a weight per sequence (the sum of the set's counts over the hits); a histogram as the set (make an
+ *   accumulator and add it once); more than one GPU. */
+typedef struct dnagpu_seq_hits dnagpu_seq_hits;
+#define DNAGPU_HITS_CANONICAL 1u   /* probe with the canonical form of the row's key (dnagpu_kmer_strand's) */
+int dnagpu_table_hits(dnagpu_ctx *ctx, const dnagpu_dna *dna, const dnagpu_acc *set, unsigned flags,
+                      uint64_t min_count, uint64_t max_count, uint64_t seq_first, uint64_t seq_count, dnagpu_seq_hits **out);
+uint64_t dnagpu_seq_hits_sequences(const dnagpu_seq_hits *h);
+uint64_t dnagpu_seq_hits_first(const dnagpu_seq_hits *h);
+int      dnagpu_seq_hits_k(const dnagpu_seq_hits *h);
+int dnagpu_seq_hits_totals(const dnagpu_seq_hits *h, uint64_t *rows, uint64_t *hits, uint64_t *seqs_hit);
+const uint32_t *dnagpu_seq_hits_device_rows(const dnagpu_seq_hits *h);
+const uint32_t *dnagpu_seq_hits_device_hits(const dnagpu_seq_hits *h);
+int dnagpu_seq_hits_read(dnagpu_ctx *ctx, const dnagpu_seq_hits *h, uint64_t first, uint64_t count,
+                         uint64_t *out_rows, uint64_t *out_hits, int out_on_device);
+int dnagpu_seq_hits_select(dnagpu_ctx *ctx, const dnagpu_seq_hits *h, uint64_t min_hits, uint64_t max_hits,
+                           uint64_t frac_num, uint64_t frac_den, uint64_t *out_seq, uint64_t *out_rows, uint64_t *out_hits,
+                           uint64_t cap, uint64_t *n_out, int out_on_device);
+void dnagpu_seq_hits_free(dnagpu_ctx *ctx, dnagpu_seq_hits *h);
 
 /* ---- count-ordered queries over counted groups: the reference's first counting statement is not a bare GROUP BY but
  *   SELECT k.kmer, count(*) FROM generate_kmers(...) AS k(kmer) GROUP BY k.kmer ORDER BY count(*) DESC   (test.sql:95)
