@@ -409,11 +409,12 @@ hipError_t launch_index_compact_count(const u32 *row, u64 n, const u32 *bitmap, 
 hipError_t launch_index_compact_write(const u64 *r, const u32 *row, u64 n, const u32 *bitmap, const u32 *tile_offsets, u64 *out_r,
                                       u32 *out_row, u64 n_out, hipStream_t s);
 
-// ---------------------------------------------------------------- superkmer_kernels.hip
+// ---------------------------------------------------------------- the super-k-mer engine (sk_device.hpp), three files
 // super-k-mer (minimizer) partitioning for long k-mers: the dna sweeps (level 0: records per coarse digit of every
 // chunk of rows / records scattered into the coarse buckets), the record level (level 1: d1), and the expansion of
 // mid buckets into key nodes.  k in [sk_min_k(), 32]; c0n = coarse buckets, b1bits = bits of d1, r0bits = split
 // bits of the root (2^r0bits >= c0n); records are 16 bytes each.
+// ---------------------------------------------------------------- sk_level0_kernels.hip
 int sk_min_k();
 int sk_minimizer_len(int k);          // m: 15 for k >= 23, 13 for k = 21, 22, 12 for k = 20
 int sk_tile_rows();
@@ -433,6 +434,23 @@ int sk_slab_words();
 u32 sk_slab_cap(u32 est, u64 chunk_rows, u64 sampled);
 hipError_t launch_sk_slab_init(const u32 *est, u32 r0bits, u32 chunk_rows, u32 sampled, u32 n_chunks, u32 *slab, Node *nodes,
                                hipStream_t s);
+// (a stage of the tail that is compiled in sk_level0_kernels.hip: see the head of that file)
+// long buckets of few distinct keys (repeats): one workgroup per bucket, one LDS table for the whole bucket; status[i] = 1
+// where the distinct keys outgrew the table (the bucket's range is then all padding)
+// slices of SKB records per big bucket: nsl[p] = its slices, msl[p] = the same if more than one (else 0); after exclusive
+// scans: sl_bucket / sl_idx[first slice of p + j] = (p, j).  Partial areas of sk_big_partial_slots() groups each, one per
+// slice of a sliced bucket (mfirst = scan of msl); part_n[area] = its groups (~0: the slice gave up).
+hipError_t launch_sk_node_lens(const Node *nodes, u32 n, u32 *lens, hipStream_t s);
+u32 sk_big_slice_records();
+u64 sk_big_partial_slots();
+hipError_t launch_sk_big_slices(const Node *fin, const u32 *list, u32 n_list, u32 *nsl, u32 *msl, hipStream_t s);
+hipError_t launch_sk_big_slice_fill(const u32 *nsl_raw, const u32 *sfirst, u32 n_list, u32 *sl_bucket, u32 *sl_idx, hipStream_t s);
+hipError_t launch_sk_count_big(const Node *fin, const u32 *list, const u32 *list_off, const u32 *nsl, const u32 *mfirst,
+                               const u32 *sl_bucket, const u32 *sl_idx, u32 n_slices, u32 n_list, const void *recs, int k,
+                               u64 *n_groups, u64 *seg_off, u32 *seg_cnt, u64 *out_keys, u32 *out_counts, u32 *status, u64 *part_keys,
+                               u32 *part_cnts, u32 *part_n, bool any_sliced, hipStream_t s);
+
+// ---------------------------------------------------------------- sk_level1_kernels.hip
 hipError_t launch_sk_hist1(const Node *nodes, const Chunk *chunks, u32 n_chunks, const void *recs, u32 *hist, u32 *kcount,
                            hipStream_t s, bool by_d2 = false);
 hipError_t launch_sk_scatter1(const Node *nodes, const Chunk *chunks, u32 n_chunks, const void *src, void *dst, const u32 *hist,
@@ -457,7 +475,29 @@ u32 sk_sample1_len();
 u32 sk_sample1_every();
 hipError_t launch_sk_sampled_regions(const Node *nodes, const Chunk *samples, u32 n_samples, const void *recs, u32 n_mid, u32 *est,
                                      u32 *rcap, u32 *rstart, u32 *scan_tmp, u32 *total, hipStream_t s);
-hipError_t launch_sk_heavy_finals(const Node *kids, u32 n, const u32 *kcount, Node *out, hipStream_t s);
+// every mid bucket's records regrouped by d2 from src into the same range of dst; out_nodes[16 i + j] = final bucket:
+// start / len in records, child_base = its k-mers
+int sk_regroup_tile();   // records one workgroup regroups in one go; longer mid buckets need any_long (a second kernel)
+hipError_t launch_sk_regroup(const Node *mids, u32 n_mids, const void *src, void *dst, Node *out_nodes, bool any_long, hipStream_t s);
+
+// ---------------------------------------------------------------- sk_tail_kernels.hip
+int sk_count_cap();       // most k-mers a final bucket may hold to be counted from its records
+hipError_t launch_sk_select_flags(const Node *fin, u32 n_fin, u32 cap, u32 big_limit, u32 *f_small, u32 *f_big, u32 *k_range,
+                                  u32 *k_big, hipStream_t s);
+hipError_t launch_sk_select_lists(const Node *fin, u32 n_fin, u32 cap, u32 big_limit, const u32 *p_small, const u32 *p_big,
+                                  const u32 *kb_range, u32 *list_small, u32 *off_small, u32 *list_big, u32 *off_big, hipStream_t s);
+// buckets that go through the expansion: too many k-mers for sk_count_big, or given up by it (big_status[p] != 0)
+hipError_t launch_sk_over_flags(const Node *fin, u32 n_fin, u32 cap, u32 big_limit, const u32 *p_big, const u32 *big_status,
+                                u32 *f_over, u32 *k_over, hipStream_t s);
+hipError_t launch_sk_over_list(const Node *fin, u32 n_fin, const u32 *f_raw, const u32 *p_over, const u32 *kb_over, Node *over_nodes,
+                               u32 *over_kbase, hipStream_t s);
+// final buckets list[0..n_list) (indices into fin) counted from their records in an LDS hash table; groups appended
+// at *cursor, seg_off / seg_cnt[bucket] = where they went
+// list_off[i] = first output slot of bucket list[i] (its range is as long as its k-mers; slots past its distinct keys are
+// count-0 padding); *n_groups += the groups written
+// (left: 2 n_list + 1 words of work memory -- the buckets the record test leaves to the k-mer table kernel)
+hipError_t launch_sk_count(const Node *fin, const u32 *list, const u32 *list_off, u32 n_list, const void *recs, int k, u64 *n_groups,
+                           u64 *seg_off, u32 *seg_cnt, u64 *out_keys, u32 *out_counts, u32 *left, hipStream_t s);
 // buckets sk_count does not take, expanded to keys in record order (no host step): slices of sk_flat_slice() records
 // per bucket (n_slices[i], then after an exclusive scan slice_first[i]; slice_rec0 = first record, slice_nrec = records),
 // k-mers per slice, after a scan the keys of slice s at key_base + slice_koff[s] and one key node per bucket
@@ -474,43 +514,9 @@ hipError_t launch_sk_slice_nodes(const Node *buckets, u32 nb, const u32 *slice_f
 hipError_t launch_sk_unmix(u64 *keys, u64 first, const u64 *end, u64 max_groups, int k, hipStream_t s);
 hipError_t launch_sk_expand_flat(const void *recs, const u32 *slice_rec0, const u32 *slice_nrec, const u32 *slice_koff, u32 key_base,
                                  u32 n_slices, int k, u64 *keys, hipStream_t s);
-// every mid bucket's records regrouped by d2 from src into the same range of dst; out_nodes[16 i + j] = final bucket:
-// start / len in records, child_base = its k-mers
-int sk_regroup_tile();   // records one workgroup regroups in one go; longer mid buckets need any_long (a second kernel)
-hipError_t launch_sk_regroup(const Node *mids, u32 n_mids, const void *src, void *dst, Node *out_nodes, bool any_long, hipStream_t s);
-// final buckets list[0..n_list) (indices into fin) counted from their records in an LDS hash table; groups appended
-// at *cursor, seg_off / seg_cnt[bucket] = where they went
-// list_off[i] = first output slot of bucket list[i] (its range is as long as its k-mers; slots past its distinct keys are
-// count-0 padding); *n_groups += the groups written
-// (left: 2 n_list + 1 words of work memory -- the buckets the record test leaves to the k-mer table kernel)
-hipError_t launch_sk_count(const Node *fin, const u32 *list, const u32 *list_off, u32 n_list, const void *recs, int k, u64 *n_groups,
-                           u64 *seg_off, u32 *seg_cnt, u64 *out_keys, u32 *out_counts, u32 *left, hipStream_t s);
+hipError_t launch_sk_heavy_finals(const Node *kids, u32 n, const u32 *kcount, Node *out, hipStream_t s);
 
-int sk_count_cap();       // most k-mers a final bucket may hold to be counted from its records
-hipError_t launch_sk_select_flags(const Node *fin, u32 n_fin, u32 cap, u32 big_limit, u32 *f_small, u32 *f_big, u32 *k_range,
-                                  u32 *k_big, hipStream_t s);
-hipError_t launch_sk_select_lists(const Node *fin, u32 n_fin, u32 cap, u32 big_limit, const u32 *p_small, const u32 *p_big,
-                                  const u32 *kb_range, u32 *list_small, u32 *off_small, u32 *list_big, u32 *off_big, hipStream_t s);
-// buckets that go through the expansion: too many k-mers for sk_count_big, or given up by it (big_status[p] != 0)
-hipError_t launch_sk_over_flags(const Node *fin, u32 n_fin, u32 cap, u32 big_limit, const u32 *p_big, const u32 *big_status,
-                                u32 *f_over, u32 *k_over, hipStream_t s);
-hipError_t launch_sk_over_list(const Node *fin, u32 n_fin, const u32 *f_raw, const u32 *p_over, const u32 *kb_over, Node *over_nodes,
-                               u32 *over_kbase, hipStream_t s);
-// long buckets of few distinct keys (repeats): one workgroup per bucket, one LDS table for the whole bucket; status[i] = 1
-// where the distinct keys outgrew the table (the bucket's range is then all padding)
-// slices of SKB records per big bucket: nsl[p] = its slices, msl[p] = the same if more than one (else 0); after exclusive
-// scans: sl_bucket / sl_idx[first slice of p + j] = (p, j).  Partial areas of sk_big_partial_slots() groups each, one per
-// slice of a sliced bucket (mfirst = scan of msl); part_n[area] = its groups (~0: the slice gave up).
-hipError_t launch_sk_node_lens(const Node *nodes, u32 n, u32 *lens, hipStream_t s);
-u32 sk_big_slice_records();
-u64 sk_big_partial_slots();
-hipError_t launch_sk_big_slices(const Node *fin, const u32 *list, u32 n_list, u32 *nsl, u32 *msl, hipStream_t s);
-hipError_t launch_sk_big_slice_fill(const u32 *nsl_raw, const u32 *sfirst, u32 n_list, u32 *sl_bucket, u32 *sl_idx, hipStream_t s);
-hipError_t launch_sk_count_big(const Node *fin, const u32 *list, const u32 *list_off, const u32 *nsl, const u32 *mfirst,
-                               const u32 *sl_bucket, const u32 *sl_idx, u32 n_slices, u32 n_list, const void *recs, int k,
-                               u64 *n_groups, u64 *seg_off, u32 *seg_cnt, u64 *out_keys, u32 *out_counts, u32 *status, u64 *part_keys,
-                               u32 *part_cnts, u32 *part_n, bool any_sliced, hipStream_t s);
-
+// ---------------------------------------------------------------- count_kernels.hip, continued
 // scatter-only microbenchmark entry (bench tooling): one level over a key array
 int scatter_tile_keys();
 int scatter_threads();

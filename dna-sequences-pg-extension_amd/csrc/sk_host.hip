@@ -6,7 +6,7 @@
 
 using namespace dnagpu;
 
-// ---- super-k-mer engine (superkmer_kernels.hip): the partition passes move 16-byte records of ~9 k-mers
+// ---- super-k-mer engine (sk_device.hpp, sk_*_kernels.hip): the partition passes move 16-byte records of ~9 k-mers
 // instead of 8-byte keys, and a final bucket is counted from its records in an LDS hash table: no key of it is
 // ever written to HBM.
 

@@ -1289,7 +1289,7 @@ def table_of_sequences(seed, n_seqs, lo, hi):
     return orc.synth_words(seed, n), starts
 
 
-# the super-k-mer engine's geometry (superkmer_kernels.hip): a wave tile emits records for SKW_ROWS = 63 x 32 rows (lane 63
+# the super-k-mer engine's geometry (sk_device.hpp): a wave tile emits records for SKW_ROWS = 63 x 32 rows (lane 63
 # only supplies hashes), a workgroup's four waves take one round of SK_TILE_ROWS, chunks are cut at multiples of a round
 SK_WAVE_ROWS = 2016
 SK_ROUND_ROWS = 4 * SK_WAVE_ROWS

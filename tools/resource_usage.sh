@@ -1,8 +1,9 @@
 #!/bin/bash
 # tools/resource_usage.sh [file.hip ...]: VGPRs / spills / scratch / LDS / occupancy of every kernel, from hipcc's
-# -Rpass-analysis=kernel-resource-usage (no GPU needed).  Default: the four kernel files.
+# -Rpass-analysis=kernel-resource-usage (no GPU needed).  Default: the super-k-mer engine's
+# three kernel files and the three of the tree, the extraction and the filters.
 cd "$(dirname "$0")/../dna-sequences-pg-extension_amd/csrc"
-FILES=${@:-"superkmer_kernels.hip count_kernels.hip extract_kernels.hip filter_kernels.hip"}
+FILES=${@:-"sk_level0_kernels.hip sk_level1_kernels.hip sk_tail_kernels.hip count_kernels.hip extract_kernels.hip filter_kernels.hip"}
 for f in $FILES; do
   hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -c $f -o /tmp/ru_$$.o -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c "
 import re,sys
