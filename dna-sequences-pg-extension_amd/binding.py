@@ -149,6 +149,9 @@ def lib():
     L.dnagpu_dna_sequences.argtypes = [vp]
     L.dnagpu_dna_sequences.restype = C.c_uint64
     L.dnagpu_count_kmers_table.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
+    L.dnagpu_dna_gather.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
+    L.dnagpu_dna_take.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
+    L.dnagpu_dna_sequence_starts.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_int]
     L.dnagpu_sk_buckets.argtypes = [vp, C.c_uint64, C.c_int]
     L.dnagpu_sk_records.argtypes = [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(vp)]
     L.dnagpu_records_buckets.argtypes = [vp]
@@ -359,6 +362,19 @@ class Dna:
     @property
     def n_sequences(self):
         return int(lib().dnagpu_dna_sequences(self.h))
+
+    def sequence_starts(self, first=0, count=None):
+        """entries [first, first + count) of the n_sequences + 1 starts of the resident sequence set (count=None: all from
+        first on; a Dna without a set has none) -> uint64[]"""
+        if count is None:
+            count = (self.n_sequences + 1 if self.n_sequences else 0) - first
+        out = np.empty(max(count, 1), dtype=np.uint64)
+        _chk(lib().dnagpu_dna_sequence_starts(self.ctx.h, self.h, first, count, out.ctypes.data, 0))
+        return out[:count]
+
+    def sequence_starts_device(self, first, count, dev_out):
+        """the same into count uint64 of device memory"""
+        _chk(lib().dnagpu_dna_sequence_starts(self.ctx.h, self.h, first, count, dev_out, 1))
 
     def free(self):
         if self.h:
@@ -956,6 +972,48 @@ class Context:
             count = dna.n_bases - first
         h = C.c_void_p()
         _chk(lib().dnagpu_dna_revcomp(self.h, dna.h, first, count, C.byref(h)))
+        return Dna(self, h)
+
+    def dna_take(self, dna, ids, flip=None, on_device=False):
+        """the sequences ids (global, 0-based, any order, repeats allowed) of the resident table dna as a new resident table
+        -> Dna; flip: one flag per id, non-zero = that sequence reverse-complemented.  host: arrays; on_device: ids =
+        (dev_ids, n) of uint64 -- what SeqHits.select(on_device=True) leaves in dev_seq -- and flip a device pointer of n
+        uint8 or None"""
+        if on_device:
+            return self.dna_take_device(dna, ids[0], ids[1], flip)
+        a = np.ascontiguousarray(ids, dtype=np.uint64)
+        f = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, dtype=np.uint8)
+        if f is not None and f.size != a.size:
+            raise ValueError("flip must hold one flag per id")
+        h = C.c_void_p()
+        _chk(lib().dnagpu_dna_take(self.h, dna.h, a.ctypes.data if a.size else None, f.ctypes.data if f is not None and f.size else None,
+                                   a.size, 0, C.byref(h)))
+        return Dna(self, h)
+
+    def dna_take_device(self, dna, dev_ids, n, dev_flip=None):
+        h = C.c_void_p()
+        _chk(lib().dnagpu_dna_take(self.h, dna.h, dev_ids, dev_flip, n, 1, C.byref(h)))
+        return Dna(self, h)
+
+    def dna_gather(self, dna, first, length, flip=None, on_device=False):
+        """segments [first[i], first[i] + length[i]) of dna's stream, back to back, as a new resident table of one sequence
+        per segment -> Dna; flip as in dna_take.  host: arrays; on_device: first = (dev_first, n), length and flip device
+        pointers"""
+        if on_device:
+            return self.dna_gather_device(dna, first[0], length, first[1], flip)
+        a = np.ascontiguousarray(first, dtype=np.uint64)
+        b = np.ascontiguousarray(length, dtype=np.uint64)
+        f = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, dtype=np.uint8)
+        if b.size != a.size or (f is not None and f.size != a.size):
+            raise ValueError("first, length and flip must be of one size")
+        h = C.c_void_p()
+        _chk(lib().dnagpu_dna_gather(self.h, dna.h, a.ctypes.data if a.size else None, b.ctypes.data if b.size else None,
+                                     f.ctypes.data if f is not None and f.size else None, a.size, 0, C.byref(h)))
+        return Dna(self, h)
+
+    def dna_gather_device(self, dna, dev_first, dev_len, n, dev_flip=None):
+        h = C.c_void_p()
+        _chk(lib().dnagpu_dna_gather(self.h, dna.h, dev_first, dev_len, dev_flip, n, 1, C.byref(h)))
         return Dna(self, h)
 
     def from_wire_device(self, dev_wire, wire_bytes):

@@ -276,6 +276,22 @@ hipError_t launch_hits_select_write(const u32 *rows, const u32 *hits, u64 n, con
                                     u64 seq_first, u64 *out_seq, u64 *out_rows, u64 *out_hits, u64 cap, hipStream_t s);
 hipError_t launch_hits_widen(const u32 *in, u64 *out, u64 n, hipStream_t s);
 
+// ---- the gather of segments of a packed stream into a new one (take_kernels.hip; the piece arithmetic is
+// take_math.hpp's).  segments: the list of n entries built and validated in one pass -- ids != nullptr: entry i is sequence
+// ids[i] of the table (seq_starts, n_seqs), its first base goes to seg_first[i]; else entry i is (in_first[i], in_len[i]) of
+// a stream of n_bases bases and seg_first is not written.  len32[i] = the entry's length, res2[0] = the sum of the lengths
+// in 64 bits (each counted as at most 2^32), res2[1] != 0: an id >= n_seqs or a segment that leaves the stream (res2 is
+// zeroed here).
+hipError_t launch_take_segments(const u64 *ids, const u64 *seq_starts, u64 n_seqs, const u64 *in_first, const u64 *in_len,
+                                u64 n_bases, u64 n, u64 *seg_first, u32 *len32, unsigned long long *res2, hipStream_t s);
+// out_starts[0 .. n] from the exclusive scan of the lengths (n entries) and their total
+hipError_t launch_take_starts(const u32 *scan, u64 n, u64 total, u64 *out_starts, hipStream_t s);
+// the sweep: out[0 .. ceil(total / 32)) = the segments back to back, segment i = the out_starts[i + 1] - out_starts[i] bases at
+// base seg_first[i] of src, reverse-complemented where seg_flip[i] != 0 (seg_flip may be null).  Every output word is
+// stored once, whole; bits behind the last base are zero; no word of src is read that holds no base of a segment.
+hipError_t launch_take_copy(const u64 *src, const u64 *seg_first, const uint8_t *seg_flip, const u64 *out_starts, u64 n, u64 total,
+                            u64 *out, hipStream_t s);
+
 // ---- queries over counted groups (query_kernels.hip).  A group source is a histogram part (n slots of
 // keys / 32-bit counts, count 0 = padding) or the accumulator's table (n = P * ACC_SLOTS 16-byte slots, occ[p] == 0: the
 // partition is not read); both are cut into tiles of Q_TILE slots.

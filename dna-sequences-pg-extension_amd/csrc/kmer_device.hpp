@@ -18,7 +18,7 @@ __host__ __device__ __forceinline__ u64 kmer_mask(int k)
 }
 
 // bits [sh, sh+64) of the 128-bit value hi:lo, sh in 0..62
-__device__ __forceinline__ u64 funnel(u64 lo, u64 hi, unsigned sh)
+__host__ __device__ __forceinline__ u64 funnel(u64 lo, u64 hi, unsigned sh)
 {
     return (lo >> sh) | ((hi << 1) << (63u - sh));
 }

@@ -139,6 +139,16 @@ def lib():
         L.table_hits_failed.argtypes = [vp]
         L.table_hits_end.restype = None
         L.table_hits_end.argtypes = [vp]
+        L.table_screen_begin.restype = vp
+        L.table_screen_begin.argtypes = [vp, C.c_bool] + [C.c_int64] * 6
+        L.table_screen_add.restype = C.c_bool
+        L.table_screen_add.argtypes = [vp, vp]
+        L.table_screen_next.restype = C.c_bool
+        L.table_screen_next.argtypes = [vp] + [C.POINTER(C.c_int64)] * 3 + [C.POINTER(vp)]
+        L.table_screen_failed.restype = C.c_bool
+        L.table_screen_failed.argtypes = [vp]
+        L.table_screen_end.restype = None
+        L.table_screen_end.argtypes = [vp]
         L.kmer_index_create.restype = vp
         L.kmer_index_create.argtypes = [C.POINTER(_Kmer), C.c_uint64]
         L.kmer_index_rows.restype = C.c_uint64
@@ -542,6 +552,36 @@ def table_hits(rows, set_agg, canonical=False, min_count=1, max_count=None):
                 tuple(x.value for x in tot))
     finally:
         lib().table_hits_end(t)
+
+
+def table_screen(rows, set_agg, canonical=False, min_count=1, max_count=None, min_hits=0, max_hits=None, frac=(0, 1)):
+    """SELECT <row ordinal>, d.sequence, count(*) ... JOIN counts_b b ... GROUP BY 1, 2 HAVING min_hits <= hits <= max_hits AND
+    hits / rows >= frac[0] / frac[1]: the rows of the table that pass the screen, themselves.  rows / set_agg / canonical /
+    min_count / max_count as table_hits -> (seq int64[], rows int64[], hits int64[], [dna]) in table order"""
+    import numpy as np
+    t = lib().table_screen_begin(set_agg.a if set_agg is not None else None, bool(canonical), int(min_count),
+                                 -1 if max_count is None else int(max_count), int(min_hits),
+                                 -1 if max_hits is None else int(max_hits), int(frac[0]), int(frac[1]))
+    if not t:
+        raise _err()
+    try:
+        for r in rows:
+            if isinstance(r, str):
+                r = dna(r)
+            if not lib().table_screen_add(t, r.p):
+                raise _err()
+        seq, nrows, hits, out = [], [], [], []
+        sq, nr, nh, p = C.c_int64(), C.c_int64(), C.c_int64(), C.c_void_p()
+        while lib().table_screen_next(t, C.byref(sq), C.byref(nr), C.byref(nh), C.byref(p)):
+            seq.append(sq.value)
+            nrows.append(nr.value)
+            hits.append(nh.value)
+            out.append(dna(p=p.value))
+        if lib().table_screen_failed(t):
+            raise _err()
+        return np.array(seq, dtype=np.int64), np.array(nrows, dtype=np.int64), np.array(hits, dtype=np.int64), out
+    finally:
+        lib().table_screen_end(t)
 
 
 class kmer_index:

@@ -1470,6 +1470,236 @@ void table_hits_end(TableHits *t)
     free(t);
 }
 
+/* ------------------------------------------------------------------ the rows of a table that pass a screen: table_screen */
+
+_Static_assert(sizeof(Dna *) == sizeof(uint64_t), "agg_grow sizes the array of rows");
+
+struct TableScreen {
+    dnagpu_acc *set;                             /* the aggregate's accumulator (the aggregate outlives this object) */
+    unsigned flags;
+    uint64_t min_count, max_count, min_hits, max_hits, frac_num, frac_den;
+    bool started, failed;
+    uint64_t *words, n_bases, cap_words;         /* the open batch, packed as table_hits_add packs its batches */
+    uint64_t *starts, n_seqs, cap_seqs;
+    uint64_t n_added;                            /* rows of the batches screened so far = the ordinal of the open batch's first row */
+    uint64_t *seq, *rows, *hits, cap_seq, cap_rows, cap_hits;     /* the passing rows of the batches screened so far ... */
+    Dna **out;                                   /* ... and the rows themselves (NULL once handed out) */
+    uint64_t cap_out, n_pass, next;
+};
+
+TableScreen *table_screen_begin(CountKmersAgg *set, bool canonical, int64_t min_count, int64_t max_count, int64_t min_hits,
+                                int64_t max_hits, int64_t frac_num, int64_t frac_den)
+{
+    if (!set) {
+        ereport_error("table_screen: the aggregate is missing");
+        return NULL;
+    }
+    if (frac_den <= 0) {
+        ereport_error("table_screen: the fraction's denominator must be positive");
+        return NULL;
+    }
+    if (frac_den > (int64_t)UINT32_MAX || frac_num > (int64_t)UINT32_MAX) {
+        ereport_error("table_screen: the terms of the fraction must be below 2^32");
+        return NULL;
+    }
+    dnagpu_acc *acc = agg_flushed_acc(set, "table_screen");
+    if (!acc)
+        return NULL;
+    TableScreen *t = (TableScreen *)calloc(1, sizeof *t);
+    if (!t) {
+        ereport_error("out of memory");
+        return NULL;
+    }
+    t->set = acc;
+    t->flags = canonical ? DNAGPU_HITS_CANONICAL : 0u;
+    t->min_count = min_count > 0 ? (uint64_t)min_count : 1;
+    t->max_count = max_count < 0 ? UINT64_MAX : (uint64_t)max_count;
+    t->min_hits = min_hits > 0 ? (uint64_t)min_hits : 0;
+    t->max_hits = max_hits < 0 ? UINT64_MAX : (uint64_t)max_hits;
+    t->frac_num = frac_num > 0 ? (uint64_t)frac_num : 0;
+    t->frac_den = (uint64_t)frac_den;
+    return t;
+}
+
+/* bases [first, first + len) of a packed stream as a value of its own */
+static Dna *dna_cut(const uint64_t *src, uint64_t first, uint64_t len)
+{
+    const uint64_t nw = (len + 31) / 32;
+    Dna *out = (Dna *)calloc(1, sizeof(Dna));
+    uint64_t *w = (uint64_t *)calloc(nw ? nw : 1, sizeof(uint64_t));
+    if (!out || !w) {
+        free(out);
+        free(w);
+        ereport_error("out of memory");
+        return NULL;
+    }
+    for (uint64_t j = 0; j < nw; j++) {
+        const uint64_t q = first + 32 * j, nb = len - 32 * j < 32 ? len - 32 * j : 32;
+        const unsigned sh = (unsigned)(q & 31) * 2;
+        uint64_t v = src[q >> 5] >> sh;
+        if ((q & 31) + nb > 32)                                           /* (only then: the next word holds a base of the row) */
+            v |= src[(q >> 5) + 1] << (64 - sh);
+        if (nb < 32)
+            v &= ((uint64_t)1 << (2 * nb)) - 1;
+        w[j] = v;
+    }
+    out->length = len;
+    out->bit_sequence = w;
+    return out;
+}
+
+static bool ts_grow(TableScreen *t, uint64_t more)
+{
+    const uint64_t need = t->n_pass + more;
+    return agg_grow((void **)&t->seq, &t->cap_seq, need) && agg_grow((void **)&t->rows, &t->cap_rows, need) &&
+           agg_grow((void **)&t->hits, &t->cap_hits, need) && agg_grow((void **)&t->out, &t->cap_out, need);
+}
+
+/* the n_out passing rows of the open batch: their ids, rows and hits from the select's device buffers (n entries apart), the
+ * rows themselves from the taken table */
+static bool ts_collect(TableScreen *t, const dnagpu_dna *taken, const uint64_t *dev, uint64_t n, uint64_t n_out)
+{
+    if (!ts_grow(t, n_out))
+        return false;
+    const uint64_t total = dnagpu_dna_length(taken);
+    uint64_t *words = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)((total + 31) / 32 + 1));
+    uint64_t *starts = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(n_out + 1));
+    bool ok = words && starts;
+    if (!ok)
+        ereport_error("out of memory");
+    ok = ok && gpu_ok(dnagpu_buffer_download(g_ctx, dev, n_out * 8, t->seq + t->n_pass)) &&
+         gpu_ok(dnagpu_buffer_download(g_ctx, dev + n, n_out * 8, t->rows + t->n_pass)) &&
+         gpu_ok(dnagpu_buffer_download(g_ctx, dev + 2 * n, n_out * 8, t->hits + t->n_pass)) &&
+         gpu_ok(dnagpu_dna_download(g_ctx, taken, words)) && gpu_ok(dnagpu_dna_sequence_starts(g_ctx, taken, 0, n_out + 1, starts, 0));
+    for (uint64_t i = 0; ok && i < n_out; i++) {
+        Dna *row = dna_cut(words, starts[i], starts[i + 1] - starts[i]);
+        if (!row) {
+            ok = false;
+            break;
+        }
+        t->seq[t->n_pass] += t->n_added;                                  /* the ordinal of the add call */
+        t->out[t->n_pass++] = row;
+    }
+    free(words);
+    free(starts);
+    return ok;
+}
+
+/* the open batch: screened on the device, its passing rows appended, emptied */
+static bool ts_flush(TableScreen *t)
+{
+    const uint64_t n = t->n_seqs;
+    if (n == 0)
+        return true;
+    bool ok = true;
+    if (t->n_bases == 0) {                                                /* empty rows only: no row, no hit, nothing to upload */
+        if (t->min_hits == 0) {                                           /* (0 * den >= num * 0: the fraction asks nothing of them) */
+            ok = ts_grow(t, n);
+            for (uint64_t i = 0; ok && i < n; i++) {
+                Dna *row = dna_cut(t->words, 0, 0);
+                if (!row) {
+                    ok = false;
+                    break;
+                }
+                t->seq[t->n_pass] = t->n_added + i;
+                t->rows[t->n_pass] = t->hits[t->n_pass] = 0;
+                t->out[t->n_pass++] = row;
+            }
+        }
+    } else {
+        dnagpu_dna *d = NULL, *taken = NULL;
+        dnagpu_seq_hits *h = NULL;
+        void *dev = NULL;
+        uint64_t n_out = 0;
+        ok = ctx() != NULL && gpu_ok(dnagpu_dna_upload(g_ctx, t->words, t->n_bases, &d)) &&
+             gpu_ok(dnagpu_dna_set_sequences(g_ctx, d, t->starts, n)) &&
+             gpu_ok(dnagpu_table_hits(g_ctx, d, t->set, t->flags, t->min_count, t->max_count, 0, n, &h)) &&
+             gpu_ok(dnagpu_buffer_alloc(g_ctx, 3 * 8 * n, &dev));
+        uint64_t *dv = (uint64_t *)dev;
+        ok = ok && gpu_ok(dnagpu_seq_hits_select(g_ctx, h, t->min_hits, t->max_hits, t->frac_num, t->frac_den, dv, dv + n, dv + 2 * n,
+                                                 n, &n_out, 1));
+        if (ok && n_out > 0)
+            ok = gpu_ok(dnagpu_dna_take(g_ctx, d, dv, NULL, n_out, 1, &taken)) && ts_collect(t, taken, dv, n, n_out);
+        if (taken)
+            dnagpu_dna_free(g_ctx, taken);
+        if (dev)
+            dnagpu_buffer_free(g_ctx, dev);
+        if (h)
+            dnagpu_seq_hits_free(g_ctx, h);
+        if (d)
+            dnagpu_dna_free(g_ctx, d);
+    }
+    t->n_added += n;
+    t->n_bases = 0;
+    t->n_seqs = 0;
+    return ok;
+}
+
+bool table_screen_add(TableScreen *t, const Dna *row)
+{
+    if (t->started || t->failed) {
+        ereport_error("table_screen: row added after the first row was served or the scan failed");
+        return false;
+    }
+    if (t->n_seqs > 0 && t->n_bases + row->length > g_agg_flush_bases && !ts_flush(t)) {     /* a long row: a batch of its own */
+        t->failed = true;
+        return false;
+    }
+    if (!batch_append(&t->words, &t->n_bases, &t->cap_words, &t->starts, &t->n_seqs, &t->cap_seqs, row)) {
+        t->failed = true;
+        return false;
+    }
+    if (t->n_bases >= g_agg_flush_bases && !ts_flush(t)) {
+        t->failed = true;
+        return false;
+    }
+    return true;
+}
+
+bool table_screen_next(TableScreen *t, int64_t *seq, int64_t *rows, int64_t *hits, Dna **row)
+{
+    if (t->failed)
+        return false;
+    if (!t->started) {
+        t->started = true;
+        if (!ts_flush(t)) {                                               /* the last batch */
+            t->failed = true;
+            return false;
+        }
+    }
+    if (t->next >= t->n_pass)
+        return false;
+    const uint64_t i = t->next++;
+    if (seq)
+        *seq = (int64_t)t->seq[i];
+    if (rows)
+        *rows = (int64_t)t->rows[i];
+    if (hits)
+        *hits = (int64_t)t->hits[i];
+    if (row) {
+        *row = t->out[i];                                                 /* the caller's from here on */
+        t->out[i] = NULL;
+    }
+    return true;
+}
+
+bool table_screen_failed(const TableScreen *t) { return t->failed; }
+
+void table_screen_end(TableScreen *t)
+{
+    if (!t)
+        return;
+    for (uint64_t i = 0; i < t->n_pass; i++)
+        dna_free(t->out[i]);
+    free(t->words);
+    free(t->starts);
+    free(t->seq);
+    free(t->rows);
+    free(t->hits);
+    free(t->out);
+    free(t);
+}
+
 /* ------------------------------------------------------------------ the index over a stored kmer column */
 
 struct KmerIndex {

@@ -211,6 +211,29 @@ void table_hits_totals(const TableHits *t, int64_t *rows, int64_t *hits, int64_t
 bool table_hits_failed(const TableHits *t);
 void table_hits_end(TableHits *t);
 
+/* ---- SELECT d.id, d.sequence, count(*) FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS g(kmer) JOIN counts_b b
+ * ON g.kmer = b.kmer WHERE b.count BETWEEN min_count AND max_count GROUP BY d.id, d.sequence HAVING <hits / fraction>: the
+ * ROWS of a table that pass a screen against a counted set, themselves (read screening, host depletion, containment
+ * filtering) ----
+ * begin: set / canonical / min_count / max_count as table_hits_begin.  The HAVING forms are dnagpu_seq_hits_select's: a row
+ * passes with min_hits <= hits <= max_hits and hits * frac_den >= frac_num * rows; min_hits < 0 means 0, max_hits < 0 no
+ * upper bound, frac_num < 0 means 0 (0 / 1 asks nothing of the fraction; min_hits = max_hits = 0 is the depletion query).
+ * NULL + dna_glue_errmsg() for frac_den <= 0, a term of the fraction above 2^32 - 1, a NULL or failed aggregate or a GPU error.
+ * add = one call per row, in order, batched exactly as table_hits_add batches them (the aggregate's flush size; a longer row
+ * is a batch of its own).  A batch that is full is screened at once and on the device alone: dnagpu_dna_upload +
+ * dnagpu_dna_set_sequences + dnagpu_table_hits + dnagpu_seq_hits_select into device buffers + dnagpu_dna_take with those ids
+ * still on the device; then dnagpu_dna_download + dnagpu_dna_sequence_starts of the taken table and the 24 bytes (id, rows,
+ * hits) per passing row are all that comes back.  next = one passing row, in table order: seq = the 0-based ordinal of its add
+ * call, rows / hits as table_hits_next, *row = the row itself (malloc'd: dna_free it; row may be NULL); the first next
+ * screens the last batch, and add is refused from then on.  false from next = done, or an ERROR: table_screen_failed. */
+typedef struct TableScreen TableScreen;
+TableScreen *table_screen_begin(CountKmersAgg *set, bool canonical, int64_t min_count, int64_t max_count,
+                                int64_t min_hits, int64_t max_hits, int64_t frac_num, int64_t frac_den);
+bool table_screen_add(TableScreen *t, const Dna *row);
+bool table_screen_next(TableScreen *t, int64_t *seq, int64_t *rows, int64_t *hits, Dna **row);
+bool table_screen_failed(const TableScreen *t);
+void table_screen_end(TableScreen *t);
+
 /* ---- CREATE INDEX ... ON kmer_data_t USING spgist (kmer_sequence spgist_kmer_ops) and the index scans of `=`, `^@` and `@>`
  * over the stored column (dna--1.0.sql:304-314; test.sql:156-270) ----
  * create: column[i] = the kmer of heap row i; the keys go to the device once and are sorted there (dnagpu_kmer_index_build).

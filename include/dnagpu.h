@@ -38,7 +38,8 @@ extern "C" {
  * over a stored kmer column (dnagpu_kmer_index_*) and its updates (dnagpu_kmer_index_append / _delete / _next_row), the
  * join of two accumulators (dnagpu_acc_join, dnagpu_acc_partitions), the strand-neutral forms (dnagpu_dna_revcomp,
  * dnagpu_kmer_strand, dnagpu_acc_add_canonical), the per-sequence hits of a table in a counted set (dnagpu_table_hits,
- * dnagpu_seq_hits_*): additions only, so the number stays */
+ * dnagpu_seq_hits_*), sequences by id and stream segments as a new resident table (dnagpu_dna_take, dnagpu_dna_gather,
+ * dnagpu_dna_sequence_starts): additions only, so the number stays */
 #define DNAGPU_ABI_VERSION 2
 
 /* ---- status codes ------------------------------------------------------------------------
@@ -253,6 +254,42 @@ int dnagpu_generate_kmers_table(dnagpu_ctx *ctx, const dnagpu_dna *dna, int k, c
                                 uint64_t first, uint64_t count,
                                 uint64_t *out_keys, uint64_t *out_seq, uint64_t *out_pos,
                                 uint64_t cap, uint64_t *n_out, int out_on_device);
+/* ---- sequences by id, and segments of a stream, as a new resident table ("give me those reads": what follows a
+ * dnagpu_seq_hits_select, as input to the next count, hit or join) ----
+ * dnagpu_dna_gather: segment i is bases [seg_first[i], seg_first[i] + seg_len[i]) of src's stream.  Any order; segments may
+ *   overlap, repeat or be empty.  src needs no sequence set, and one it has is ignored: a segment may span boundaries.
+ *   seg_flip may be NULL (no segment is flipped); a non-zero seg_flip[i] puts the reverse complement of segment i into the
+ *   result, under dnagpu_dna_revcomp's definition: the complement is code ^ 1, base j comes from base seg_len[i] - 1 - j.
+ * dnagpu_dna_take: the same where segment i is sequence seq_ids[i] of a table made resident with dnagpu_dna_set_sequences.
+ *   Ids are global and 0-based, may repeat and come in any order; they are uint64 because that is what
+ *   dnagpu_seq_hits_select writes to out_seq -- with on_device != 0 that buffer is passed straight in.
+ * The lists are host memory, or device memory when on_device != 0 (all of them alike).
+ * Result of both: a new owned dnagpu_dna (dnagpu_dna_free).  Its stream is the segments back to back in list order,
+ *   ceil(total / 32) words, the bits behind the last base zero (dnagpu_dna_upload's rule).  It holds a resident sequence set
+ *   of n sequences (the marks and n + 1 starts): segment i is sequence i, an empty segment an empty sequence, so every entry
+ *   point that takes a resident table takes it.  n == 0 gives a valid dna of 0 bases with no set; n > 0 with a total of 0
+ *   gives 0 bases and n empty sequences.  The result does not depend on src afterwards; src, its set and its words are only
+ *   read, no word of src at or beyond its n_words is read and the result never depends on bits behind src's last base
+ *   (dnagpu_dna_wrap's rule).  The call waits for its work.
+ * Checks, in order: a NULL ctx, src / table or out, or a NULL seg_first / seg_len / seq_ids with n > 0, is
+ *   DNAGPU_ERR_BAD_ARG; take on a non-empty stream without a sequence set is DNAGPU_ERR_BAD_ARG (dnagpu_count_kmers_table's
+ *   rule); n > 2^32 - 1 is DNAGPU_ERR_TOO_LARGE; a segment that leaves the stream (seg_first > length or seg_len > length -
+ *   seg_first) or an id >= the table's sequences is DNAGPU_ERR_BAD_ARG -- found on the device, over all entries, before the
+ *   result is allocated; a total above 2^32 - 1 bases is DNAGPU_ERR_TOO_LARGE (dnagpu_dna_set_sequences' own limit for a
+ *   resident table, judged in 64 bits; callers page by id window, and windows tile); an allocation failure is
+ *   DNAGPU_ERR_OOM.  On every error *out is left as it was and nothing stays allocated.
+ * dnagpu_dna_sequence_starts: entries [first, first + count) of the n_seqs + 1 starts of dna's sequence set (a dna without a
+ *   set has 0 entries), to host memory, or to device memory when out_on_device != 0, by dnagpu_ranking_read's window rule:
+ *   first > entries or count > entries - first is DNAGPU_ERR_BAD_ARG; count == 0 is DNAGPU_OK.  A NULL ctx or dna, or a NULL
+ *   out_starts with count > 0, is DNAGPU_ERR_BAD_ARG.  Waits for the copy. */
+int dnagpu_dna_gather(dnagpu_ctx *ctx, const dnagpu_dna *src,
+                      const uint64_t *seg_first, const uint64_t *seg_len, const uint8_t *seg_flip,
+                      uint64_t n_segs, int on_device, dnagpu_dna **out);
+int dnagpu_dna_take(dnagpu_ctx *ctx, const dnagpu_dna *table,
+                    const uint64_t *seq_ids, const uint8_t *seq_flip,
+                    uint64_t n_ids, int on_device, dnagpu_dna **out);
+int dnagpu_dna_sequence_starts(dnagpu_ctx *ctx, const dnagpu_dna *dna, uint64_t first, uint64_t count,
+                               uint64_t *out_starts, int out_on_device);
 /* Same over an arbitrary array of n keys of k bases already in device memory.  dev_keys is used as
  * scratch and its contents are unspecified afterwards. */
 int dnagpu_count_keys(dnagpu_ctx *ctx, uint64_t *dev_keys, uint64_t n, int k, dnagpu_hist **out);

@@ -1,0 +1,690 @@
+"""Sequences by id and stream segments gathered into a new resident table on the device (dnagpu_dna_take, dnagpu_dna_gather,
+dnagpu_dna_sequence_starts) with the glue's table_screen on top.  CPU tests: the argument rules that need no
+device, the binding's surface, the glue's refusals, the text reference on a hand-worked list, take_math.hpp as a host program
+(plain and with sanitizers).  GPU tests: the reference is TEXT -- orc.dna_encode of the concatenated segment texts, reverse-
+complemented with str.translate where flipped, and numpy.cumsum for the starts -- and every comparison is equality.  Every GPU
+test runs twice: plainly, and with DNAGPU_DEBUG_POISON_POOL | DNAGPU_DEBUG_GUARD_POOL."""
+import ctypes as C
+import importlib
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import oracle as orc
+from __graft_entry__ import ROOT, load_package
+
+U64_MAX = 2 ** 64 - 1
+BAD_ARG, TOO_LARGE = 5, 6
+COMPLEMENT = str.maketrans("ATCG", "TAGC")
+SEED = 0x7A3 << 32
+POISON = 0x9E9E9E9E9E9E9E9E
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    return load_package()
+
+
+@pytest.fixture(scope="module")
+def g(pkg):
+    return importlib.import_module(pkg.__name__ + ".glue")
+
+
+# ------------------------------------------------------------------ the text reference
+
+def revcomp_text(t):
+    return t[::-1].translate(COMPLEMENT)
+
+
+def random_text(seed, n):
+    return "".join(np.random.default_rng(seed).choice(list("ATCG"), n)) if n else ""
+
+
+def encode(text):
+    """-> the packed words of text, exactly ceil(len / 32) of them"""
+    nw = (len(text) + 31) // 32
+    return orc.dna_encode(text)[0][:nw] if text else np.zeros(0, dtype=np.uint64)
+
+
+def encode_table(texts):
+    """-> (words, starts uint64[n + 1]) of the rows back to back"""
+    starts = np.zeros(len(texts) + 1, dtype=np.uint64)
+    starts[1:] = np.cumsum([len(t) for t in texts], dtype=np.uint64)
+    whole = "".join(texts)
+    return (encode(whole) if whole else np.zeros(1, dtype=np.uint64)), starts
+
+
+def segment_texts(text, first, length, flip=None):
+    out = [text[int(f):int(f) + int(n)] for f, n in zip(first, length)]
+    if flip is not None:
+        out = [revcomp_text(t) if fl else t for t, fl in zip(out, flip)]
+    return out
+
+
+def check_table(d, texts, what=""):
+    """d is exactly the table of texts: length, words (zero bits behind the last base: the reference's), sequences, starts"""
+    words, starts = encode_table(texts)
+    total = int(starts[-1])
+    assert d.n_bases == total, what
+    got = d.download()
+    assert len(got) == (total + 31) // 32
+    bad = np.flatnonzero(got != words[:len(got)])
+    assert not len(bad), f"{what}: word {bad[:4]} of {len(got)}: {[hex(int(x)) for x in got[bad[:4]]]} / {[hex(int(x)) for x in words[bad[:4]]]}"
+    assert d.n_sequences == len(texts), what
+    if texts:
+        assert np.array_equal(d.sequence_starts(), starts), what
+
+
+# ------------------------------------------------------------------ CPU: what needs no device
+
+def test_take_argument_rules_without_a_device(pkg):
+    L = pkg.lib()
+    out = C.c_void_p(77)
+    one = (C.c_uint64 * 1)(0)
+    assert L.dnagpu_dna_take(None, None, None, None, 0, 0, C.byref(out)) == BAD_ARG
+    assert L.dnagpu_dna_take(None, None, one, None, 1, 0, C.byref(out)) == BAD_ARG
+    assert L.dnagpu_dna_take(None, None, None, None, 0, 0, None) == BAD_ARG
+    assert L.dnagpu_dna_gather(None, None, None, None, None, 0, 0, C.byref(out)) == BAD_ARG
+    assert L.dnagpu_dna_gather(None, None, one, one, None, 1, 0, C.byref(out)) == BAD_ARG
+    assert L.dnagpu_dna_gather(None, None, None, None, None, 0, 0, None) == BAD_ARG
+    assert out.value == 77
+    assert L.dnagpu_dna_sequence_starts(None, None, 0, 0, None, 0) == BAD_ARG
+    assert L.dnagpu_dna_sequence_starts(None, None, 0, 1, one, 0) == BAD_ARG
+    assert one[0] == 0
+
+
+def test_take_binding_surface(pkg):
+    assert pkg.abi_version() == 2
+    for name in ("dna_take", "dna_take_device", "dna_gather", "dna_gather_device"):
+        assert hasattr(pkg.Context, name)
+    for name in ("sequence_starts", "sequence_starts_device"):
+        assert hasattr(pkg.Dna, name)
+
+
+def test_glue_table_screen_refuses_a_null_aggregate(g):
+    with pytest.raises(g.GlueError) as ei:
+        g.table_screen(["ATCG"], None)
+    assert "table_screen: the aggregate is missing" in str(ei.value)
+
+
+def test_the_tests_reference_on_a_hand_worked_list():
+    """a guard on the reference itself, against text written out by hand.  It runs no code of the project."""
+    text = "ATCGGA"
+    assert revcomp_text("ATCGGA") == "TCCGAT" and revcomp_text("") == ""
+    assert segment_texts(text, [1, 0, 6, 3], [3, 2, 0, 3], [0, 1, 1, 1]) == ["TCG", "AT", "", "TCC"]
+    words, starts = encode_table(["TCG", "AT", "", "TCC"])
+    assert starts.tolist() == [0, 3, 5, 5, 8]
+    # TCGATTCC with A = 00, T = 01, C = 10, G = 11, base 0 in the lowest bits
+    codes = [1, 2, 3, 0, 1, 1, 2, 2]
+    assert len(words) == 1 and int(words[0]) == sum(c << (2 * i) for i, c in enumerate(codes))
+    assert len(encode("A" * 33)) == 2 and len(encode("A" * 32)) == 1 and len(encode("")) == 0
+
+
+SANITIZERS = ["-g", "-Xarch_host", "-fsanitize=address,undefined"]
+
+
+@pytest.mark.parametrize("extra", [[], SANITIZERS], ids=["plain", "sanitizers"])
+def test_take_math_on_the_host(tmp_path, extra):
+    """take_math.hpp, host code of the header the sweep shares, as a stand-alone program (the second build with
+    AddressSanitizer and UndefinedBehaviorSanitizer on it): every output word assembled from the header's pieces against a
+    naive base-by-base gather -- lengths 0, 1, 31, 32, 33, 64, 65 at every source offset 0..63 and output offset 0..31,
+    random lists with empty, overlapping and flipped segments, a source of exactly n_words words"""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    exe = str(tmp_path / "take_math_check")
+    subprocess.check_call([hipcc, "-O1", "-std=c++17", "--offload-arch=gfx950", *extra, "-I",
+                           os.path.join(ROOT, "dna-sequences-pg-extension_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "host", "take_math_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok") and not r.stderr, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+# ------------------------------------------------------------------ GPU
+
+@pytest.fixture(scope="module")
+def ctx(pkg):
+    c = pkg.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(params=["plain", "poison"])
+def dbg(request, ctx, pkg):
+    """every GPU test once as it is and once with poisoned, guarded pool buffers; the guard bands are checked afterwards"""
+    ctx.set_debug(pkg.DEBUG_POISON_POOL | pkg.DEBUG_GUARD_POOL if request.param == "poison" else 0)
+    yield request.param
+    assert pkg.lib().dnagpu_synchronize(ctx.h) == 0
+    ctx.set_debug(0)
+
+
+_TEXT = {}
+
+
+def text_of(seed, n):
+    """a random text, made once and never modified"""
+    if (seed, n) not in _TEXT:
+        _TEXT[(seed, n)] = random_text(seed, n)
+    return _TEXT[(seed, n)]
+
+
+def resident(ctx, texts):
+    words, starts = encode_table(texts)
+    d = ctx.upload(words, int(starts[-1]))
+    d.set_sequences(starts)
+    return d
+
+
+def upload_text(ctx, text):
+    return ctx.upload(encode(text) if text else np.zeros(1, dtype=np.uint64), len(text))
+
+
+def check_gather(ctx, d, text, first, length, flip, what):
+    out = ctx.dna_gather(d, first, length, flip)
+    check_table(out, segment_texts(text, first, length, flip), what)
+    out.free()
+
+
+@pytest.mark.gpu
+def test_take_identity_and_order(ctx, dbg):
+    """70 sequences, sequence i of i bases (so an empty one is among them): all ids in order reproduce the table -- words,
+    length, starts --; reverse order, a shuffled order and every id twice are the reference's"""
+    texts = [text_of(SEED + i, i) for i in range(70)]
+    d = resident(ctx, texts)
+    ids = np.arange(70)
+    same = ctx.dna_take(d, ids)
+    check_table(same, texts, "in order")
+    assert np.array_equal(same.download(), d.download()) and np.array_equal(same.sequence_starts(), d.sequence_starts())
+    same.free()
+    for what, order in [("reversed", ids[::-1]), ("shuffled", np.random.default_rng(5).permutation(70)), ("twice", np.repeat(ids, 2)),
+                        ("twice, interleaved", np.concatenate([ids, ids]))]:
+        t = ctx.dna_take(d, order)
+        check_table(t, [texts[i] for i in order], what)
+        t.free()
+    flip = np.random.default_rng(6).integers(0, 2, 70)
+    t = ctx.dna_take(d, ids[::-1], flip)
+    check_table(t, [revcomp_text(texts[i]) if f else texts[i] for i, f in zip(ids[::-1], flip)], "reversed, some flipped")
+    t.free()
+    d.free()
+
+
+def alignment_list():
+    """for every (s, d) in 0..31 x 0..31: a filler of (d - cur) mod 32 bases (cur = the output position so far; empty when
+    that is 0), then the probe first = 64 + s, len = 45 -> (first, length, is_probe)"""
+    first, length, probe, cur = [], [], [], 0
+    for s in range(32):
+        for d in range(32):
+            fill = (d - cur) % 32
+            first += [(s * 5 + d) % 200, 64 + s]
+            length += [fill, 45]
+            probe += [0, 1]
+            cur += fill + 45
+    return np.array(first), np.array(length), np.array(probe)
+
+
+def test_the_alignment_list_holds_every_pair():
+    """a condition on test_gather_every_alignment_pair's INPUT: all 1024 pairs (source offset mod 32, output offset mod 32)
+    occur among the probes, and a filler is empty where the output already stands at d"""
+    first, length, probe = alignment_list()
+    out_at = np.concatenate([[0], np.cumsum(length)[:-1]])
+    pairs = {(int(f) % 32, int(o) % 32) for f, o, p in zip(first, out_at, probe) if p}
+    assert len(pairs) == 1024
+    assert (length[probe == 0] == 0).any() and (length[probe == 0] > 0).any() and int(first.max() + 45) <= 256
+
+
+@pytest.mark.gpu
+def test_gather_every_alignment_pair(ctx, dbg):
+    """one gather over a 256-base source whose probes cover every (source offset, output offset) pair mod 32; once more with
+    every probe flipped"""
+    text = text_of(SEED + 100, 256)
+    first, length, probe = alignment_list()
+    d = upload_text(ctx, text)
+    check_gather(ctx, d, text, first, length, None, "forward")
+    check_gather(ctx, d, text, first, length, probe, "probes flipped")
+    d.free()
+
+
+@pytest.mark.gpu
+def test_gather_many_pieces_per_word(ctx, dbg):
+    """20,000 segments of one base (32 pieces per output word), then 40,000 with every other one empty, forward and flipped"""
+    text = text_of(SEED + 101, 997)
+    rng = np.random.default_rng(101)
+    d = upload_text(ctx, text)
+    first = rng.integers(0, 997, 20_000)
+    ones = np.ones(20_000, dtype=np.int64)
+    check_gather(ctx, d, text, first, ones, None, "20000 x 1")
+    check_gather(ctx, d, text, first, ones, ones, "20000 x 1, flipped")
+    first2 = rng.integers(0, 998, 40_000)
+    len2 = np.tile([1, 0], 20_000)
+    first2[len2 == 1] = np.minimum(first2[len2 == 1], 996)
+    check_gather(ctx, d, text, first2, len2, None, "every other one empty")
+    check_gather(ctx, d, text, first2, len2, rng.integers(0, 2, 40_000), "every other one empty, some flipped")
+    d.free()
+
+
+@pytest.mark.gpu
+def test_gather_one_long_segment(ctx, dbg):
+    """70,000 bases at base 13 of a 70,100-base source: many tiles, two source words per output word throughout"""
+    text = text_of(SEED + 102, 70_100)
+    d = upload_text(ctx, text)
+    check_gather(ctx, d, text, [13], [70_000], None, "forward")
+    check_gather(ctx, d, text, [13], [70_000], [1], "flipped")
+    check_gather(ctx, d, text, [13, 0, 70_099], [70_000, 70_100, 1], [1, 0, 1], "three, the whole source among them")
+    d.free()
+
+
+def test_the_threshold_lists_sit_on_the_threshold(pkg):
+    """a condition on test_gather_at_the_tile_list_threshold's INPUT, from the constants of take_math.hpp: with segments of 32
+    bases the first tile of the sweep (1024 output words) holds exactly 1024 segments, the most its LDS form takes; with a
+    first segment of 31 bases it holds 1025"""
+    text = open(os.path.join(ROOT, "dna-sequences-pg-extension_amd", "csrc", "take_math.hpp")).read()
+    assert "TAKE_THREADS = 256;" in text and "TAKE_WORDS_PER_THREAD = 4;" in text and "TAKE_LDS_SEGS = 1024;" in text
+    tile_bases = 32 * 256 * 4
+    for first_len, in_tile in ((32, 1024), (31, 1025)):
+        starts = np.concatenate([[0], np.cumsum(threshold_lengths(first_len))])
+        assert int((starts[:-1] < tile_bases).sum()) == in_tile and int(starts[-1]) > 2 * tile_bases
+
+
+def threshold_lengths(first_len):
+    return np.array([first_len] + [32] * 2100)
+
+
+@pytest.mark.gpu
+def test_gather_at_the_tile_list_threshold(ctx, dbg):
+    """tiles of exactly 1024 segments (the most the sweep keeps in LDS) and of 1025 (read where they are), over three tiles"""
+    text = text_of(SEED + 160, 5000)
+    d = upload_text(ctx, text)
+    rng = np.random.default_rng(160)
+    for first_len in (32, 31):
+        length = threshold_lengths(first_len)
+        first = rng.integers(0, 5000 - 32, len(length))
+        check_gather(ctx, d, text, first, length, None, f"first segment of {first_len}")
+        check_gather(ctx, d, text, first, length, rng.integers(0, 2, len(length)), f"first segment of {first_len}, some flipped")
+    d.free()
+
+
+@pytest.mark.gpu
+def test_take_empties(ctx, dbg, pkg):
+    """runs of empty segments at the start, in the middle and at the end; all segments empty (0 bases, n sequences, a table
+    that counts to 0 groups); n == 0 (0 bases, no set)"""
+    text = text_of(SEED + 103, 300)
+    d = upload_text(ctx, text)
+    first = [5, 300, 0, 7, 40, 41, 42, 43, 100, 300, 299, 0]
+    length = [0, 0, 0, 33, 0, 0, 0, 0, 64, 0, 0, 0]
+    check_gather(ctx, d, text, first, length, None, "runs of empties")
+    check_gather(ctx, d, text, first, length, [1] * 12, "runs of empties, flipped")
+    check_gather(ctx, d, text, [0, 300, 150], [0, 0, 0], [0, 1, 0], "all empty")
+    e = ctx.dna_gather(d, [0, 300, 150], [0, 0, 0])
+    assert (e.n_bases, e.n_sequences) == (0, 3) and e.sequence_starts().tolist() == [0, 0, 0, 0]
+    h = ctx.count_kmers_table(e, 5)
+    assert (h.distinct, h.total) == (0, 0)
+    h.free()
+    e.free()
+    for none in (ctx.dna_gather(d, [], []), ctx.dna_gather(d, [], [], [])):
+        assert (none.n_bases, none.n_sequences) == (0, 0) and len(none.sequence_starts()) == 0
+        none.free()
+    t = resident(ctx, ["", "", "ATCG", ""])
+    none = ctx.dna_take(t, [])
+    assert (none.n_bases, none.n_sequences) == (0, 0)
+    none.free()
+    e = ctx.dna_take(t, [0, 3, 1, 1])
+    check_table(e, ["", "", "", ""], "empty sequences by id")
+    e.free()
+    t.free()
+    d.free()
+
+
+@pytest.mark.gpu
+def test_take_from_a_wrapped_view(ctx, dbg):
+    """the source is a dnagpu_dna_wrap view whose last word has ones behind its last base and poisoned words behind that: the
+    output is the reference's, its tail bits zero; a segment ends exactly at the source's last base, flipped too"""
+    n_bases = 1000 + 13
+    text = text_of(SEED + 104, n_bases)
+    words = encode(text).copy()
+    nw = len(words)
+    words[-1] |= np.uint64(U64_MAX ^ ((1 << (2 * (n_bases % 32))) - 1))
+    buf = ctx.buffer_alloc(8 * (nw + 4))
+    ctx.upload_u64(buf, np.concatenate([words, np.full(4, POISON, dtype=np.uint64)]))
+    view = ctx.wrap(buf, nw, n_bases)
+    first = [n_bases - 45, 0, n_bases - 1, n_bases - 32, n_bases - 33, n_bases, 500]
+    length = [45, n_bases, 1, 32, 33, 0, 77]
+    for flip in (None, [1] * 7, [0, 1, 0, 1, 0, 1, 0]):
+        out = ctx.dna_gather(view, first, length, flip)
+        texts = segment_texts(text, first, length, flip)
+        check_table(out, texts, f"view, flip={flip}")
+        total = sum(length)
+        assert total % 32 != 0 and int(out.download()[-1]) >> (2 * (total % 32)) == 0
+        out.free()
+    lens = [13, 0, 500, 487, 13]
+    starts = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    view.set_sequences(starts)
+    rows = [text[int(a):int(b)] for a, b in zip(starts[:-1], starts[1:])]
+    t = ctx.dna_take(view, [4, 4, 0, 3], [1, 0, 0, 1])
+    check_table(t, [revcomp_text(rows[4]), rows[4], rows[0], revcomp_text(rows[3])], "take from a view")
+    t.free()
+    view.free()
+    ctx.buffer_free(buf)
+
+
+# ---- the numpy reference of table_hits and select, restated from tests/test_table_hits.py
+
+def add_up(keys, counts):
+    keys = np.asarray(keys, dtype=np.uint64)
+    counts = np.asarray(counts).astype(np.uint64)
+    order = np.argsort(keys, kind="stable")
+    keys, counts = keys[order], counts[order]
+    if not len(keys):
+        return keys, counts
+    at = np.flatnonzero(np.concatenate([[True], keys[1:] != keys[:-1]]))
+    return keys[at], np.add.reduceat(counts, at).astype(np.uint64)
+
+
+def table_keys(texts, k):
+    words, starts = encode_table(texts)
+    return orc.generate_kmers_table(words, starts, k) if int(starts[-1]) else np.zeros(0, dtype=np.uint64)
+
+
+def mask_of(k):
+    return np.uint64((1 << (2 * k)) - 1)
+
+
+def rc_np(keys, k):
+    """include/dnagpu.h, dnagpu_kmer_strand: base i of rc(key) = the complement (code ^ 1) of base k - 1 - i of key"""
+    keys = np.asarray(keys, dtype=np.uint64) & mask_of(k)
+    out = np.zeros_like(keys)
+    for i in range(k):
+        out |= (((keys >> np.uint64(2 * (k - 1 - i))) & np.uint64(3)) ^ np.uint64(1)) << np.uint64(2 * i)
+    return out
+
+
+def rank_np(keys, k):
+    """the number whose order is text order under A < T < C < G: base 0 in the top field"""
+    keys = np.asarray(keys, dtype=np.uint64)
+    out = np.zeros_like(keys)
+    for i in range(k):
+        out |= ((keys >> np.uint64(2 * i)) & np.uint64(3)) << np.uint64(2 * (k - 1 - i))
+    return out
+
+
+def canonical_np(keys, k):
+    keys = np.asarray(keys, dtype=np.uint64) & mask_of(k)
+    rc = rc_np(keys, k)
+    return np.where(rank_np(keys, k) <= rank_np(rc, k), keys, rc)
+
+
+def ref_hits(texts, k, set_keys, canonical=False):
+    """(rows, hits) per sequence, uint64: set_keys ascending; canonical: every row is looked up by its canonical form"""
+    lens = np.array([len(t) for t in texts], dtype=np.int64)
+    rows = np.where(lens >= k, lens - k + 1, 0).astype(np.uint64)
+    keys = table_keys(texts, k)
+    assert len(keys) == int(rows.sum())
+    if canonical:
+        keys = canonical_np(keys, k)
+    hit = np.zeros(len(keys), dtype=bool)
+    if len(set_keys) and len(keys):
+        at = np.minimum(np.searchsorted(set_keys, keys), len(set_keys) - 1)
+        hit = set_keys[at] == keys
+    seq_of = np.repeat(np.arange(len(texts)), rows.astype(np.int64))
+    return rows, np.bincount(seq_of[hit], minlength=len(texts)).astype(np.uint64)
+
+
+def ref_select(first, rows, hits, min_hits, max_hits, num, den):
+    r, h = rows.astype(object), hits.astype(object)               # Python integers: no product can wrap
+    keep = np.array([min_hits <= b <= max_hits and b * den >= num * a for a, b in zip(r, h)], dtype=bool)
+    idx = np.flatnonzero(keep)
+    return (idx + first).astype(np.uint64), rows[idx], hits[idx]
+
+
+def source_text(seed, n, k):
+    """the sequence a set is counted from; for short k a two-letter one, so that the set is not every key there is"""
+    if k <= 8:
+        return "".join(np.random.default_rng(seed).choice(list("AT"), n))
+    return text_of(seed, n)
+
+
+def cut_table(src, lengths, seed):
+    """one text per length: cut from src, fresh random bases, or (from 64 bases on) a piece of src followed by random ones"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for i, n in enumerate(lengths):
+        fresh = "".join(rng.choice(list("ATCG"), n)) if n else ""
+        at = int(rng.integers(0, max(len(src) - n, 0) + 1))
+        if n > len(src) or i % 3 == 1:
+            out.append(fresh)
+        elif i % 3 == 0 or n < 64:
+            out.append(src[at:at + n])
+        else:
+            cut = n // 2 + int(rng.integers(0, 7))
+            out.append(src[at:at + cut] + fresh[cut:])
+        assert len(out[-1]) == n
+    return out
+
+
+def set_of(ctx, text, k, canonical=False):
+    d = upload_text(ctx, text)
+    h = ctx.count_kmers(d, k)
+    a = ctx.accumulator(k)
+    a.add(h, canonical=canonical)
+    h.free()
+    d.free()
+    return a
+
+
+def strictly_between(rows, hits):
+    assert 0 < int(hits.sum()) < int(rows.sum()), "the inputs do not test the probe: no hit, or nothing but hits"
+
+
+@pytest.mark.gpu
+def test_take_ids_and_flags_on_the_device(ctx, dbg):
+    """SeqHits.select(on_device=True) fed straight to dna_take(on_device=True) is the host-list form; first / length / flip in
+    device memory are the host form"""
+    k = 11
+    src = text_of(SEED + 105, 20_000)
+    lengths = np.random.default_rng(105).choice([0, 5, 11, 12, 40, 100, 333], 400).tolist()
+    texts = cut_table(src, lengths, SEED + 106)
+    acc = set_of(ctx, src, k)
+    d = resident(ctx, texts)
+    with ctx.table_hits(d, acc) as sh:
+        ids, _, _, n_sel = sh.select(1, U64_MAX, (1, 2))
+        assert 0 < n_sel < len(texts) and len(ids) == n_sel
+        dev = ctx.buffer_alloc(8 * len(texts))
+        assert sh.select(1, U64_MAX, (1, 2), cap=len(texts), on_device=True, out=(dev, None, None)) == n_sel
+    flip = np.random.default_rng(107).integers(0, 2, n_sel).astype(np.uint8)
+    dflip = ctx.buffer_alloc(max(n_sel, 1))
+    ctx.upload_bytes(dflip, flip)
+    for f_host, f_dev in ((None, None), (flip, dflip)):
+        want = [revcomp_text(texts[int(i)]) if f_host is not None and f_host[j] else texts[int(i)] for j, i in enumerate(ids)]
+        a = ctx.dna_take(d, (dev, n_sel), f_dev, on_device=True)
+        b = ctx.dna_take(d, ids, f_host)
+        check_table(a, want, "ids on the device")
+        check_table(b, want, "ids on the host")
+        a.free()
+        b.free()
+    first = np.random.default_rng(108).integers(0, 15_000, n_sel).astype(np.uint64)
+    length = np.random.default_rng(109).integers(0, 300, n_sel).astype(np.uint64)
+    bufs = [ctx.buffer_alloc(8 * n_sel) for _ in range(2)]
+    ctx.upload_u64(bufs[0], first)
+    ctx.upload_u64(bufs[1], length)
+    stream_text = "".join(texts)
+    assert len(stream_text) >= 15_300
+    a = ctx.dna_gather(d, (bufs[0], n_sel), bufs[1], dflip, on_device=True)
+    check_table(a, segment_texts(stream_text, first, length, flip), "gather lists on the device (segments span boundaries)")
+    a.free()
+    for p in [dev, dflip] + bufs:
+        ctx.buffer_free(p)
+    d.free()
+    acc.free()
+
+
+@pytest.mark.gpu
+def test_take_errors_leave_nothing_behind(ctx, dbg, pkg):
+    """an id equal to n_seqs first, in the middle and last; a segment with first == n_bases + 1; one with len == n_bases -
+    first + 1; take on a stream without a set; a total of exactly 2^32 bases (4096 segments, each the whole of a 2^20-base
+    source): *out is unchanged and the context holds the device memory it held before"""
+    L = pkg.lib()
+    texts = [text_of(SEED + 110 + i, n) for i, n in enumerate([10, 0, 50, 33, 7])]
+    d = resident(ctx, texts)
+    n_seqs, n_bases = len(texts), sum(len(t) for t in texts)
+    big = upload_text(ctx, text_of(SEED + 120, 1 << 20))
+    bare = upload_text(ctx, "".join(texts))
+    ctx.synchronize()
+    ctx.trim()
+    before = ctx.device_bytes()
+    out = C.c_void_p(5)
+
+    def u64s(v):
+        a = np.ascontiguousarray(v, dtype=np.uint64)
+        return a, a.ctypes.data
+
+    for ids in ([n_seqs, 0, 1, 2], [0, 1, n_seqs, 2, 3], [0, 1, 2, n_seqs], [U64_MAX], [1 << 32]):
+        a, p = u64s(ids)
+        assert L.dnagpu_dna_take(ctx.h, d.h, p, None, len(a), 0, C.byref(out)) == BAD_ARG, ids
+        assert out.value == 5
+    for first, length in ([[0, n_bases + 1], [1, 0]], [[0, 40, 3], [1, n_bases - 40 + 1, 2]], [[n_bases], [1]], [[3], [U64_MAX]],
+                          [[U64_MAX], [2]]):
+        a, pa = u64s(first)
+        b, pb = u64s(length)
+        assert L.dnagpu_dna_gather(ctx.h, d.h, pa, pb, None, len(a), 0, C.byref(out)) == BAD_ARG, (first, length)
+        assert out.value == 5
+    a, p = u64s([0])
+    assert L.dnagpu_dna_take(ctx.h, bare.h, p, None, 1, 0, C.byref(out)) == BAD_ARG          # a non-empty stream without a set
+    assert L.dnagpu_dna_take(ctx.h, d.h, None, None, 3, 0, C.byref(out)) == BAD_ARG          # a NULL list with n > 0
+    assert L.dnagpu_dna_gather(ctx.h, d.h, p, None, None, 1, 0, C.byref(out)) == BAD_ARG
+    assert L.dnagpu_dna_gather(ctx.h, d.h, None, p, None, 1, 0, C.byref(out)) == BAD_ARG
+    assert L.dnagpu_dna_take(ctx.h, d.h, p, None, 1 << 32, 0, C.byref(out)) == TOO_LARGE     # n itself, before anything is read
+    assert L.dnagpu_dna_gather(ctx.h, d.h, p, p, None, 1 << 32, 0, C.byref(out)) == TOO_LARGE
+    a, pa = u64s(np.zeros(4096))
+    b, pb = u64s(np.full(4096, 1 << 20))
+    assert L.dnagpu_dna_gather(ctx.h, big.h, pa, pb, None, 4096, 0, C.byref(out)) == TOO_LARGE
+    assert out.value == 5
+    ctx.synchronize()
+    ctx.trim()
+    assert ctx.device_bytes() == before
+    ok = ctx.dna_gather(big, np.zeros(4095), np.concatenate([np.full(4094, 0), [1 << 20]]))      # the same shape, a legal total
+    assert (ok.n_bases, ok.n_sequences) == (1 << 20, 4095)
+    ok.free()
+    for o in (d, big, bare):
+        o.free()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [5, 31])
+def test_take_composes_with_the_table_entry_points(ctx, dbg, k):
+    """count_kmers_table(take(ids)) is the oracle's count of the taken texts; table_hits(take(ids)) is the entries ids of
+    table_hits(table); with every sequence flipped, DNAGPU_HITS_CANONICAL and a set made with dnagpu_acc_add_canonical, rows
+    and hits are those of the unflipped table"""
+    src = source_text(SEED + 130, 20_000, k)
+    lengths = [0, k - 1, k, k + 1, 64, 65, 100, 333, 1000, 31, 32, 33, 2000, 7, 150] * 4
+    texts = cut_table(src, lengths, SEED + 131 + k)
+    rng = np.random.default_rng(k)
+    ids = rng.integers(0, len(texts), 45)
+    taken_texts = [texts[i] for i in ids]
+    sk = np.unique(table_keys([src], k))
+    rows, hits = ref_hits(texts, k, sk)
+    strictly_between(rows[ids], hits[ids])
+
+    d = resident(ctx, texts)
+    t = ctx.dna_take(d, ids)
+    check_table(t, taken_texts, "taken")
+    h = ctx.count_kmers_table(t, k)
+    gk, gc = add_up(*h.download())
+    keys = table_keys(taken_texts, k)
+    ok, oc = add_up(keys, np.ones(len(keys), dtype=np.uint64))
+    assert np.array_equal(gk, ok) and np.array_equal(gc, oc) and h.total == len(keys)
+    h.free()
+
+    acc = set_of(ctx, src, k)
+    with ctx.table_hits(d, acc) as whole, ctx.table_hits(t, acc) as part:
+        wr, wh = whole.read()
+        pr, ph = part.read()
+        assert np.array_equal(wr, rows) and np.array_equal(wh, hits)
+        assert np.array_equal(pr, wr[ids]) and np.array_equal(ph, wh[ids])
+    acc.free()
+
+    ck = np.unique(canonical_np(sk, k))
+    c_rows, c_hits = ref_hits(texts, k, ck, canonical=True)
+    strictly_between(c_rows, c_hits)
+    canon = set_of(ctx, src, k, canonical=True)
+    back = ctx.dna_take(d, np.arange(len(texts)), np.ones(len(texts)))
+    check_table(back, [revcomp_text(x) for x in texts], "every sequence flipped")
+    with ctx.table_hits(d, canon, canonical=True) as fwd, ctx.table_hits(back, canon, canonical=True) as rev:
+        fr, fh = fwd.read()
+        rr, rh = rev.read()
+        assert np.array_equal(fr, c_rows) and np.array_equal(fh, c_hits)
+        assert np.array_equal(rr, fr) and np.array_equal(rh, fh)
+    canon.free()
+    for o in (t, back, d):
+        o.free()
+
+
+@pytest.mark.gpu
+def test_sequence_starts_windows(ctx, dbg, pkg):
+    """the whole array, windows that tile it, count == 0, the two refused window shapes, a dna without a set, device output"""
+    L = pkg.lib()
+    texts = [text_of(SEED + 140 + i, n) for i, n in enumerate([3, 0, 0, 40, 1, 64, 0])]
+    _, starts = encode_table(texts)
+    d = resident(ctx, texts)
+    entries = len(texts) + 1
+    assert np.array_equal(d.sequence_starts(), starts)
+    got = [d.sequence_starts(f, c) for f, c in [(0, 3), (3, 0), (3, 1), (4, 4)]]
+    assert np.array_equal(np.concatenate(got), starts)
+    assert len(d.sequence_starts(entries, 0)) == 0 and np.array_equal(d.sequence_starts(5), starts[5:])
+    one = (C.c_uint64 * 9)(*([77] * 9))
+    for first, count in [(entries + 1, 0), (0, entries + 1), (entries, 1), (2, U64_MAX)]:
+        assert L.dnagpu_dna_sequence_starts(ctx.h, d.h, first, count, one, 0) == BAD_ARG
+    assert L.dnagpu_dna_sequence_starts(ctx.h, d.h, 0, 1, None, 0) == BAD_ARG
+    assert L.dnagpu_dna_sequence_starts(ctx.h, d.h, 0, 0, None, 0) == 0
+    assert list(one) == [77] * 9
+    buf = ctx.buffer_alloc(8 * 4)
+    ctx.upload_u64(buf, np.full(4, POISON, dtype=np.uint64))
+    d.sequence_starts_device(2, 3, buf)
+    assert ctx.download_u64(buf, 4).tolist() == starts[2:5].tolist() + [POISON]
+    ctx.buffer_free(buf)
+    d.free()
+    bare = upload_text(ctx, "ATCGATCG")
+    assert len(bare.sequence_starts()) == 0
+    assert L.dnagpu_dna_sequence_starts(ctx.h, bare.h, 0, 1, one, 0) == BAD_ARG
+    assert L.dnagpu_dna_sequence_starts(ctx.h, bare.h, 0, 0, one, 0) == 0
+    bare.free()
+
+
+@pytest.mark.gpu
+def test_glue_table_screen_over_batches(ctx, g, dbg):
+    """300 short rows through the glue with a flush size that makes at least five batches: exactly the rows the numpy
+    ref_select keeps come back, each equal to the row that was added, with its global ordinal, rows and hits; a threshold
+    nothing passes returns no row; a begin with frac_den == 0 fails with a message"""
+    k = 7
+    src = text_of(SEED + 150, 4_000)
+    rng = np.random.default_rng(151)
+    lengths = rng.integers(1, 60, 300).tolist()
+    lengths[5] = 400                                                      # longer than a batch: a batch of its own
+    texts = cut_table(src, lengths, SEED + 152)
+    assert sum(lengths) >= 5 * 1500
+    sk = np.unique(table_keys([src], k))
+    rows, hits = ref_hits(texts, k, sk)
+    strictly_between(rows, hits)
+    g.set_agg_flush_bases(1500)
+    try:
+        with g.count_kmers_table_agg(k, [src]) as agg:
+            for lo, hi, num, den in [(1, None, 1, 2), (0, 0, 0, 1), (2, 9, 0, 1), (0, None, 1, 1)]:
+                es, er, eh = ref_select(0, rows, hits, lo, U64_MAX if hi is None else hi, num, den)
+                assert 0 < len(es) < len(texts)
+                seq, gr, gh, out = g.table_screen(texts, agg, min_hits=lo, max_hits=hi, frac=(num, den))
+                assert np.array_equal(seq.astype(np.uint64), es), (lo, hi, num, den)
+                assert np.array_equal(gr.astype(np.uint64), er) and np.array_equal(gh.astype(np.uint64), eh)
+                assert [str(x) for x in out] == [texts[int(i)] for i in es]
+                assert [len(x) for x in out] == [lengths[int(i)] for i in es]
+            assert len(ref_select(0, rows, hits, 10 ** 6, U64_MAX, 0, 1)[0]) == 0
+            seq, gr, gh, out = g.table_screen(texts, agg, min_hits=10 ** 6)
+            assert len(seq) == len(gr) == len(gh) == len(out) == 0
+            for den in (0, -3):
+                with pytest.raises(g.GlueError) as ei:
+                    g.table_screen(texts, agg, frac=(1, den))
+                assert "denominator must be positive" in str(ei.value)
+            again = g.table_hits(texts, agg)                              # the aggregate is still usable afterwards
+            assert np.array_equal(again[2].astype(np.uint64), hits)
+    finally:
+        g.set_agg_flush_bases(1 << 30)
