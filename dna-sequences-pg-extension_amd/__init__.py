@@ -48,11 +48,15 @@ from .binding import (  # noqa: F401
     Multi,
     ORDER_COUNT_ASC,
     ORDER_COUNT_DESC,
+    PROFILE_CANONICAL,
+    PROFILE_MAX_K,
     Ranking,
     abi_version,
     device_count,
     kmer_count,
     lib,
     lib_path,
+    profile_geometry,
+    profile_width,
     strerror,
 )

@@ -37,7 +37,9 @@ JOIN_INNER = 0                        # JOIN .. ON a.kmer = b.kmer; INTERSECT
 JOIN_ANTI = 1                         # EXCEPT; NOT IN; NOT EXISTS
 JOIN_LEFT = 2                         # LEFT JOIN
 HITS_CANONICAL = 1                    # dnagpu_table_hits: probe with the canonical form of the row's key
-STRAND_REVCOMP = 0                    # dnagpu_kmer_strand: out = rc(key)
+PROFILE_CANONICAL = 1                 # dnagpu_table_profile: count every row under its canonical form
+PROFILE_MAX_K = 6
+STRAND_REVCOMP = 0                  # dnagpu_kmer_strand: out = rc(key)
 STRAND_CANONICAL = 1                  # ... out = whichever of key and rc(key) comes first under A < T < C < G
 SPECTRUM_MAX_BINS = 1 << 20
 TOP_MAX = 1 << 20
@@ -210,6 +212,10 @@ def lib():
                                          C.c_int]
     L.dnagpu_seq_hits_free.argtypes = [vp, vp]
     L.dnagpu_seq_hits_free.restype = None
+    L.dnagpu_profile_width.argtypes = [C.c_int]
+    L.dnagpu_profile_width.restype = C.c_uint64
+    L.dnagpu_table_profile.argtypes = [vp, vp, C.c_int, C.c_uint, C.c_uint64, C.c_uint64, vp, vp, C.c_int]
+    L.dnagpu_profile_geometry.argtypes = [u64p, u64p]
     for obj in ("hist", "acc"):
         getattr(L, f"dnagpu_{obj}_spectrum").argtypes = [vp, vp, C.c_uint64, u64p]
         getattr(L, f"dnagpu_{obj}_select").argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, u64p, C.c_int]
@@ -304,6 +310,18 @@ def device_count():
 
 def abi_version():
     return lib().dnagpu_abi_version()
+
+
+def profile_width(k):
+    """columns of a profile: 4^k for k in 1 .. 6, otherwise 0 (dnagpu_profile_width; needs no device)"""
+    return int(lib().dnagpu_profile_width(k))
+
+
+def profile_geometry():
+    """(wave_rows, tile_rows): the row limits of dnagpu_table_profile's two sequence classes"""
+    w, t = C.c_uint64(), C.c_uint64()
+    _chk(lib().dnagpu_profile_geometry(C.byref(w), C.byref(t)))
+    return w.value, t.value
 
 
 def kmer_count(n_bases, k):
@@ -1158,6 +1176,25 @@ class Context:
         _chk(lib().dnagpu_table_hits(self.h, dna.h, acc.h, HITS_CANONICAL if canonical else 0, min_count, max_count, seq_first,
                                      seq_count, C.byref(out)))
         return SeqHits(self, out)
+
+    def table_profile(self, dna, k, canonical=False, seq_first=0, seq_count=None, out_counts_dev=None, out_rows_dev=None):
+        """the k-mer profile of every sequence of [seq_first, seq_first + seq_count) of the resident table dna (seq_count=None:
+        all from seq_first on), k <= 6 -> (counts uint32[n, 4^k], rows uint64[n]): counts[i, key] = the rows of sequence
+        seq_first + i whose key is `key` (canonical: under their canonical form).  With out_counts_dev (device memory of
+        n * 4^k uint32, 4-byte aligned) the result is written there instead, the rows to out_rows_dev (n uint64, or None) ->
+        None"""
+        if seq_count is None:
+            seq_count = dna.n_sequences - seq_first
+        flags = PROFILE_CANONICAL if canonical else 0
+        fn = lib().dnagpu_table_profile
+        if out_counts_dev is not None:
+            _chk(fn(self.h, dna.h, k, flags, seq_first, seq_count, out_counts_dev, out_rows_dev, 1))
+            return None
+        width = profile_width(k)
+        counts = np.empty((max(seq_count, 0), width), dtype=np.uint32)
+        rows = np.empty(max(seq_count, 0), dtype=np.uint64)
+        _chk(fn(self.h, dna.h, k, flags, seq_first, seq_count, counts.ctypes.data, rows.ctypes.data, 0))
+        return counts, rows
 
     def accumulator(self, k):
         """an empty k-mer accumulator on this context (dnagpu_acc_create): add histograms batch by batch, 64-bit counts"""

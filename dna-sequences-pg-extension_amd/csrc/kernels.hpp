@@ -276,6 +276,18 @@ hipError_t launch_hits_select_write(const u32 *rows, const u32 *hits, u64 n, con
                                     u64 seq_first, u64 *out_seq, u64 *out_rows, u64 *out_hits, u64 cap, hipStream_t s);
 hipError_t launch_hits_widen(const u32 *in, u64 *out, u64 n, hipStream_t s);
 
+// ---- the k-mer profile of every sequence of a window of a table (profile_kernels.hip; classes and items are
+// profile_math.hpp's).  starts = seq_starts + seq_first (seq_count + 1 entries), k in 1 .. 6, out = seq_count rows of 4^k u32.
+// plan: out_rows[i] (may be null) = the rows of sequence i, items[i] = its item count (0: the wave class)
+hipError_t launch_profile_plan(const u64 *starts, u64 seq_count, int k, u64 *out_rows, u32 *items, hipStream_t s);
+// wave: writes every cell of every row of out -- the profile of a wave-class sequence, zeros for a tiled one
+hipError_t launch_profile_wave(const u64 *words, u64 n_words, const u64 *starts, u64 seq_count, int k, int canonical, u32 *out,
+                               hipStream_t s);
+// tile (behind wave on the same stream): off = the exclusive scan of items[], n_items = its total; adds the counts of every
+// item into its sequence's row
+hipError_t launch_profile_tile(const u64 *words, u64 n_words, const u64 *starts, u64 seq_count, const u32 *off, u32 n_items, int k,
+                               int canonical, u32 *out, hipStream_t s);
+
 // ---- the gather of segments of a packed stream into a new one (take_kernels.hip; the piece arithmetic is
 // take_math.hpp's).  segments: the list of n entries built and validated in one pass -- ids != nullptr: entry i is sequence
 // ids[i] of the table (seq_starts, n_seqs), its first base goes to seg_first[i]; else entry i is (in_first[i], in_len[i]) of

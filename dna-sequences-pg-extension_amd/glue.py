@@ -139,6 +139,18 @@ def lib():
         L.table_hits_failed.argtypes = [vp]
         L.table_hits_end.restype = None
         L.table_hits_end.argtypes = [vp]
+        L.table_profile_begin.restype = vp
+        L.table_profile_begin.argtypes = [C.c_int, C.c_bool]
+        L.table_profile_add.restype = C.c_bool
+        L.table_profile_add.argtypes = [vp, vp]
+        L.table_profile_next.restype = C.c_bool
+        L.table_profile_next.argtypes = [vp] + [C.POINTER(C.c_int64)] * 3
+        L.table_profile_width.restype = C.c_int64
+        L.table_profile_width.argtypes = [vp]
+        L.table_profile_failed.restype = C.c_bool
+        L.table_profile_failed.argtypes = [vp]
+        L.table_profile_end.restype = None
+        L.table_profile_end.argtypes = [vp]
         L.table_screen_begin.restype = vp
         L.table_screen_begin.argtypes = [vp, C.c_bool] + [C.c_int64] * 6
         L.table_screen_add.restype = C.c_bool
@@ -552,6 +564,37 @@ def table_hits(rows, set_agg, canonical=False, min_count=1, max_count=None):
                 tuple(x.value for x in tot))
     finally:
         lib().table_hits_end(t)
+
+
+def table_profile(rows, k, canonical=False):
+    """SELECT <row ordinal>, k.kmer, count(*) FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS k(kmer) GROUP BY
+    1, 2 as a dense profile, k <= 6: rows = the table's `dna` values (or their text).  A generator of (seq, rows, counts
+    int64[4^k]) in table order; counts[key] = the row's k-mers of that key (canonical: under their canonical form).  A bad k
+    raises before the first row is taken."""
+    import numpy as np
+    t = lib().table_profile_begin(int(k), bool(canonical))
+    if not t:
+        raise _err()
+
+    def gen():
+        try:
+            for r in rows:
+                if isinstance(r, str):
+                    r = dna(r)
+                if not lib().table_profile_add(t, r.p):
+                    raise _err()
+            width = lib().table_profile_width(t)
+            sq, nr = C.c_int64(), C.c_int64()
+            while True:
+                counts = np.empty(width, dtype=np.int64)
+                if not lib().table_profile_next(t, C.byref(sq), C.byref(nr), counts.ctypes.data_as(C.POINTER(C.c_int64))):
+                    break
+                yield sq.value, nr.value, counts
+            if lib().table_profile_failed(t):
+                raise _err()
+        finally:
+            lib().table_profile_end(t)
+    return gen()
 
 
 def table_screen(rows, set_agg, canonical=False, min_count=1, max_count=None, min_hits=0, max_hits=None, frac=(0, 1)):

@@ -1470,6 +1470,131 @@ void table_hits_end(TableHits *t)
     free(t);
 }
 
+/* ------------------------------------------------------------------ the k-mer profile of every row of a table: table_profile */
+
+struct TableProfile {
+    int k;
+    unsigned flags;
+    uint64_t width;                              /* 4^k */
+    bool started, failed;
+    uint64_t *words, n_bases, cap_words;         /* the open batch, packed as table_hits_add packs its batches */
+    uint64_t *starts, n_seqs, cap_seqs;
+    uint64_t *rows, n_done, cap_rows;            /* the answers of the rows of the batches profiled so far */
+    uint32_t *counts;                            /* n_done * width */
+    uint64_t cap_counts;                         /* in 8-byte units (agg_grow's) */
+    uint64_t next;
+};
+
+TableProfile *table_profile_begin(int k, bool canonical)
+{
+    if (k < 1 || k > 32) {
+        ereport_error("%s", dnagpu_strerror(DNAGPU_ERR_INVALID_K));          /* dna.c:772-773 */
+        return NULL;
+    }
+    if (k > DNAGPU_PROFILE_MAX_K) {
+        ereport_error("table_profile: a profile has 4^k columns and is offered for k <= %d", DNAGPU_PROFILE_MAX_K);
+        return NULL;
+    }
+    TableProfile *t = (TableProfile *)calloc(1, sizeof *t);
+    if (!t) {
+        ereport_error("out of memory");
+        return NULL;
+    }
+    t->k = k;
+    t->flags = canonical ? DNAGPU_PROFILE_CANONICAL : 0u;
+    t->width = dnagpu_profile_width(k);
+    return t;
+}
+
+/* the open batch: profiled on the device, its answers appended, emptied */
+static bool tp_flush(TableProfile *t)
+{
+    const uint64_t n = t->n_seqs;
+    if (n == 0)
+        return true;
+    if (!agg_grow((void **)&t->rows, &t->cap_rows, t->n_done + n) ||
+        !agg_grow((void **)&t->counts, &t->cap_counts, ((t->n_done + n) * t->width + 1) / 2))
+        return false;
+    uint32_t *counts = t->counts + t->n_done * t->width;
+    bool ok = true;
+    if (t->n_bases == 0) {                                                /* empty rows only: nothing to upload */
+        memset(t->rows + t->n_done, 0, (size_t)n * sizeof(uint64_t));
+        memset(counts, 0, (size_t)(n * t->width) * sizeof(uint32_t));
+    } else {
+        dnagpu_dna *d = NULL;
+        ok = ctx() != NULL && gpu_ok(dnagpu_dna_upload(g_ctx, t->words, t->n_bases, &d)) &&
+             gpu_ok(dnagpu_dna_set_sequences(g_ctx, d, t->starts, n)) &&
+             gpu_ok(dnagpu_table_profile(g_ctx, d, t->k, t->flags, 0, n, counts, t->rows + t->n_done, 0));
+        if (d)
+            dnagpu_dna_free(g_ctx, d);
+    }
+    if (ok)
+        t->n_done += n;
+    t->n_bases = 0;
+    t->n_seqs = 0;
+    return ok;
+}
+
+bool table_profile_add(TableProfile *t, const Dna *row)
+{
+    if (t->started || t->failed) {
+        ereport_error("table_profile: row added after the first row was served or the scan failed");
+        return false;
+    }
+    if (t->n_seqs > 0 && t->n_bases + row->length > g_agg_flush_bases && !tp_flush(t)) {     /* a long row: a batch of its own */
+        t->failed = true;
+        return false;
+    }
+    if (!batch_append(&t->words, &t->n_bases, &t->cap_words, &t->starts, &t->n_seqs, &t->cap_seqs, row)) {
+        t->failed = true;
+        return false;
+    }
+    if (t->n_bases >= g_agg_flush_bases && !tp_flush(t)) {
+        t->failed = true;
+        return false;
+    }
+    return true;
+}
+
+bool table_profile_next(TableProfile *t, int64_t *seq, int64_t *rows, int64_t *counts)
+{
+    if (t->failed)
+        return false;
+    if (!t->started) {
+        t->started = true;
+        if (!tp_flush(t)) {                                               /* the last batch */
+            t->failed = true;
+            return false;
+        }
+    }
+    if (t->next >= t->n_done)
+        return false;
+    const uint64_t i = t->next++;
+    if (seq)
+        *seq = (int64_t)i;
+    if (rows)
+        *rows = (int64_t)t->rows[i];
+    if (counts)
+        for (uint64_t c = 0; c < t->width; c++)
+            counts[c] = (int64_t)t->counts[i * t->width + c];
+    return true;
+}
+
+int64_t table_profile_width(const TableProfile *t) { return (int64_t)t->width; }
+
+bool table_profile_failed(const TableProfile *t) { return t->failed; }
+
+void table_profile_end(TableProfile *t)
+{
+    if (!t)
+        return;
+    free(t->words);
+    free(t->starts);
+    free(t->rows);
+    free(t->counts);
+    free(t);
+}
+
 /* ------------------------------------------------------------------ the rows of a table that pass a screen: table_screen */
 
 _Static_assert(sizeof(Dna *) == sizeof(uint64_t), "agg_grow sizes the array of rows");

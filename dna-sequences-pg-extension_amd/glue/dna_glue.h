@@ -211,6 +211,23 @@ void table_hits_totals(const TableHits *t, int64_t *rows, int64_t *hits, int64_t
 bool table_hits_failed(const TableHits *t);
 void table_hits_end(TableHits *t);
 
+/* ---- SELECT d.id, k.kmer, count(*) FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS k(kmer) GROUP BY d.id,
+ * k.kmer: the k-mer profile of every ROW of a table as 4^k counts per row, k <= 6 ----
+ * begin: NULL + dna_glue_errmsg() for a k outside 1 .. 32 (the reference's text, dna.c:772-773) and for k in 7 .. 32 (the
+ * glue's own text: a profile that wide is not offered).  canonical = count every k-mer under its canonical form.
+ * add = one call per row, in order, packed and batched exactly as table_hits_add does (the aggregate's flush size; a longer
+ * row is a batch of its own); a batch that is full is profiled at once (dnagpu_dna_upload + dnagpu_dna_set_sequences +
+ * dnagpu_table_profile).  next = one row of the answer, in table order: seq = the 0-based ordinal of the add call, rows =
+ * its generate_kmers rows, counts[key] (table_profile_width(t) = 4^k entries, the caller's array; may be NULL) = those of
+ * them whose key is `key`; the first next profiles the last batch, and add is refused from then on. */
+typedef struct TableProfile TableProfile;
+TableProfile *table_profile_begin(int k, bool canonical);
+bool table_profile_add(TableProfile *t, const Dna *row);
+bool table_profile_next(TableProfile *t, int64_t *seq, int64_t *rows, int64_t *counts);
+int64_t table_profile_width(const TableProfile *t);
+bool table_profile_failed(const TableProfile *t);
+void table_profile_end(TableProfile *t);
+
 /* ---- SELECT d.id, d.sequence, count(*) FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS g(kmer) JOIN counts_b b
  * ON g.kmer = b.kmer WHERE b.count BETWEEN min_count AND max_count GROUP BY d.id, d.sequence HAVING <hits / fraction>: the
  * ROWS of a table that pass a screen against a counted set, themselves (read screening, host depletion, containment

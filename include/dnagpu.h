@@ -39,7 +39,8 @@ extern "C" {
  * join of two accumulators (dnagpu_acc_join, dnagpu_acc_partitions), the strand-neutral forms (dnagpu_dna_revcomp,
  * dnagpu_kmer_strand, dnagpu_acc_add_canonical), the per-sequence hits of a table in a counted set (dnagpu_table_hits,
  * dnagpu_seq_hits_*), sequences by id and stream segments as a new resident table (dnagpu_dna_take, dnagpu_dna_gather,
- * dnagpu_dna_sequence_starts): additions only, so the number stays */
+ * dnagpu_dna_sequence_starts), the k-mer profile of every sequence of a table (dnagpu_table_profile): additions only, so
+ * the number stays */
 #define DNAGPU_ABI_VERSION 2
 
 /* ---- status codes ------------------------------------------------------------------------
@@ -486,6 +487,46 @@ int dnagpu_seq_hits_select(dnagpu_ctx *ctx, const dnagpu_seq_hits *h, uint64_t m
                            uint64_t frac_num, uint64_t frac_den, uint64_t *out_seq, uint64_t *out_rows, uint64_t *out_hits,
                            uint64_t cap, uint64_t *n_out, int out_on_device);
 void dnagpu_seq_hits_free(dnagpu_ctx *ctx, dnagpu_seq_hits *h);
+
+/* ---- the k-mer profile of every sequence of a table: test.sql:140-150 with d.id added to the GROUP BY,
+ *   SELECT d.id, k.kmer, count(*) FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS k(kmer)
+ *   GROUP BY d.id, k.kmer
+ * -- the tetranucleotide profile of a contig, the hexamer table of a gene, GC content at k = 1 -- as a dense matrix of
+ * W = 4^k columns per sequence, for k <= DNAGPU_PROFILE_MAX_K.
+ * dnagpu_profile_width(k) = 4^k for k in 1 .. 6, otherwise 0; it needs no device.
+ * dnagpu_table_profile
+ *   Input: a table made resident with dnagpu_dna_set_sequences, or one dnagpu_dna_take / dnagpu_dna_gather produced; a
+ *   non-empty stream without a set is DNAGPU_ERR_BAD_ARG (dnagpu_count_kmers_table's rule).  The table, its set and the
+ *   stream are only read; no word at or beyond the stream's words is read and the result never depends on bits behind the
+ *   last base (dnagpu_dna_wrap's rule).
+ *   Window: sequences [seq_first, seq_first + seq_count) under dnagpu_dna_sequence_starts' rule applied to the table's
+ *   sequences: seq_first > sequences or seq_count > sequences - seq_first is DNAGPU_ERR_BAD_ARG; seq_count == 0 is DNAGPU_OK
+ *   and writes nothing; seq_count > 2^32 - 1 is DNAGPU_ERR_TOO_LARGE.  Callers page by window, and windows tile.
+ *   Output: out_counts[(s - seq_first) * W + key] = the rows of sequence s's own generate_kmers(., k) whose key is `key`
+ *   (the library's key format: base i at bits 2i .. 2i + 1, A = 0 T = 1 C = 2 G = 3, so the column order is the `keys` order
+ *   of every other entry point); out_rows[s - seq_first] = len >= k ? len - k + 1 : 0, and may be NULL.  Every cell of
+ *   the window's matrix is written, zeros included -- the caller does not clear it -- and nothing outside it is touched.
+ *   Counts are 32-bit: a resident table holds at most 2^32 - 1 bases.  Outputs are host memory, or device memory when
+ *   out_on_device != 0 (out_counts 4-byte aligned, out_rows 8-byte aligned).  The host form stages in pool memory; a
+ *   staging buffer that cannot be had is DNAGPU_ERR_OOM.  The call waits for its work.
+ *   DNAGPU_PROFILE_CANONICAL: every row is counted under its canonical form (dnagpu_kmer_strand's, A < T < C < G); columns
+ *   that are not canonical are 0, and a k-mer that is its own reverse complement counts once per row:
+ *   canon[c] = fwd[c] + fwd[rc(c)] when c != rc(c), fwd[c] when c == rc(c).
+ *   Checks, in order: a NULL ctx or dna is DNAGPU_ERR_BAD_ARG; flags other than 0 or 1 is DNAGPU_ERR_BAD_ARG; k < 1 or
+ *   k > 32 is DNAGPU_ERR_INVALID_K; k in 7 .. 32 is DNAGPU_ERR_TOO_LARGE (wider than a dense profile offers:
+ *   dnagpu_last_error() says so); the window; the missing set; a NULL out_counts with seq_count > 0 is DNAGPU_ERR_BAD_ARG.
+ *   On any error no output byte is written.
+ * dnagpu_profile_geometry: the two limits of the kernels' sequence classes, in rows -- a sequence of at most *wave_rows
+ *   rows is counted by one wave, a longer one in items of *tile_rows rows (either pointer may be NULL; needs no device).
+ *   For tests and measurements.
+ * Out of scope: k > 6 (a sparse, sorted (id, kmer, count) result); frequencies or distances; more than one GPU. */
+#define DNAGPU_PROFILE_CANONICAL 1u
+#define DNAGPU_PROFILE_MAX_K     6
+uint64_t dnagpu_profile_width(int k);
+int dnagpu_table_profile(dnagpu_ctx *ctx, const dnagpu_dna *dna, int k, unsigned flags,
+                         uint64_t seq_first, uint64_t seq_count,
+                         uint32_t *out_counts, uint64_t *out_rows, int out_on_device);
+int dnagpu_profile_geometry(uint64_t *wave_rows, uint64_t *tile_rows);
 
 /* ---- count-ordered queries over counted groups: the reference's first counting statement is not a bare GROUP BY but
  *   SELECT k.kmer, count(*) FROM generate_kmers(...) AS k(kmer) GROUP BY k.kmer ORDER BY count(*) DESC   (test.sql:95)
