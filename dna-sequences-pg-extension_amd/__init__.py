@@ -24,6 +24,8 @@ from .binding import (  # noqa: F401
     DEBUG_SLAB0_OVERFLOW,
     DEBUG_SAMPLE1,
     DEBUG_SPEC1_OVERFLOW,
+    DEBUG_WEAK_FINGERPRINT,
+    MATCH_NONE,
     Accumulator,
     Context,
     Dna,
@@ -40,6 +42,7 @@ from .binding import (  # noqa: F401
     SPECTRUM_MAX_BINS,
     STRAND_CANONICAL,
     STRAND_REVCOMP,
+    SeqClasses,
     SeqHits,
     TOP_MAX,
     MULTI_AUTO,
@@ -58,5 +61,6 @@ from .binding import (  # noqa: F401
     lib_path,
     profile_geometry,
     profile_width,
+    seq_equal_geometry,
     strerror,
 )

@@ -33,6 +33,8 @@ DEBUG_SAMPLE1 = 512                   # level 1: regions from a sampled histogra
 DEBUG_RANK_SMALL = 1024               # rank: a class limit of 4 counts and sort chunks of 2048 rows (the tail path at small sizes)
 DEBUG_JOIN_PARTITION = 2048           # dnagpu_acc_join: the partition path for any sizes
 DEBUG_JOIN_DIRECT = 4096              # dnagpu_acc_join: the direct path for any sizes
+DEBUG_WEAK_FINGERPRINT = 8192         # equal sequences: 2-bit fingerprints (several verify rounds, run walks in the match)
+MATCH_NONE = (1 << 64) - 1            # dnagpu_table_match: no sequence of the built table equals this one
 JOIN_INNER = 0                        # JOIN .. ON a.kmer = b.kmer; INTERSECT
 JOIN_ANTI = 1                         # EXCEPT; NOT IN; NOT EXISTS
 JOIN_LEFT = 2                         # LEFT JOIN
@@ -216,6 +218,20 @@ def lib():
     L.dnagpu_profile_width.restype = C.c_uint64
     L.dnagpu_table_profile.argtypes = [vp, vp, C.c_int, C.c_uint, C.c_uint64, C.c_uint64, vp, vp, C.c_int]
     L.dnagpu_profile_geometry.argtypes = [u64p, u64p]
+    L.dnagpu_dna_equals.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]
+    L.dnagpu_table_classes.argtypes = [vp, vp, C.POINTER(vp)]
+    for f in ("sequences", "distinct"):
+        getattr(L, f"dnagpu_seq_classes_{f}").argtypes = [vp]
+        getattr(L, f"dnagpu_seq_classes_{f}").restype = C.c_uint64
+    L.dnagpu_seq_classes_rounds.argtypes = [vp]
+    L.dnagpu_seq_classes_rounds.restype = C.c_uint32
+    L.dnagpu_seq_classes_read.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_int]
+    L.dnagpu_seq_classes_select.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, u64p, C.c_int]
+    L.dnagpu_seq_classes_members.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, C.c_int]
+    L.dnagpu_table_match.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, vp, vp, u64p, C.c_int]
+    L.dnagpu_seq_classes_free.argtypes = [vp, vp]
+    L.dnagpu_seq_classes_free.restype = None
+    L.dnagpu_seq_equal_geometry.argtypes = [u64p, u64p]
     for obj in ("hist", "acc"):
         getattr(L, f"dnagpu_{obj}_spectrum").argtypes = [vp, vp, C.c_uint64, u64p]
         getattr(L, f"dnagpu_{obj}_select").argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, u64p, C.c_int]
@@ -321,6 +337,13 @@ def profile_geometry():
     """(wave_rows, tile_rows): the row limits of dnagpu_table_profile's two sequence classes"""
     w, t = C.c_uint64(), C.c_uint64()
     _chk(lib().dnagpu_profile_geometry(C.byref(w), C.byref(t)))
+    return w.value, t.value
+
+
+def seq_equal_geometry():
+    """(wave_bases, tile_bases): the base limits of the two sequence classes of the equality kernels"""
+    w, t = C.c_uint64(), C.c_uint64()
+    _chk(lib().dnagpu_seq_equal_geometry(C.byref(w), C.byref(t)))
     return w.value, t.value
 
 
@@ -559,6 +582,106 @@ class SeqHits:
                 self.ctx.synchronize()          # raises if a kernel wrote past the end of a work buffer
             lib().dnagpu_seq_hits_free(self.ctx.h, self.h)
             self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
+class SeqClasses:
+    """dnagpu_seq_classes: the classes of equal sequences of a resident table (Context.table_classes).  It borrows the table:
+    keep the Dna alive and its sequence set unchanged until free()"""
+
+    def __init__(self, ctx, handle, table):
+        self.ctx, self.h, self.table = ctx, handle, table
+
+    @property
+    def sequences(self):
+        return int(lib().dnagpu_seq_classes_sequences(self.h))
+
+    @property
+    def distinct(self):
+        return int(lib().dnagpu_seq_classes_distinct(self.h))
+
+    @property
+    def rounds(self):
+        return int(lib().dnagpu_seq_classes_rounds(self.h))
+
+    def read(self, first=0, count=None, on_device=False, out=None):
+        """entries [first, first + count) (count=None: all from first on) -> (rep, copies) as uint64: the smallest id of the
+        sequence's class and the class's size.  on_device: into out=(dev_rep, dev_copies) of count uint64 each (either may be
+        None) -> count"""
+        if count is None:
+            count = self.sequences - first
+        fn = lib().dnagpu_seq_classes_read
+        if on_device:
+            _chk(fn(self.ctx.h, self.h, first, count, out[0], out[1], 1))
+            return count
+        rep = np.empty(max(count, 1), dtype=np.uint64)
+        copies = np.empty(max(count, 1), dtype=np.uint64)
+        _chk(fn(self.ctx.h, self.h, first, count, rep.ctypes.data, copies.ctypes.data, 0))
+        return rep[:count], copies[:count]
+
+    def select(self, min_copies=1, max_copies=U64_MAX, cap=None, on_device=False, out=None, want=(True, True)):
+        """the representatives with min_copies <= copies <= max_copies in ascending id (GROUP BY sequence: min(id), count(*),
+        HAVING).  host: -> (seq, copies, n_matches): at most cap rows (cap=None: all of them -- two calls); an array `want`
+        turns off comes back as None.  on_device: into out=(dev_seq, dev_copies) of cap uint64 each (either may be None) ->
+        n_matches; dev_seq goes straight into Context.dna_take_device"""
+        n = C.c_uint64()
+        fn = lib().dnagpu_seq_classes_select
+        if cap is None:
+            _chk(fn(self.ctx.h, self.h, min_copies, max_copies, None, None, 0, C.byref(n), 0))
+            cap = n.value
+        if on_device:
+            _chk(fn(self.ctx.h, self.h, min_copies, max_copies, out[0], out[1], cap, C.byref(n), 1))
+            return n.value
+        arrs = [np.empty(max(cap, 1), dtype=np.uint64) if w else None for w in want]
+        ptrs = [a.ctypes.data if a is not None else None for a in arrs]
+        _chk(fn(self.ctx.h, self.h, min_copies, max_copies, ptrs[0], ptrs[1], cap, C.byref(n), 0))
+        m = min(n.value, cap)
+        return tuple(a[:m] if a is not None else None for a in arrs) + (n.value,)
+
+    def members(self, seq, cap=None, on_device=False, out=None):
+        """the ids of every sequence equal to sequence seq, seq included, ascending -> (ids, n_matches); on_device: into
+        out = dev_seq of cap uint64 -> n_matches"""
+        n = C.c_uint64()
+        fn = lib().dnagpu_seq_classes_members
+        if cap is None:
+            _chk(fn(self.ctx.h, self.h, seq, None, 0, C.byref(n), 0))
+            cap = n.value
+        if on_device:
+            _chk(fn(self.ctx.h, self.h, seq, out, cap, C.byref(n), 1))
+            return n.value
+        ids = np.empty(max(cap, 1), dtype=np.uint64)
+        _chk(fn(self.ctx.h, self.h, seq, ids.ctypes.data, cap, C.byref(n), 0))
+        return ids[:min(n.value, cap)], n.value
+
+    def match(self, probe, seq_first=0, seq_count=None, on_device=False, out=None):
+        """the join of the resident table probe to this one: for every sequence of [seq_first, seq_first + seq_count) of probe
+        (seq_count=None: all from seq_first on) the smallest id here of a sequence equal to it (MATCH_NONE: none) and that
+        class's size (0) -> (match, copies, n_matched).  on_device: into out=(dev_match, dev_copies) of seq_count uint64 each
+        (either may be None) -> n_matched"""
+        if seq_count is None:
+            seq_count = probe.n_sequences - seq_first
+        n = C.c_uint64()
+        fn = lib().dnagpu_table_match
+        if on_device:
+            _chk(fn(self.ctx.h, self.h, probe.h, seq_first, seq_count, out[0], out[1], C.byref(n), 1))
+            return n.value
+        match = np.empty(max(seq_count, 1), dtype=np.uint64)
+        copies = np.empty(max(seq_count, 1), dtype=np.uint64)
+        _chk(fn(self.ctx.h, self.h, probe.h, seq_first, seq_count, match.ctypes.data, copies.ctypes.data, C.byref(n), 0))
+        return match[:seq_count], copies[:seq_count], n.value
+
+    def free(self):
+        if self.h:
+            if self.ctx._base_debug & DEBUG_GUARD_POOL:
+                self.ctx.synchronize()          # raises if a kernel wrote past the end of a work buffer
+            lib().dnagpu_seq_classes_free(self.ctx.h, self.h)
+            self.h = None
+            self.table = None
 
     def __enter__(self):
         return self
@@ -1195,6 +1318,18 @@ class Context:
         rows = np.empty(max(seq_count, 0), dtype=np.uint64)
         _chk(fn(self.h, dna.h, k, flags, seq_first, seq_count, counts.ctypes.data, rows.ctypes.data, 0))
         return counts, rows
+
+    def dna_equals(self, a, b):
+        """dna = dna (dna.c:334-350) of two device-resident values: the same number of bases and every base equal -> bool"""
+        eq = C.c_int(-1)
+        _chk(lib().dnagpu_dna_equals(self.h, a.h, b.h, C.byref(eq)))
+        return bool(eq.value)
+
+    def table_classes(self, dna):
+        """the classes of equal sequences of the resident table dna -> SeqClasses (free it before dna)"""
+        out = C.c_void_p()
+        _chk(lib().dnagpu_table_classes(self.h, dna.h, C.byref(out)))
+        return SeqClasses(self, out, dna)
 
     def accumulator(self, k):
         """an empty k-mer accumulator on this context (dnagpu_acc_create): add histograms batch by batch, 64-bit counts"""

@@ -1,5 +1,5 @@
 // host_common.hpp -- what the host files of the C-ABI (dnagpu_api.hip, count_host.hip, sk_host.hip, multi_host.hip, query_host.hip,
-// filter_host.hip, index_host.hip, join_host.hip, hits_host.hip, take_host.hip, profile_host.hip) share
+// filter_host.hip, index_host.hip, join_host.hip, hits_host.hip, take_host.hip, profile_host.hip, seqeq_host.hip) share
 // (internal, like kernels.hpp): the error macros, the context / dna / histogram objects, the buffer pool, and the few
 // functions one of the files calls in another.  Declarations only, plus the templates and macros that must be visible;
 // the definitions are in dnagpu_api.hip unless a section says otherwise.
@@ -288,6 +288,17 @@ struct dnagpu_seq_hits {
     u32 *rows = nullptr;        // pool memory, n entries each (null when n == 0)
     u32 *hits = nullptr;
     u64 tot_rows = 0, tot_hits = 0, tot_seqs_hit = 0;
+};
+
+// the classes of equal sequences of a table (seqeq_host.hip).  It BORROWS the table: dnagpu_table_match compares against its bases.
+struct dnagpu_seq_classes {
+    const dnagpu_dna *table = nullptr;
+    u64 n = 0, distinct = 0;    // sequences, classes
+    u32 rounds = 0;             // verify rounds of the build
+    u32 *rep = nullptr;         // pool memory, n entries each (null when n == 0): the smallest id of s's class, its size
+    u32 *copies = nullptr;
+    u64 *sfp = nullptr;         // the (fingerprint, id) pairs sorted by fingerprint, ids ascending inside a run
+    u32 *sid = nullptr;
 };
 
 struct dnagpu_records {

@@ -304,6 +304,63 @@ hipError_t launch_take_starts(const u32 *scan, u64 n, u64 total, u64 *out_starts
 hipError_t launch_take_copy(const u64 *src, const u64 *seg_first, const uint8_t *seg_flip, const u64 *out_starts, u64 n, u64 total,
                             u64 *out, hipStream_t s);
 
+// ---- equal sequences (seqeq_kernels.hip; classes, items, realigned word and fingerprint are
+// seqeq_math.hpp's).  A table, or a window of one: starts = seq_starts + seq_first, n + 1 entries.
+struct SeqTable {
+    const u64 *words;
+    u64 n_words;
+    const u64 *starts;
+};
+// the fingerprint sweep: fp_short writes fp[i] of every short sequence and the length's part of every long one, ids[i] = i and
+// items[i] = the sequence's item count (either may be null); fp_long (off = the exclusive scan of items, n_items its total)
+// adds every item's partial sum; weaken keeps SEQEQ_WEAK_MASK of every fingerprint (DNAGPU_DEBUG_WEAK_FINGERPRINT)
+hipError_t launch_seqeq_fp_short(const SeqTable &t, u64 n, u64 *fp, u32 *ids, u32 *items, hipStream_t s);
+hipError_t launch_seqeq_fp_long(const SeqTable &t, u64 n, const u32 *off, u32 n_items, u64 *fp, hipStream_t s);
+hipError_t launch_seqeq_weaken(u64 *fp, u64 n, hipStream_t s);
+// One verify round over the fingerprint-sorted list (lfp, lid)[0 .. m), ids ascending inside a run.  head_flags: head[i] = 1
+// where a run starts; the caller scans head into run; head_slots: slot[r] = the slot of the head of run r.  verify: hidx[i]
+// = the slot of the head of entry i's run, eq[i] = 1 for the head and for an entry equal to it, items[i] = the item count of
+// a long pair of equal lengths (eq = 1 until pair_items clears it), else 0.  apply (pre = the exclusive scan of eq): equal
+// entries take the head's id as rep, copies[head id] = the run's equal entries, the n_out others move in order to
+// (out_fp, out_id).
+hipError_t launch_seqeq_head_flags(const u64 *lfp, u64 m, u32 *head, hipStream_t s);
+hipError_t launch_seqeq_head_slots(const u32 *head, const u32 *run, u64 m, u32 *slot, hipStream_t s);
+hipError_t launch_seqeq_verify(const SeqTable &t, const u32 *lid, u64 m, const u32 *head, const u32 *run, const u32 *slot, u32 *hidx,
+                               u32 *eq, u32 *items, hipStream_t s);
+// long pairs by items: pair p = sequence (ia ? ia[p] : p) of a against sequence ib[ib_slot[p]] of b, of equal lengths; off =
+// the exclusive scan of the pairs' item counts; an item that differs stores 0 into flag[p]
+hipError_t launch_seqeq_pair_items(const SeqTable &a, const u32 *ia, const SeqTable &b, const u32 *ib, const u32 *ib_slot,
+                                   u64 n_pairs, const u32 *off, u32 n_items, u32 *flag, hipStream_t s);
+hipError_t launch_seqeq_apply(const u64 *lfp, const u32 *lid, u64 m, const u32 *hidx, const u32 *eq, const u32 *pre, u32 *rep,
+                              u32 *copies, u64 *out_fp, u32 *out_id, u64 n_out, hipStream_t s);
+// copies[s] = copies[rep[s]] for every s; *distinct (zeroed by the caller) += the representatives
+hipError_t launch_seqeq_spread(const u32 *rep, u32 *copies, u64 n, u64 *distinct, hipStream_t s);
+// The match of np probe sequences (fingerprints pfp) against a built side (bt, its sorted list (sfp, sid)[0 .. nb), rep).
+// walk, first != 0: every probe walks the representatives of its fingerprint's run: match[p] = the id of the first equal
+// one or 0xFFFFFFFF, items[p] = 0; a probe that meets a long candidate of its length parks there instead: cur[p] = the slot,
+// flag[p] = 1, items[p] = the pair's item count.  The caller scans items, runs pair_items (ia = null, ib = sid, ib_slot =
+// cur) and calls walk with first == 0, which settles or moves on the parked probes only -- until no items are left.
+hipError_t launch_seqeq_match_walk(const SeqTable &pt, u64 np, const u64 *pfp, const SeqTable &bt, const u64 *sfp, const u32 *sid,
+                                   u64 nb, const u32 *rep, int first, u32 *cur, u32 *flag, u32 *items, u32 *match, hipStream_t s);
+// out_match[p] = match32[p] widened (all-ones for none; match32 == null: no probe matches), out_copies[p] = the match's class
+// size or 0 (either may be null); *n_matched (zeroed by the caller) += the probes with a match
+hipError_t launch_seqeq_match_out(const u32 *match32, const u32 *copies, u64 n, u64 *out_match, u64 *out_copies, u64 *n_matched,
+                                  hipStream_t s);
+// the stable selects, count -> tile_counts[tile] (seqeq_select_tiles(n) tiles), write (tile_offsets = their exclusive scan) ->
+// the matches in ascending id, entries from cap on not stored, either array may be null.  members == 0: the representatives
+// with lo <= copies <= hi; members != 0: every sequence whose rep is target.
+struct SeqSelect {
+    int members;
+    u32 target;
+    u64 lo, hi;
+};
+u32 seqeq_select_tiles(u64 n);
+hipError_t launch_seqeq_select_count(const u32 *rep, const u32 *copies, u64 n, const SeqSelect &q, u32 *tile_counts, hipStream_t s);
+hipError_t launch_seqeq_select_write(const u32 *rep, const u32 *copies, u64 n, const SeqSelect &q, const u32 *tile_offsets,
+                                     u64 *out_seq, u64 *out_copies, u64 cap, hipStream_t s);
+// two whole values of n_bases bases each: a word that differs stores 0 into *flag, which the caller has set non-zero
+hipError_t launch_seqeq_whole(const u64 *a, u64 a_words, const u64 *b, u64 b_words, u64 n_bases, u32 *flag, hipStream_t s);
+
 // ---- queries over counted groups (query_kernels.hip).  A group source is a histogram part (n slots of
 // keys / 32-bit counts, count 0 = padding) or the accumulator's table (n = P * ACC_SLOTS 16-byte slots, occ[p] == 0: the
 // partition is not read); both are cut into tiles of Q_TILE slots.

@@ -151,6 +151,31 @@ def lib():
         L.table_profile_failed.argtypes = [vp]
         L.table_profile_end.restype = None
         L.table_profile_end.argtypes = [vp]
+        L.dna_equals.restype = C.c_bool
+        L.dna_equals.argtypes = [vp, vp]
+        L.dna_ne.restype = C.c_bool
+        L.dna_ne.argtypes = [vp, vp]
+        L.table_distinct_begin.restype = vp
+        L.table_distinct_begin.argtypes = []
+        L.table_distinct_add.restype = C.c_bool
+        L.table_distinct_add.argtypes = [vp, vp]
+        L.table_distinct_next.restype = C.c_bool
+        L.table_distinct_next.argtypes = [vp] + [C.POINTER(C.c_int64)] * 2
+        L.table_distinct_failed.restype = C.c_bool
+        L.table_distinct_failed.argtypes = [vp]
+        L.table_distinct_end.restype = None
+        L.table_distinct_end.argtypes = [vp]
+        L.table_match_begin.restype = vp
+        L.table_match_begin.argtypes = []
+        for side in ("build", "probe"):
+            getattr(L, f"table_match_add_{side}").restype = C.c_bool
+            getattr(L, f"table_match_add_{side}").argtypes = [vp, vp]
+        L.table_match_next.restype = C.c_bool
+        L.table_match_next.argtypes = [vp] + [C.POINTER(C.c_int64)] * 3
+        L.table_match_failed.restype = C.c_bool
+        L.table_match_failed.argtypes = [vp]
+        L.table_match_end.restype = None
+        L.table_match_end.argtypes = [vp]
         L.table_screen_begin.restype = vp
         L.table_screen_begin.argtypes = [vp, C.c_bool] + [C.c_int64] * 6
         L.table_screen_add.restype = C.c_bool
@@ -595,6 +620,74 @@ def table_profile(rows, k, canonical=False):
         finally:
             lib().table_profile_end(t)
     return gen()
+
+
+def _as_dna(x):
+    return dna(x) if isinstance(x, str) else x
+
+
+def equals(a, b):                                  # dna = dna (equals, dna.c:352-367); host: a length test and a memcmp
+    a, b = _as_dna(a), _as_dna(b)
+    return bool(lib().dna_equals(a.p, b.p))
+
+
+def dna_ne(a, b):                                  # dna <> dna (dna_ne, dna.c:369-384)
+    a, b = _as_dna(a), _as_dna(b)
+    return bool(lib().dna_ne(a.p, b.p))
+
+
+def table_distinct(rows):
+    """SELECT min(<row ordinal>), count(*) FROM t GROUP BY sequence: rows = the table's `dna` values (or their text) ->
+    (seq int64[], copies int64[]): the ordinal of the first row of every distinct content, ascending, and how many rows equal
+    it.  The rows are ONE resident table: more than 2^32 - 1 bases is an ERROR."""
+    import numpy as np
+    t = lib().table_distinct_begin()
+    if not t:
+        raise _err()
+    try:
+        for r in rows:
+            r = _as_dna(r)
+            if not lib().table_distinct_add(t, r.p):
+                raise _err()
+        seq, copies = [], []
+        sq, cp = C.c_int64(), C.c_int64()
+        while lib().table_distinct_next(t, C.byref(sq), C.byref(cp)):
+            seq.append(sq.value)
+            copies.append(cp.value)
+        if lib().table_distinct_failed(t):
+            raise _err()
+        return np.array(seq, dtype=np.int64), np.array(copies, dtype=np.int64)
+    finally:
+        lib().table_distinct_end(t)
+
+
+def table_match(probe_rows, build_rows):
+    """SELECT a.id, min(b.id), count(*) FROM a JOIN b ON a.sequence = b.sequence GROUP BY a.id over row ordinals: the matched
+    probe rows only -> (probe_seq int64[], build_seq int64[], copies int64[]) in ascending probe ordinal; build_seq = the
+    first build row equal to the probe row, copies = the build rows equal to it.  Either side is ONE resident table."""
+    import numpy as np
+    t = lib().table_match_begin()
+    if not t:
+        raise _err()
+    try:
+        for r in build_rows:
+            r = _as_dna(r)
+            if not lib().table_match_add_build(t, r.p):
+                raise _err()
+        for r in probe_rows:
+            r = _as_dna(r)
+            if not lib().table_match_add_probe(t, r.p):
+                raise _err()
+        out = ([], [], [])
+        vals = [C.c_int64() for _ in range(3)]
+        while lib().table_match_next(t, *[C.byref(v) for v in vals]):
+            for o, v in zip(out, vals):
+                o.append(v.value)
+        if lib().table_match_failed(t):
+            raise _err()
+        return tuple(np.array(o, dtype=np.int64) for o in out)
+    finally:
+        lib().table_match_end(t)
 
 
 def table_screen(rows, set_agg, canonical=False, min_count=1, max_count=None, min_hits=0, max_hits=None, frac=(0, 1)):

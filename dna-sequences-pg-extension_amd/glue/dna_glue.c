@@ -1595,6 +1595,238 @@ void table_profile_end(TableProfile *t)
     free(t);
 }
 
+/* ------------------------------------------------------------------ equal rows: dna = dna, table_distinct, table_match */
+
+/* equals / dna_ne (dna_eq_internal, dna.c:334-384): two host datums are a length test and a memcmp, so these run on the host;
+ * bits behind the last base are not compared (the reference relies on zero tails) */
+bool dna_equals(const Dna *a, const Dna *b)
+{
+    if (a->length != b->length)
+        return false;
+    const uint64_t full = a->length / 32, rest = a->length % 32;
+    if (full && memcmp(a->bit_sequence, b->bit_sequence, (size_t)full * sizeof(uint64_t)) != 0)
+        return false;
+    if (rest) {
+        const uint64_t mask = ((uint64_t)1 << (2 * rest)) - 1;
+        return ((a->bit_sequence[full] ^ b->bit_sequence[full]) & mask) == 0;
+    }
+    return true;
+}
+
+bool dna_ne(const Dna *a, const Dna *b) { return !dna_equals(a, b); }
+
+#define TABLE_MAX_BASES 0xFFFFFFFFull            /* one resident table: dnagpu_dna_set_sequences' limit */
+
+/* one side of table_distinct / table_match: the rows packed back to back, ONE resident table when uploaded */
+typedef struct EqSide {
+    uint64_t *words, n_bases, cap_words;
+    uint64_t *starts, n_seqs, cap_seqs;
+    dnagpu_dna *dev;
+} EqSide;
+
+static bool eq_side_add(EqSide *s, const Dna *row, const char *who)
+{
+    if (row->length > TABLE_MAX_BASES - s->n_bases) {
+        ereport_error("%s: the rows hold more than 4294967295 bases (2^32 - 1), the limit of one resident table", who);
+        return false;
+    }
+    return batch_append(&s->words, &s->n_bases, &s->cap_words, &s->starts, &s->n_seqs, &s->cap_seqs, row);
+}
+
+/* the side as a resident table (n_seqs > 0); rows without a base make a stream of no words */
+static bool eq_side_upload(EqSide *s)
+{
+    static const uint64_t none[1] = {0};
+    return ctx() != NULL && gpu_ok(dnagpu_dna_upload(g_ctx, s->n_bases ? s->words : none, s->n_bases, &s->dev)) &&
+           gpu_ok(dnagpu_dna_set_sequences(g_ctx, s->dev, s->starts, s->n_seqs));
+}
+
+static void eq_side_free(EqSide *s)
+{
+    if (s->dev)
+        dnagpu_dna_free(g_ctx, s->dev);
+    free(s->words);
+    free(s->starts);
+    memset(s, 0, sizeof *s);
+}
+
+struct TableDistinct {
+    EqSide rows;
+    bool started, failed;
+    uint64_t *seq, *copies, n_out, next;         /* the representatives, ascending */
+};
+
+TableDistinct *table_distinct_begin(void)
+{
+    TableDistinct *t = (TableDistinct *)calloc(1, sizeof *t);
+    if (!t)
+        ereport_error("out of memory");
+    return t;
+}
+
+bool table_distinct_add(TableDistinct *t, const Dna *row)
+{
+    if (t->started || t->failed) {
+        ereport_error("table_distinct: row added after the first row was served or the scan failed");
+        return false;
+    }
+    if (!eq_side_add(&t->rows, row, "table_distinct")) {
+        t->failed = true;
+        return false;
+    }
+    return true;
+}
+
+/* the whole table: classes on the device, the representatives read back */
+static bool td_run(TableDistinct *t)
+{
+    if (t->rows.n_seqs == 0)
+        return true;
+    dnagpu_seq_classes *c = NULL;
+    uint64_t n = 0;
+    bool ok = eq_side_upload(&t->rows) && gpu_ok(dnagpu_table_classes(g_ctx, t->rows.dev, &c));
+    if (ok) {
+        n = dnagpu_seq_classes_distinct(c);
+        t->seq = (uint64_t *)malloc((size_t)(n ? n : 1) * sizeof(uint64_t));
+        t->copies = (uint64_t *)malloc((size_t)(n ? n : 1) * sizeof(uint64_t));
+        if (!t->seq || !t->copies) {
+            ereport_error("out of memory");
+            ok = false;
+        }
+    }
+    ok = ok && gpu_ok(dnagpu_seq_classes_select(g_ctx, c, 1, UINT64_MAX, t->seq, t->copies, n, &t->n_out, 0));
+    if (ok && t->n_out != n) {
+        ereport_error("table_distinct: the select returned %llu of %llu classes", (unsigned long long)t->n_out, (unsigned long long)n);
+        ok = false;
+    }
+    if (c)
+        dnagpu_seq_classes_free(g_ctx, c);
+    return ok;
+}
+
+bool table_distinct_next(TableDistinct *t, int64_t *seq, int64_t *copies)
+{
+    if (t->failed)
+        return false;
+    if (!t->started) {
+        t->started = true;
+        if (!td_run(t)) {
+            t->failed = true;
+            return false;
+        }
+    }
+    if (t->next >= t->n_out)
+        return false;
+    const uint64_t i = t->next++;
+    if (seq)
+        *seq = (int64_t)t->seq[i];
+    if (copies)
+        *copies = (int64_t)t->copies[i];
+    return true;
+}
+
+bool table_distinct_failed(const TableDistinct *t) { return t->failed; }
+
+void table_distinct_end(TableDistinct *t)
+{
+    if (!t)
+        return;
+    eq_side_free(&t->rows);
+    free(t->seq);
+    free(t->copies);
+    free(t);
+}
+
+struct TableMatch {
+    EqSide build, probe;
+    bool started, failed;
+    uint64_t *match, *copies, next;              /* one entry per probe row */
+};
+
+TableMatch *table_match_begin(void)
+{
+    TableMatch *t = (TableMatch *)calloc(1, sizeof *t);
+    if (!t)
+        ereport_error("out of memory");
+    return t;
+}
+
+static bool tm_add(TableMatch *t, EqSide *side, const Dna *row)
+{
+    if (t->started || t->failed) {
+        ereport_error("table_match: row added after the first row was served or the scan failed");
+        return false;
+    }
+    if (!eq_side_add(side, row, "table_match")) {
+        t->failed = true;
+        return false;
+    }
+    return true;
+}
+
+bool table_match_add_build(TableMatch *t, const Dna *row) { return tm_add(t, &t->build, row); }
+bool table_match_add_probe(TableMatch *t, const Dna *row) { return tm_add(t, &t->probe, row); }
+
+static bool tm_run(TableMatch *t)
+{
+    const uint64_t np = t->probe.n_seqs;
+    if (np == 0 || t->build.n_seqs == 0) {       /* nothing to ask, or nothing to find: no row */
+        t->probe.n_seqs = 0;
+        return true;
+    }
+    t->match = (uint64_t *)malloc((size_t)np * sizeof(uint64_t));
+    t->copies = (uint64_t *)malloc((size_t)np * sizeof(uint64_t));
+    if (!t->match || !t->copies) {
+        ereport_error("out of memory");
+        return false;
+    }
+    dnagpu_seq_classes *c = NULL;
+    const bool ok = eq_side_upload(&t->build) && eq_side_upload(&t->probe) &&
+                    gpu_ok(dnagpu_table_classes(g_ctx, t->build.dev, &c)) &&
+                    gpu_ok(dnagpu_table_match(g_ctx, c, t->probe.dev, 0, np, t->match, t->copies, NULL, 0));
+    if (c)
+        dnagpu_seq_classes_free(g_ctx, c);
+    return ok;
+}
+
+bool table_match_next(TableMatch *t, int64_t *probe_seq, int64_t *build_seq, int64_t *copies)
+{
+    if (t->failed)
+        return false;
+    if (!t->started) {
+        t->started = true;
+        if (!tm_run(t)) {
+            t->failed = true;
+            return false;
+        }
+    }
+    while (t->next < t->probe.n_seqs && t->match[t->next] == DNAGPU_MATCH_NONE)
+        t->next++;                               /* (an inner join: a probe row without a partner gives no row) */
+    if (t->next >= t->probe.n_seqs)
+        return false;
+    const uint64_t i = t->next++;
+    if (probe_seq)
+        *probe_seq = (int64_t)i;
+    if (build_seq)
+        *build_seq = (int64_t)t->match[i];
+    if (copies)
+        *copies = (int64_t)t->copies[i];
+    return true;
+}
+
+bool table_match_failed(const TableMatch *t) { return t->failed; }
+
+void table_match_end(TableMatch *t)
+{
+    if (!t)
+        return;
+    eq_side_free(&t->build);
+    eq_side_free(&t->probe);
+    free(t->match);
+    free(t->copies);
+    free(t);
+}
+
 /* ------------------------------------------------------------------ the rows of a table that pass a screen: table_screen */
 
 _Static_assert(sizeof(Dna *) == sizeof(uint64_t), "agg_grow sizes the array of rows");

@@ -228,6 +228,36 @@ int64_t table_profile_width(const TableProfile *t);
 bool table_profile_failed(const TableProfile *t);
 void table_profile_end(TableProfile *t);
 
+/* ---- dna = dna, dna <> dna (equals / dna_ne, dna.c:334-384; the operators of dna--1.0.sql:58-86): the same
+ * number of bases and every base equal.  Two host datums are a length test and a memcmp, so these two run on the host; the
+ * set forms below run on the device. */
+bool dna_equals(const Dna *a, const Dna *b);
+bool dna_ne(const Dna *a, const Dna *b);
+
+/* ---- SELECT min(<row ordinal>), count(*) FROM t GROUP BY sequence: the distinct ROWS of a table (dnagpu_table_classes +
+ * dnagpu_seq_classes_select).  add = one call per row, in order; all rows are ONE resident table (classes span batches), so
+ * more than 2^32 - 1 bases is an ERROR.  next = one class: seq = the ordinal of the first add call of that content, copies =
+ * the rows equal to it; classes come in ascending seq; the first next runs the device work and add is refused from then on. */
+typedef struct TableDistinct TableDistinct;
+TableDistinct *table_distinct_begin(void);
+bool table_distinct_add(TableDistinct *t, const Dna *row);
+bool table_distinct_next(TableDistinct *t, int64_t *seq, int64_t *copies);
+bool table_distinct_failed(const TableDistinct *t);
+void table_distinct_end(TableDistinct *t);
+
+/* ---- SELECT a.id, min(b.id), count(*) FROM a JOIN b ON a.sequence = b.sequence GROUP BY a.id (also WHERE sequence IN (SELECT
+ * sequence FROM b)): the join of a probe table to a built one (dnagpu_table_classes over the build rows + dnagpu_table_match).
+ * add_build / add_probe = one call per row of that side, in any interleaving; either side is ONE resident table (the 2^32 - 1
+ * bases ERROR above).  next = one MATCHED probe row, in ascending probe ordinal: build_seq = the ordinal of the first build row
+ * equal to it, copies = the build rows equal to it; a probe row without a partner gives no row. */
+typedef struct TableMatch TableMatch;
+TableMatch *table_match_begin(void);
+bool table_match_add_build(TableMatch *t, const Dna *row);
+bool table_match_add_probe(TableMatch *t, const Dna *row);
+bool table_match_next(TableMatch *t, int64_t *probe_seq, int64_t *build_seq, int64_t *copies);
+bool table_match_failed(const TableMatch *t);
+void table_match_end(TableMatch *t);
+
 /* ---- SELECT d.id, d.sequence, count(*) FROM dna_sequences d, LATERAL generate_kmers(d.sequence, k) AS g(kmer) JOIN counts_b b
  * ON g.kmer = b.kmer WHERE b.count BETWEEN min_count AND max_count GROUP BY d.id, d.sequence HAVING <hits / fraction>: the
  * ROWS of a table that pass a screen against a counted set, themselves (read screening, host depletion, containment

@@ -19,7 +19,7 @@
  * are synchronous with respect to the caller unless documented otherwise and not re-entrant.
  * Every pointer named dev_* is device memory on the context's GPU; every other pointer is host
  * memory owned by the caller.  The library never keeps a caller pointer after the call returns,
- * except dnagpu_dna_wrap (documented there).
+ * except dnagpu_dna_wrap and dnagpu_table_classes (documented there).
  */
 #ifndef DNAGPU_H
 #define DNAGPU_H
@@ -39,8 +39,8 @@ extern "C" {
  * join of two accumulators (dnagpu_acc_join, dnagpu_acc_partitions), the strand-neutral forms (dnagpu_dna_revcomp,
  * dnagpu_kmer_strand, dnagpu_acc_add_canonical), the per-sequence hits of a table in a counted set (dnagpu_table_hits,
  * dnagpu_seq_hits_*), sequences by id and stream segments as a new resident table (dnagpu_dna_take, dnagpu_dna_gather,
- * dnagpu_dna_sequence_starts), the k-mer profile of every sequence of a table (dnagpu_table_profile): additions only, so
- * the number stays */
+ * dnagpu_dna_sequence_starts), the k-mer profile of every sequence of a table (dnagpu_table_profile), equal sequences
+ * (dnagpu_dna_equals, dnagpu_table_classes, dnagpu_seq_classes_*, dnagpu_table_match): additions only, so the number stays */
 #define DNAGPU_ABI_VERSION 2
 
 /* ---- status codes ------------------------------------------------------------------------
@@ -528,6 +528,76 @@ int dnagpu_table_profile(dnagpu_ctx *ctx, const dnagpu_dna *dna, int k, unsigned
                          uint32_t *out_counts, uint64_t *out_rows, int out_on_device);
 int dnagpu_profile_geometry(uint64_t *wave_rows, uint64_t *tile_rows);
 
+/* ---- equal sequences: dna = dna, DISTINCT, the join on sequence (equals / dna_ne, dna.c:334-384; the operators =, <> and
+ * ~= of dna--1.0.sql:58-86; test.sql:1-20).  The type has no hash or btree operator class, so the reference answers
+ *   SELECT min(id), count(*) FROM t GROUP BY sequence        WHERE sequence = $1        a JOIN b ON a.sequence = b.sequence
+ * as nested loops over dna_eq_internal; here they run on the device over resident tables.
+ * Equality: two sequences are equal when they have the same number of bases and every base is equal -- dna.c:334-350 for
+ *   well-formed values.  The result never depends on bits behind a last base (dnagpu_dna_wrap's rule; the reference compares
+ *   whole words and relies on zero tails).  Two empty sequences are equal.  Length is part of the identity: A is code 00, so
+ *   ACG, ACGA and ACGAA have the same words and are three different sequences.
+ * dnagpu_dna_equals: the whole values a and b (sequence sets are ignored); *equal = 1 or 0.  Different lengths answer 0 with
+ *   no device work; a == b (the same object) is 1.  A NULL ctx, a, b or equal is DNAGPU_ERR_BAD_ARG.  No word at or beyond
+ *   either side's n_words is read.  Waits for its work.
+ * dnagpu_table_classes: partitions the sequences of a resident table (from dnagpu_dna_set_sequences, or a result of
+ *   dnagpu_dna_take / _gather) into classes of equal sequences: rep[s] = the smallest id of s's class (rep[rep[s]] == rep[s] <=
+ *   s), copies[s] = the size of s's class, dnagpu_seq_classes_distinct = the number of classes.  Exact for every input: a
+ *   64-bit content fingerprint only proposes candidates, the bases decide.  The object owns its device arrays, which come
+ *   from the context's pool (the stream rule above), and it BORROWS the table -- the second exception beside dnagpu_dna_wrap
+ *   to "the library never keeps a caller pointer": the caller keeps the dnagpu_dna alive, with its sequence set unchanged,
+ *   until dnagpu_seq_classes_free, because dnagpu_table_match verifies against the table's bases.  A table of 0 sequences
+ *   gives a valid object that holds no device memory (distinct 0, rounds 0).
+ *   Checks, in order: a NULL ctx, table or out is DNAGPU_ERR_BAD_ARG; a non-empty stream without a sequence set is
+ *   DNAGPU_ERR_BAD_ARG (dnagpu_count_kmers_table's rule); more than 2^32 - 1 sequences is DNAGPU_ERR_TOO_LARGE; an allocation
+ *   failure is DNAGPU_ERR_OOM with nothing leaked and *out left as it was.  Waits for its work.
+ * dnagpu_seq_classes_sequences / _distinct / _rounds: 0 for NULL.  _rounds = the verify rounds the build ran: 0 for an empty
+ *   table, 1 whenever no two different sequences shared a fingerprint (for tests and probes).
+ * dnagpu_seq_classes_read: entries [first, first + count) of rep and copies as uint64 (either may be NULL; host memory, or
+ *   device memory when out_on_device != 0), by dnagpu_ranking_read's window rule: first > sequences or count > sequences -
+ *   first is DNAGPU_ERR_BAD_ARG; count == 0 or both outputs NULL is DNAGPU_OK.  Waits for the copy.
+ * dnagpu_seq_classes_select: the representatives (rep[s] == s) with min_copies <= copies <= max_copies, in ASCENDING ID --
+ *   GROUP BY sequence with min(id), count(*) and HAVING: 1 .. max is DISTINCT, 2 .. max the duplicated reads, 1 .. 1 the
+ *   singletons.  min_copies == 0 means 1; min > max matches nothing (DNAGPU_OK).  *n_out = ALL matches, and when it exceeds
+ *   cap the FIRST cap of that order are written (dnagpu_seq_hits_select's rule: a caller pages on it and feeds out_seq to
+ *   dnagpu_dna_take).  Either array may be NULL.  A NULL ctx, c or n_out is DNAGPU_ERR_BAD_ARG.  Waits for its work.
+ * dnagpu_seq_classes_members: the ids of every sequence equal to sequence seq, seq included, ascending -- SELECT id FROM t
+ *   WHERE sequence = (that one) -- under the same cap rule; seq >= sequences is DNAGPU_ERR_BAD_ARG.
+ * dnagpu_table_match: the join of a probe table to a built one,
+ *     SELECT a.id, min(b.id), count(*) FROM a JOIN b ON a.sequence = b.sequence GROUP BY a.id
+ *   with a row for every a.id: for every sequence s of [seq_first, seq_first + seq_count) of probe, out_match[s - seq_first] =
+ *   the smallest id in the built table of a sequence equal to it, or DNAGPU_MATCH_NONE, and out_copies[s - seq_first] = that
+ *   class's size, or 0; *n_matched (may be NULL) = the probe sequences with a match.  A probe of one sequence is WHERE
+ *   sequence = $1; probe may be the built table itself (the result is then rep and copies); an empty built table matches
+ *   nothing.  The window follows dnagpu_table_profile's rule and windows tile; every cell of the window is written, nothing
+ *   outside it, and on any error no output byte is written.  Outputs are host memory, or device memory when out_on_device
+ *   != 0.  Checks, in order: a NULL ctx, build or probe is DNAGPU_ERR_BAD_ARG; the window (a window that leaves the probe's
+ *   sequences is DNAGPU_ERR_BAD_ARG, then seq_count > 2^32 - 1 is DNAGPU_ERR_TOO_LARGE); a probe stream without a set;
+ *   both outputs and n_matched NULL with seq_count > 0 is DNAGPU_ERR_BAD_ARG.  Waits for its work.
+ * dnagpu_seq_equal_geometry: the limits of the kernels' two sequence classes, in bases -- a sequence of at most *wave_bases
+ *   bases is fingerprinted and compared whole by a part of one wave, a longer one in items of *tile_bases bases (either
+ *   pointer may be NULL; needs no device).  For tests and measurements.
+ * Out of scope: strand-neutral equality (a read equal to its reverse complement); prefix, containment or approximate
+ *   matches; an order on dna; updating a classes object after the table changes; more than one GPU; tables past one resident
+ *   stream of 2^32 - 1 bases. */
+typedef struct dnagpu_seq_classes dnagpu_seq_classes;
+#define DNAGPU_MATCH_NONE UINT64_MAX
+int dnagpu_dna_equals(dnagpu_ctx *ctx, const dnagpu_dna *a, const dnagpu_dna *b, int *equal);
+int dnagpu_table_classes(dnagpu_ctx *ctx, const dnagpu_dna *table, dnagpu_seq_classes **out);
+uint64_t dnagpu_seq_classes_sequences(const dnagpu_seq_classes *c);
+uint64_t dnagpu_seq_classes_distinct(const dnagpu_seq_classes *c);
+uint32_t dnagpu_seq_classes_rounds(const dnagpu_seq_classes *c);
+int dnagpu_seq_classes_read(dnagpu_ctx *ctx, const dnagpu_seq_classes *c, uint64_t first, uint64_t count,
+                            uint64_t *out_rep, uint64_t *out_copies, int out_on_device);
+int dnagpu_seq_classes_select(dnagpu_ctx *ctx, const dnagpu_seq_classes *c, uint64_t min_copies, uint64_t max_copies,
+                              uint64_t *out_seq, uint64_t *out_copies, uint64_t cap, uint64_t *n_out, int out_on_device);
+int dnagpu_seq_classes_members(dnagpu_ctx *ctx, const dnagpu_seq_classes *c, uint64_t seq,
+                               uint64_t *out_seq, uint64_t cap, uint64_t *n_out, int out_on_device);
+int dnagpu_table_match(dnagpu_ctx *ctx, const dnagpu_seq_classes *build, const dnagpu_dna *probe,
+                       uint64_t seq_first, uint64_t seq_count,
+                       uint64_t *out_match, uint64_t *out_copies, uint64_t *n_matched, int out_on_device);
+void dnagpu_seq_classes_free(dnagpu_ctx *ctx, dnagpu_seq_classes *c);
+int dnagpu_seq_equal_geometry(uint64_t *wave_bases, uint64_t *tile_bases);
+
 /* ---- count-ordered queries over counted groups: the reference's first counting statement is not a bare GROUP BY but
  *   SELECT k.kmer, count(*) FROM generate_kmers(...) AS k(kmer) GROUP BY k.kmer ORDER BY count(*) DESC   (test.sql:95)
  * and its second summarises the distribution of the counts (count(*) FILTER (WHERE count = 1), test.sql:112-114) -----------
@@ -904,6 +974,10 @@ uint64_t dnagpu_kmer_index_next_row(const dnagpu_kmer_index *idx);
  * the probe that times both); the first holds when both are set. */
 #define DNAGPU_DEBUG_JOIN_PARTITION 2048u
 #define DNAGPU_DEBUG_JOIN_DIRECT 4096u
+/* DNAGPU_DEBUG_WEAK_FINGERPRINT: dnagpu_table_classes and dnagpu_table_match keep only the low 2 bits of every fingerprint, so
+ * that at small sizes different sequences share fingerprints: the several verify rounds of the build and the run walk of the
+ * match (tests).  Results are identical with and without it. */
+#define DNAGPU_DEBUG_WEAK_FINGERPRINT 8192u
 int dnagpu_set_debug(dnagpu_ctx *ctx, unsigned flags);
 
 /* ---- instrumentation ------------------------------------------------------------------------
