@@ -8,8 +8,6 @@ using namespace dnagpu;
 
 namespace {
 
-constexpr u64 U32_MAX64 = 0xFFFFFFFFull;
-
 bool has_table(const dnagpu_acc *a)
 {
     return a->distinct != 0 && a->t.pbits != 0 && a->t.table && a->t.occ;
@@ -59,22 +57,6 @@ int hits_build(dnagpu_ctx *ctx, const dnagpu_dna *dna, const dnagpu_acc *set, bo
     h->rows = rows;
     h->hits = hits;
     return DNAGPU_OK;                                // (the scratch arrays go back to the pool here)
-}
-
-// n entries of a u32 device array widened to u64 at `out` (host memory, or device memory)
-int widen_out(dnagpu_ctx *ctx, PoolScope &ps, const u32 *src, u64 n, u64 *out, int out_on_device)
-{
-    if (!out)
-        return DNAGPU_OK;
-    if (out_on_device) {
-        HIP_TRY(launch_hits_widen(src, out, n, ctx->stream));
-        return DNAGPU_OK;
-    }
-    u64 *stage = nullptr;
-    RC_TRY(ps.alloc((size_t)n, &stage));
-    HIP_TRY(launch_hits_widen(src, stage, n, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(out, stage, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    return DNAGPU_OK;
 }
 
 }  // namespace
@@ -160,31 +142,17 @@ extern "C" int dnagpu_seq_hits_select(dnagpu_ctx *ctx, const dnagpu_seq_hits *h,
     hipStream_t st = ctx->stream;
     PoolScope ps(ctx);
     const HitsPredicate p = {min_hits, max_hits, frac_num, frac_den};
-    const u32 nt = hits_select_tiles(h->n);
-    u32 *tiles = nullptr, *scan_tmp = nullptr;
-    RC_TRY(ps.alloc((size_t)nt + 1, &tiles));        // (the last word: the total)
-    RC_TRY(ps.alloc((size_t)scan_tmp_words(nt), &scan_tmp));
-    HIP_TRY(launch_hits_select_count(h->rows, h->hits, h->n, p, tiles, st));
-    HIP_TRY(launch_scan_u32(tiles, tiles, nt, scan_tmp, tiles + nt, st));
-    u32 total = 0;
-    RC_TRY(read_back(ctx, &total, tiles + nt, sizeof total));
+    u32 *tiles = nullptr, total = 0;
+    RC_TRY(select_tiles(ctx, ps, hits_select_tiles(h->n),
+                        [&](u32 *t) { return launch_hits_select_count(h->rows, h->hits, h->n, p, t, st); }, &tiles, &total));
     *n_out = total;
     const u64 n_write = std::min<u64>(total, cap);
-    u64 *outs[3] = {out_seq, out_rows, out_hits};
     if (n_write == 0 || (!out_seq && !out_rows && !out_hits))
         return DNAGPU_OK;
-    u64 *dev[3] = {out_seq, out_rows, out_hits};
-    if (!out_on_device)
-        for (int i = 0; i < 3; i++)
-            if (outs[i])
-                RC_TRY(ps.alloc((size_t)n_write, &dev[i]));
-    HIP_TRY(launch_hits_select_write(h->rows, h->hits, h->n, p, tiles, h->first, dev[0], dev[1], dev[2], n_write, st));
-    if (!out_on_device)
-        for (int i = 0; i < 3; i++)
-            if (outs[i])
-                HIP_TRY(hipMemcpyAsync(outs[i], dev[i], (size_t)n_write * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DNAGPU_OK;
+    OutCols<3> o;
+    RC_TRY(o.init(ctx, ps, {out_seq, out_rows, out_hits}, n_write, out_on_device));
+    HIP_TRY(launch_hits_select_write(h->rows, h->hits, h->n, p, tiles, h->first, o.dev(0), o.dev(1), o.dev(2), n_write, st));
+    return o.finish();
     });
 }
 

@@ -1,5 +1,5 @@
 // host_common.hpp -- what the host files of the C-ABI (dnagpu_api.hip, count_host.hip, sk_host.hip, multi_host.hip, query_host.hip,
-// filter_host.hip, index_host.hip, join_host.hip, hits_host.hip, take_host.hip, profile_host.hip, seqeq_host.hip) share
+// filter_host.hip, index_host.hip, join_host.hip, hits_host.hip, take_host.hip, profile_host.hip, seqeq_host.hip, host_steps.hip) share
 // (internal, like kernels.hpp): the error macros, the context / dna / histogram objects, the buffer pool, and the few
 // functions one of the files calls in another.  Declarations only, plus the templates and macros that must be visible;
 // the definitions are in dnagpu_api.hip unless a section says otherwise.
@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <new>
 #include <vector>
@@ -195,6 +196,100 @@ void prof_end(dnagpu_ctx *ctx);      // names[i] labels the interval [mark i, ma
 inline u64 words_for(u64 n_bases) { return (n_bases + 31) / 32; }
 // validates [first, first+count) against the row count of generate_kmers(dna, k)
 int check_range(const dnagpu_dna *dna, int k, u64 first, u64 count);
+
+// ---------------------------------------------------------------- host_steps.hip
+// The host-side steps that several features drive the same way: the LSD pair sort, the scan with its total, the count half
+// of a stable select, the hand-out of u64 columns, a caller's list as device memory.  (Hidden: steps of the host files, not
+// symbols of the library.)
+#pragma GCC visibility push(hidden)
+constexpr u64 U32_MAX64 = 0xFFFFFFFFull;
+
+// `count` entries of a caller's list as device memory: the list itself (null stays null), or a copy in pool memory of ps
+template <typename T>
+int device_list(dnagpu_ctx *ctx, PoolScope &ps, const T *list, u64 count, int on_device, const T **dev)
+{
+    *dev = list;
+    if (!list || on_device)
+        return DNAGPU_OK;
+    T *copy = nullptr;
+    RC_TRY(ps.alloc((size_t)count, &copy));
+    HIP_TRY(hipMemcpyAsync(copy, list, (size_t)count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    *dev = copy;
+    return DNAGPU_OK;
+}
+
+// The stable LSD radix sort of n >= 1 (key, value) pairs by `passes` 8-bit digits of the key, ping-pong between the caller's
+// buffer pairs (key[b], val[b]), n entries each.  src = what the first pass reads: the caller's keys (src.keys != null: no
+// pair exists yet, the first scatter forms them in pair 0), or the pairs in pair 0.  A pass whose digit takes one value
+// moves nothing and is skipped -- but the last pass runs if nothing has formed the pairs yet (a column of one key).
+// *sorted = the pair that holds the result.  One 4-byte read-back per pass; every pass is labelled `mark` unless it is null
+// (the caller has called prof_begin).  The histogram and its scratch are gone when this returns.
+int lsd_sort_pairs(dnagpu_ctx *ctx, IndexSortSrc src, u64 n, int passes, u64 *const key[2], u32 *const val[2], const char *mark,
+                   int *sorted);
+
+// arr[0 .. n) scanned in place (exclusive), the sum in arr[n] and, read back, in *total.  Waits.
+int scan_total(dnagpu_ctx *ctx, u32 *arr, u64 n, u32 *scan_tmp, u32 *total);
+
+// The count half of a stable select over nt tiles: *tiles (nt + 1 words of ps) = what count_launch(tiles) counted per tile,
+// scanned into every tile's first output slot; *total = how many are selected.  Waits.
+template <typename F>
+int select_tiles(dnagpu_ctx *ctx, PoolScope &ps, u32 nt, F &&count_launch, u32 **tiles, u32 *total)
+{
+    u32 *scan_tmp = nullptr;
+    RC_TRY(ps.alloc((size_t)nt + 1, tiles));               // (the last word: the total)
+    RC_TRY(ps.alloc((size_t)scan_tmp_words(nt), &scan_tmp));
+    HIP_TRY(count_launch(*tiles));
+    return scan_total(ctx, *tiles, nt, scan_tmp, total);
+}
+
+// n words of every device array to its `out` (null: not wanted), host memory or device memory; waits for the stream
+struct ColCopy {
+    const u64 *dev;
+    u64 *out;
+};
+int copy_cols(dnagpu_ctx *ctx, const ColCopy *cols, int n_cols, u64 n, int out_on_device);
+inline int copy_cols(dnagpu_ctx *ctx, std::initializer_list<ColCopy> cols, u64 n, int out_on_device)
+{
+    return copy_cols(ctx, cols.begin(), (int)cols.size(), n, out_on_device);
+}
+
+// N optional u64 output columns of n_write entries each: the caller's arrays (null: not wanted) in host memory, or in
+// device memory when out_on_device.  dev(i) = where a kernel writes column i: the caller's pointer, or a staging buffer of
+// ps (null stays null).  finish() copies the staged columns to the host and waits for the stream.
+template <int N>
+struct OutCols {
+    dnagpu_ctx *ctx = nullptr;
+    u64 n_write = 0;
+    u64 *out[N] = {}, *col[N] = {};
+    int on_device = 0;
+
+    int init(dnagpu_ctx *c, PoolScope &ps, std::initializer_list<u64 *> outs, u64 n, int out_on_device)
+    {
+        ctx = c;
+        n_write = n;
+        on_device = out_on_device;
+        std::copy(outs.begin(), outs.end(), out);
+        for (int i = 0; i < N; i++) {
+            col[i] = on_device ? out[i] : nullptr;
+            if (!on_device && out[i] && n)
+                RC_TRY(ps.alloc((size_t)n, &col[i]));
+        }
+        return DNAGPU_OK;
+    }
+    u64 *dev(int i) const { return col[i]; }
+    int finish(u64 n) const                                // (the first n <= n_write entries)
+    {
+        ColCopy c[N];
+        for (int i = 0; i < N; i++)
+            c[i] = ColCopy{col[i], on_device ? nullptr : out[i]};
+        return copy_cols(ctx, c, N, n, 0);
+    }
+    int finish() const { return finish(n_write); }
+};
+
+// n entries of a u32 device array widened to u64 at `out` (host memory, or device memory; null: nothing).  Queued only.
+int widen_out(dnagpu_ctx *ctx, PoolScope &ps, const u32 *src, u64 n, u64 *out, int out_on_device);
+#pragma GCC visibility pop
 
 // ---------------------------------------------------------------- filter_host.hip
 // A WHERE operator as per-position sets, with the argument checks and the reference's ERRORs of every entry point that

@@ -22,24 +22,10 @@ struct dnagpu_kmer_index {
 
 namespace {
 
-// `count` words of the caller's array as device memory: the array itself, or a copy in a buffer of `ps`
-int device_words(dnagpu_ctx *ctx, PoolScope &ps, const u64 *words, u64 count, int on_device, const u64 **out)
-{
-    *out = words;
-    if (on_device)
-        return DNAGPU_OK;
-    u64 *up = nullptr;
-    RC_TRY(ps.alloc((size_t)count, &up));
-    HIP_TRY(hipMemcpyAsync(up, words, count * 8, hipMemcpyHostToDevice, ctx->stream));
-    *out = up;
-    return DNAGPU_OK;
-}
-
-// The LSD passes over dev_keys: the n >= 1 keys in device memory (read only), key j with row id row_base + j.  *out_r /
-// *out_row = the sorted pairs, buffers of `ps`; the other buffer pair and the histogram have gone back to the pool.
-// Every pass is labelled `mark` (the caller has called prof_begin).
-int sort_pairs(dnagpu_ctx *ctx, PoolScope &ps, const u64 *dev_keys, u64 n, int k, u32 row_base, const char *mark, u64 **out_r,
-               u32 **out_row)
+// The sort of dev_keys: the n >= 1 keys in device memory (read only), key j with row id row_base + j.  *out_r / *out_row =
+// the sorted pairs, buffers of `ps`; the other buffer pair has gone back to the pool.  Every pass is labelled `mark`.
+int sort_keys(dnagpu_ctx *ctx, PoolScope &ps, const u64 *dev_keys, u64 n, int k, u32 row_base, const char *mark, u64 **out_r,
+              u32 **out_row)
 {
     u64 *r[2] = {nullptr, nullptr};
     u32 *row[2] = {nullptr, nullptr};
@@ -47,32 +33,11 @@ int sort_pairs(dnagpu_ctx *ctx, PoolScope &ps, const u64 *dev_keys, u64 n, int k
         RC_TRY(ps.alloc((size_t)n, &r[b]));
         RC_TRY(ps.alloc((size_t)n, &row[b]));
     }
-    const u64 n_hist = (u64)256 * index_sort_tiles(n);
-    u32 *hist = nullptr, *scan_tmp = nullptr, *bins_dev = nullptr;
-    RC_TRY(ps.alloc((size_t)n_hist, &hist));
-    RC_TRY(ps.alloc((size_t)scan_tmp_words(n_hist), &scan_tmp));
-    RC_TRY(ps.alloc((size_t)2, &bins_dev));              // [0]: digits that occur
     const int passes = (2 * k + 7) / 8;                  // the bits above 2k are zero: the last digit may be partial
-    IndexSortSrc src{dev_keys, nullptr, nullptr, k, row_base};
-    int cur = -1;                                        // the buffer pair that holds the pairs (-1: still the caller's keys)
-    for (int p = 0; p < passes; p++) {
-        prof_mark(ctx, mark);
-        HIP_TRY(launch_index_hist(src, n, 8 * p, hist, ctx->stream));
-        HIP_TRY(launch_scan_u32(hist, hist, n_hist, scan_tmp, nullptr, ctx->stream));
-        HIP_TRY(launch_index_digit_bins(hist, n, bins_dev, ctx->stream));
-        u32 bins = 0;
-        RC_TRY(read_back(ctx, &bins, bins_dev, 4));
-        // one digit only: the scatter would copy the tile order.  (The last pass still runs if nothing has formed the
-        // pairs yet: a column of one key.)
-        if (bins <= 1 && !(p == passes - 1 && cur < 0))
-            continue;
-        const int dst = cur == 0 ? 1 : 0;
-        HIP_TRY(launch_index_scatter(src, n, 8 * p, hist, r[dst], row[dst], ctx->stream));
-        src = IndexSortSrc{nullptr, r[dst], row[dst], k, 0};
-        cur = dst;
-    }
-    for (void *p : {(void *)r[1 - cur], (void *)row[1 - cur], (void *)hist, (void *)scan_tmp, (void *)bins_dev})
-        ps.free_now(p);
+    int cur = 0;
+    RC_TRY(lsd_sort_pairs(ctx, IndexSortSrc{dev_keys, nullptr, nullptr, k, row_base}, n, passes, r, row, mark, &cur));
+    ps.free_now(r[1 - cur]);
+    ps.free_now(row[1 - cur]);
     *out_r = r[cur];
     *out_row = row[cur];
     return DNAGPU_OK;
@@ -112,7 +77,7 @@ int build_core(dnagpu_ctx *ctx, const u64 *dev_keys, u64 n, int k, dnagpu_kmer_i
     u64 *r = nullptr, distinct = 0;
     u32 *row = nullptr;
     prof_begin(ctx);
-    RC_TRY(sort_pairs(ctx, ps, dev_keys, n, k, 0, "index_pass", &r, &row));
+    RC_TRY(sort_keys(ctx, ps, dev_keys, n, k, 0, "index_pass", &r, &row));
     prof_mark(ctx, "index_distinct");
     RC_TRY(count_distinct(ctx, ps, r, n, &distinct));
     prof_end(ctx);
@@ -128,7 +93,7 @@ int append_core(dnagpu_ctx *ctx, const u64 *dev_keys, u64 m, dnagpu_kmer_index *
     u64 *br = nullptr, *nr = nullptr, distinct = 0;
     u32 *brow = nullptr, *nrow = nullptr;
     prof_begin(ctx);
-    RC_TRY(sort_pairs(ctx, ps, dev_keys, m, idx->k, (u32)idx->next_row, "index_batch_sort", &br, &brow));
+    RC_TRY(sort_keys(ctx, ps, dev_keys, m, idx->k, (u32)idx->next_row, "index_batch_sort", &br, &brow));
     const u64 total = idx->n + m;
     if (idx->n == 0) {                                   // nothing to merge with: the sorted batch is the index
         nr = br;
@@ -156,20 +121,16 @@ int delete_core(dnagpu_ctx *ctx, const u64 *dev_ids, u64 m, dnagpu_kmer_index *i
     PoolScope ps(ctx);
     const u64 n = idx->n, words = index_bitmap_words(idx->next_row);
     const u32 nt = index_sort_tiles(n);
-    u32 *bitmap = nullptr, *tiles = nullptr, *scan_tmp = nullptr, *sum = nullptr;
+    u32 *bitmap = nullptr, *tiles = nullptr;
     RC_TRY(ps.alloc((size_t)words, &bitmap));
-    RC_TRY(ps.alloc((size_t)nt, &tiles));
-    RC_TRY(ps.alloc((size_t)scan_tmp_words(nt), &scan_tmp));
-    RC_TRY(ps.alloc((size_t)2, &sum));
     prof_begin(ctx);
     prof_mark(ctx, "index_mark");
     HIP_TRY(hipMemsetAsync(bitmap, 0, words * 4, ctx->stream));
     HIP_TRY(launch_index_mark(dev_ids, m, idx->next_row, bitmap, ctx->stream));
     prof_mark(ctx, "index_compact");
-    HIP_TRY(launch_index_compact_count(idx->row, n, bitmap, tiles, ctx->stream));
-    HIP_TRY(launch_scan_u32(tiles, tiles, nt, scan_tmp, sum, ctx->stream));
     u32 kept = 0;
-    RC_TRY(read_back(ctx, &kept, sum, 4));
+    RC_TRY(select_tiles(ctx, ps, nt, [&](u32 *t) { return launch_index_compact_count(idx->row, n, bitmap, t, ctx->stream); },
+                        &tiles, &kept));
     if (kept > n)
         return DNAGPU_ERR_INTERNAL;
     if (kept == n || kept == 0) {                        // nothing listed is in the index / nothing is left of it
@@ -208,17 +169,6 @@ FilterDev residual_of(const FilterBits &fb, int p)
     return fd;
 }
 
-// `count` device words of two arrays to the caller's (host) arrays; waits
-int copy_out(dnagpu_ctx *ctx, u64 count, const u64 *da, const u64 *db, u64 *a, u64 *b)
-{
-    if (a)
-        HIP_TRY(hipMemcpyAsync(a, da, count * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (b)
-        HIP_TRY(hipMemcpyAsync(b, db, count * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return DNAGPU_OK;
-}
-
 int scan_core(dnagpu_ctx *ctx, const dnagpu_kmer_index *idx, const FilterBits &fb, u64 *out_rows, u64 *out_keys, u64 cap,
               u64 *n_out, u64 *visited, int out_on_device)
 {
@@ -229,15 +179,15 @@ int scan_core(dnagpu_ctx *ctx, const dnagpu_kmer_index *idx, const FilterBits &f
     HIP_TRY(hipSetDevice(ctx->device));
     PoolScope ps(ctx);
     u32 *off = nullptr, *beg = nullptr;
-    u64 *small = nullptr;
+    u64 *cand = nullptr;
     RC_TRY(ps.alloc((size_t)R + 1, &off));
     RC_TRY(ps.alloc((size_t)R, &beg));
-    RC_TRY(ps.alloc((size_t)2, &small));                 // [0]: the candidates; [1]: the matches
+    RC_TRY(ps.alloc((size_t)1, &cand));                  // the candidates
     prof_begin(ctx);
     prof_mark(ctx, "index_ranges");
-    HIP_TRY(launch_index_ranges(idx->r, idx->n, fb, p, R, off, beg, small, ctx->stream));
+    HIP_TRY(launch_index_ranges(idx->r, idx->n, fb, p, R, off, beg, cand, ctx->stream));
     u64 C = 0;
-    RC_TRY(read_back(ctx, &C, small, 8));
+    RC_TRY(read_back(ctx, &C, cand, 8));
     if (visited)
         *visited = C;
     if (C == 0)
@@ -247,15 +197,9 @@ int scan_core(dnagpu_ctx *ctx, const dnagpu_kmer_index *idx, const FilterBits &f
     u32 *tiles = nullptr;
     prof_mark(ctx, "index_count");
     if (a.test) {
-        const u32 nt = index_scan_tiles(C);
-        u32 *scan_tmp = nullptr;
-        RC_TRY(ps.alloc((size_t)nt, &tiles));
-        RC_TRY(ps.alloc((size_t)scan_tmp_words(nt), &scan_tmp));
-        HIP_TRY(launch_index_sweep_count(a, tiles, ctx->stream));
-        u32 *sum = reinterpret_cast<u32 *>(small + 1);
-        HIP_TRY(launch_scan_u32(tiles, tiles, nt, scan_tmp, sum, ctx->stream));
         u32 t32 = 0;
-        RC_TRY(read_back(ctx, &t32, sum, 4));
+        RC_TRY(select_tiles(ctx, ps, index_scan_tiles(C), [&](u32 *t) { return launch_index_sweep_count(a, t, ctx->stream); },
+                            &tiles, &t32));
         total = t32;
     }
     *n_out = total;
@@ -266,21 +210,11 @@ int scan_core(dnagpu_ctx *ctx, const dnagpu_kmer_index *idx, const FilterBits &f
         return DNAGPU_OK;
     }
     prof_mark(ctx, "index_write");
-    if (out_on_device) {
-        HIP_TRY(launch_index_sweep_write(a, tiles, out_rows, out_keys, nwrite, ctx->stream));
-        prof_mark(ctx, "end");
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        prof_end(ctx);
-        return DNAGPU_OK;
-    }
-    u64 *dr = nullptr, *dk = nullptr;
-    if (out_rows)
-        RC_TRY(ps.alloc((size_t)nwrite, &dr));
-    if (out_keys)
-        RC_TRY(ps.alloc((size_t)nwrite, &dk));
-    HIP_TRY(launch_index_sweep_write(a, tiles, dr, dk, nwrite, ctx->stream));
+    OutCols<2> o;
+    RC_TRY(o.init(ctx, ps, {out_rows, out_keys}, nwrite, out_on_device));
+    HIP_TRY(launch_index_sweep_write(a, tiles, o.dev(0), o.dev(1), nwrite, ctx->stream));
     prof_mark(ctx, "end");
-    const int rc = copy_out(ctx, nwrite, dr, dk, out_rows, out_keys);
+    const int rc = o.finish();
     prof_end(ctx);
     return rc;
 }
@@ -308,7 +242,7 @@ extern "C" int dnagpu_kmer_index_build(dnagpu_ctx *ctx, const uint64_t *keys, ui
     HIP_TRY(hipSetDevice(ctx->device));
     PoolScope ps(ctx);
     const u64 *dev_keys = nullptr;
-    RC_TRY(device_words(ctx, ps, keys, n, on_device, &dev_keys));
+    RC_TRY(device_list(ctx, ps, keys, n, on_device, &dev_keys));
     RC_TRY(build_core(ctx, dev_keys, n, k, idx.get()));
     *out = idx.release();
     return DNAGPU_OK;
@@ -333,7 +267,7 @@ extern "C" int dnagpu_kmer_index_append(dnagpu_ctx *ctx, dnagpu_kmer_index *idx,
     HIP_TRY(hipSetDevice(ctx->device));
     PoolScope ps(ctx);
     const u64 *dev_keys = nullptr;
-    RC_TRY(device_words(ctx, ps, keys, m, on_device, &dev_keys));
+    RC_TRY(device_list(ctx, ps, keys, m, on_device, &dev_keys));
     return append_core(ctx, dev_keys, m, idx);
     });
 }
@@ -353,7 +287,7 @@ extern "C" int dnagpu_kmer_index_delete(dnagpu_ctx *ctx, dnagpu_kmer_index *idx,
     HIP_TRY(hipSetDevice(ctx->device));
     PoolScope ps(ctx);
     const u64 *dev_ids = nullptr;
-    RC_TRY(device_words(ctx, ps, rows, m, on_device, &dev_ids));
+    RC_TRY(device_list(ctx, ps, rows, m, on_device, &dev_ids));
     u64 gone = 0;
     RC_TRY(delete_core(ctx, dev_ids, m, idx, &gone));
     if (n_deleted)
@@ -396,19 +330,13 @@ extern "C" int dnagpu_kmer_index_lookup(dnagpu_ctx *ctx, const dnagpu_kmer_index
     if (m == 0)
         return DNAGPU_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (on_device) {
-        HIP_TRY(launch_index_lookup(idx->r, idx->n, idx->k, keys, m, out_first, out_count, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return DNAGPU_OK;
-    }
     PoolScope ps(ctx);
-    u64 *dq = nullptr, *df = nullptr, *dc = nullptr;
-    RC_TRY(ps.alloc((size_t)m, &dq));
-    RC_TRY(ps.alloc((size_t)m, &df));
-    RC_TRY(ps.alloc((size_t)m, &dc));
-    HIP_TRY(hipMemcpyAsync(dq, keys, m * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(launch_index_lookup(idx->r, idx->n, idx->k, dq, m, df, dc, ctx->stream));
-    return copy_out(ctx, m, df, dc, out_first, out_count);
+    const u64 *dq = nullptr;
+    OutCols<2> o;
+    RC_TRY(device_list(ctx, ps, keys, m, on_device, &dq));
+    RC_TRY(o.init(ctx, ps, {out_first, out_count}, m, on_device));
+    HIP_TRY(launch_index_lookup(idx->r, idx->n, idx->k, dq, m, o.dev(0), o.dev(1), ctx->stream));
+    return o.finish();
     });
 }
 
@@ -423,19 +351,11 @@ extern "C" int dnagpu_kmer_index_read(dnagpu_ctx *ctx, const dnagpu_kmer_index *
     if (count == 0 || (!out_rows && !out_keys))
         return DNAGPU_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (out_on_device) {
-        HIP_TRY(launch_index_read(idx->r, idx->row, idx->k, first, count, out_rows, out_keys, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return DNAGPU_OK;
-    }
     PoolScope ps(ctx);
-    u64 *dr = nullptr, *dk = nullptr;
-    if (out_rows)
-        RC_TRY(ps.alloc((size_t)count, &dr));
-    if (out_keys)
-        RC_TRY(ps.alloc((size_t)count, &dk));
-    HIP_TRY(launch_index_read(idx->r, idx->row, idx->k, first, count, dr, dk, ctx->stream));
-    return copy_out(ctx, count, dr, dk, out_rows, out_keys);
+    OutCols<2> o;
+    RC_TRY(o.init(ctx, ps, {out_rows, out_keys}, count, out_on_device));
+    HIP_TRY(launch_index_read(idx->r, idx->row, idx->k, first, count, o.dev(0), o.dev(1), ctx->stream));
+    return o.finish();
     });
 }
 

@@ -8,8 +8,6 @@ using namespace dnagpu;
 
 namespace {
 
-constexpr u64 U32_MAX64 = 0xFFFFFFFFull;
-
 int profile_run(dnagpu_ctx *ctx, const dnagpu_dna *dna, int k, bool canonical, u64 seq_first, u64 n, u32 *out_counts,
                 u64 *out_rows, bool out_on_device)
 {
@@ -30,7 +28,7 @@ int profile_run(dnagpu_ctx *ctx, const dnagpu_dna *dna, int k, bool canonical, u
 
     const u64 *starts = dna->seq_starts + seq_first;
     HIP_TRY(launch_profile_plan(starts, n, k, rows, items, st));
-    HIP_TRY(launch_scan_u32(items, items, n, scan_tmp, items + n, st));
+    HIP_TRY(launch_scan_u32(items, items, n, scan_tmp, items + n, st));   // (not scan_total: the wave kernel is queued before the wait)
     HIP_TRY(launch_profile_wave(dna->words, dna->n_words, starts, n, k, canonical ? 1 : 0, counts, st));
     u32 n_items = 0;
     RC_TRY(read_back(ctx, &n_items, items + n, sizeof n_items));

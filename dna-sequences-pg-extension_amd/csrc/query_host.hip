@@ -92,18 +92,6 @@ int select_into(dnagpu_ctx *ctx, const GroupSet &g, u64 lo, u64 hi, u64 *dk, u64
     return DNAGPU_OK;
 }
 
-// rows [0, n) of two device arrays to the caller's (host, or device) arrays; waits for the stream
-int hand_out(dnagpu_ctx *ctx, u64 n, const u64 *dk, const u64 *dc, u64 *out_keys, u64 *out_counts, int out_on_device)
-{
-    const hipMemcpyKind kind = out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (n && out_keys)
-        HIP_TRY(hipMemcpyAsync(out_keys, dk, (size_t)n * 8, kind, ctx->stream));
-    if (n && out_counts)
-        HIP_TRY(hipMemcpyAsync(out_counts, dc, (size_t)n * 8, kind, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return DNAGPU_OK;
-}
-
 int select_core(dnagpu_ctx *ctx, const GroupSet &g, u64 lo, u64 hi, u64 *out_keys, u64 *out_counts, u64 cap, u64 *n_out,
                 int out_on_device)
 {
@@ -116,21 +104,16 @@ int select_core(dnagpu_ctx *ctx, const GroupSet &g, u64 lo, u64 hi, u64 *out_key
     u64 *cursor = nullptr;
     RC_TRY(ps.alloc(1, &cursor));
     HIP_TRY(hipMemsetAsync(cursor, 0, 8, ctx->stream));
-    u64 *dk = out_keys, *dc = out_counts;
-    if (!out_on_device) {                            // host outputs: staged in pool buffers (no more rows than there are groups)
+    if (!out_on_device)                              // host outputs: staged in pool buffers (no more rows than there are groups)
         cap = std::min(cap, g.distinct);
-        dk = dc = nullptr;
-        if (cap && out_keys)
-            RC_TRY(ps.alloc((size_t)cap, &dk));
-        if (cap && out_counts)
-            RC_TRY(ps.alloc((size_t)cap, &dc));
-    }
-    RC_TRY(select_into(ctx, g, lo, hi, dk, dc, cap, cursor));
+    OutCols<2> o;
+    RC_TRY(o.init(ctx, ps, {out_keys, out_counts}, cap, out_on_device));
+    RC_TRY(select_into(ctx, g, lo, hi, o.dev(0), o.dev(1), cap, cursor));
     u64 total = 0;
     RC_TRY(read_back(ctx, &total, cursor, 8));       // (waits for the stream: device outputs are complete)
     *n_out = total;
     if (!out_on_device)
-        RC_TRY(hand_out(ctx, std::min(total, cap), dk, dc, out_keys, out_counts, 0));
+        RC_TRY(o.finish(std::min(total, cap)));
     return DNAGPU_OK;
 }
 
@@ -224,7 +207,7 @@ int top_core(dnagpu_ctx *ctx, const GroupSet &g, u64 n, u64 *out_keys, u64 *out_
         RC_TRY(select_into(ctx, g, T, T, sk, sc, rows, cursor));     // the ties, as far as there are places left
     }
     HIP_TRY(launch_query_sort(sk, sc, (u32)m, ctx->stream));
-    RC_TRY(hand_out(ctx, rows, sk, sc, out_keys, out_counts, out_on_device));
+    RC_TRY(copy_cols(ctx, {{sk, out_keys}, {sc, out_counts}}, rows, out_on_device));
     *n_out = rows;
     return DNAGPU_OK;
 }
@@ -483,7 +466,7 @@ extern "C" int dnagpu_ranking_read(dnagpu_ctx *ctx, const dnagpu_ranking *r, uin
     if (count == 0 || (!out_keys && !out_counts))
         return DNAGPU_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    return hand_out(ctx, count, r->keys + first, r->counts + first, out_keys, out_counts, out_on_device);
+    return copy_cols(ctx, {{r->keys + first, out_keys}, {r->counts + first, out_counts}}, count, out_on_device);
     });
 }
 

@@ -9,8 +9,6 @@ using namespace dnagpu;
 
 namespace {
 
-constexpr u64 U32_MAX64 = 0xFFFFFFFFull;
-
 SeqTable table_of(const dnagpu_dna *d, u64 seq_first) { return SeqTable{d->words, d->n_words, d->seq_starts + seq_first}; }
 
 // Stage 1: fp[0 .. n) = the fingerprints of the n >= 1 sequences of t; ids (may be null) = 0 .. n - 1.  items (n + 1 words)
@@ -19,45 +17,19 @@ int fingerprints(dnagpu_ctx *ctx, const SeqTable &t, u64 n, u64 *fp, u32 *ids, u
 {
     hipStream_t st = ctx->stream;
     HIP_TRY(launch_seqeq_fp_short(t, n, fp, ids, items, st));
-    HIP_TRY(launch_scan_u32(items, items, n, scan_tmp, items + n, st));
-    RC_TRY(read_back(ctx, n_items, items + n, sizeof *n_items));
+    RC_TRY(scan_total(ctx, items, n, scan_tmp, n_items));
     HIP_TRY(launch_seqeq_fp_long(t, n, items, *n_items, fp, st));
     if (ctx->debug_flags & DNAGPU_DEBUG_WEAK_FINGERPRINT)
         HIP_TRY(launch_seqeq_weaken(fp, n, st));
     return DNAGPU_OK;
 }
 
-// Stage 2: the stable LSD sort of the pairs pair[0] = (fp, ids) by fp, eight 8-bit digits, ping-pong with pair[1]; a digit
-// that takes one value moves nothing and is skipped.  *sorted = the index of the pair that holds the result.
+// (fingerprint, id) lists: pair[0] and pair[1] are the ping-pong of stage 2, the stable LSD sort by all eight digits of fp
+// (lsd_sort_pairs)
 struct Pair {
     u64 *fp;
     u32 *id;
 };
-int sort_pairs(dnagpu_ctx *ctx, PoolScope &ps, const Pair pair[2], u64 n, int *sorted)
-{
-    const u64 n_hist = (u64)256 * index_sort_tiles(n);
-    u32 *hist = nullptr, *scan_tmp = nullptr, *bins_dev = nullptr;
-    RC_TRY(ps.alloc((size_t)n_hist, &hist));
-    RC_TRY(ps.alloc((size_t)scan_tmp_words(n_hist), &scan_tmp));
-    RC_TRY(ps.alloc((size_t)2, &bins_dev));
-    int cur = 0;
-    for (int p = 0; p < 8; p++) {
-        const IndexSortSrc src{nullptr, pair[cur].fp, pair[cur].id, 32, 0};
-        HIP_TRY(launch_index_hist(src, n, 8 * p, hist, ctx->stream));
-        HIP_TRY(launch_scan_u32(hist, hist, n_hist, scan_tmp, nullptr, ctx->stream));
-        HIP_TRY(launch_index_digit_bins(hist, n, bins_dev, ctx->stream));
-        u32 bins = 0;
-        RC_TRY(read_back(ctx, &bins, bins_dev, 4));
-        if (bins <= 1)
-            continue;
-        HIP_TRY(launch_index_scatter(src, n, 8 * p, hist, pair[1 - cur].fp, pair[1 - cur].id, ctx->stream));
-        cur = 1 - cur;
-    }
-    for (void *p : {(void *)hist, (void *)scan_tmp, (void *)bins_dev})
-        ps.free_now(p);
-    *sorted = cur;
-    return DNAGPU_OK;
-}
 
 // the scratch of the verify rounds, n entries each
 struct RoundBufs {
@@ -75,9 +47,8 @@ int verify_round(dnagpu_ctx *ctx, const SeqTable &t, const Pair &list, u64 m, bo
     HIP_TRY(launch_seqeq_head_slots(b.head, b.run, m, b.slot, st));
     HIP_TRY(launch_seqeq_verify(t, list.id, m, b.head, b.run, b.slot, b.hidx, b.eq, b.items, st));
     if (has_long) {
-        HIP_TRY(launch_scan_u32(b.items, b.items, m, b.scan_tmp, b.total, st));
         u32 n_items = 0;
-        RC_TRY(read_back(ctx, &n_items, b.total, 4));
+        RC_TRY(scan_total(ctx, b.items, m, b.scan_tmp, &n_items));   // (items has a word behind every list: n + 1)
         HIP_TRY(launch_seqeq_pair_items(t, list.id, t, list.id, b.hidx, m, b.items, n_items, b.eq, st));
     }
     HIP_TRY(launch_scan_u32(b.eq, b.pre, m, b.scan_tmp, b.total, st));
@@ -122,7 +93,9 @@ int classes_build(dnagpu_ctx *ctx, const dnagpu_dna *table, dnagpu_seq_classes *
     RC_TRY(fingerprints(ctx, t, n, pair[0].fp, pair[0].id, b.items, b.scan_tmp, &n_items));
     prof_mark(ctx, "seqeq_sort");
     int kept = 0;
-    RC_TRY(sort_pairs(ctx, ps, pair, n, &kept));
+    u64 *const fps[2] = {pair[0].fp, pair[1].fp};
+    u32 *const ids[2] = {pair[0].id, pair[1].id};
+    RC_TRY(lsd_sort_pairs(ctx, IndexSortSrc{nullptr, fps[0], ids[0], 32, 0}, n, 8, fps, ids, nullptr, &kept));
 
     // the rounds: the sorted list stays (the match walks it); the leftovers alternate between the other pair and a third
     prof_mark(ctx, "seqeq_verify");
@@ -159,23 +132,7 @@ int classes_build(dnagpu_ctx *ctx, const dnagpu_dna *table, dnagpu_seq_classes *
     return DNAGPU_OK;                                      // (the scratch arrays go back to the pool here)
 }
 
-// n entries of a u32 device array widened to u64 at `out` (host memory, or device memory)
-int widen_out(dnagpu_ctx *ctx, PoolScope &ps, const u32 *src, u64 n, u64 *out, int out_on_device)
-{
-    if (!out)
-        return DNAGPU_OK;
-    if (out_on_device) {
-        HIP_TRY(launch_hits_widen(src, out, n, ctx->stream));
-        return DNAGPU_OK;
-    }
-    u64 *stage = nullptr;
-    RC_TRY(ps.alloc((size_t)n, &stage));
-    HIP_TRY(launch_hits_widen(src, stage, n, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(out, stage, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    return DNAGPU_OK;
-}
-
-// the two selects: count, scan, write (dnagpu_seq_hits_select's shape)
+// the two selects: count, scan, write
 int select_run(dnagpu_ctx *ctx, const dnagpu_seq_classes *c, const SeqSelect &q, u64 *out_seq, u64 *out_copies, u64 cap, u64 *n_out,
                int out_on_device)
 {
@@ -185,31 +142,17 @@ int select_run(dnagpu_ctx *ctx, const dnagpu_seq_classes *c, const SeqSelect &q,
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     PoolScope ps(ctx);
-    const u32 nt = seqeq_select_tiles(c->n);
-    u32 *tiles = nullptr, *scan_tmp = nullptr;
-    RC_TRY(ps.alloc((size_t)nt + 1, &tiles));              // (the last word: the total)
-    RC_TRY(ps.alloc((size_t)scan_tmp_words(nt), &scan_tmp));
-    HIP_TRY(launch_seqeq_select_count(c->rep, c->copies, c->n, q, tiles, st));
-    HIP_TRY(launch_scan_u32(tiles, tiles, nt, scan_tmp, tiles + nt, st));
-    u32 total = 0;
-    RC_TRY(read_back(ctx, &total, tiles + nt, sizeof total));
+    u32 *tiles = nullptr, total = 0;
+    RC_TRY(select_tiles(ctx, ps, seqeq_select_tiles(c->n),
+                        [&](u32 *t) { return launch_seqeq_select_count(c->rep, c->copies, c->n, q, t, st); }, &tiles, &total));
     *n_out = total;
     const u64 n_write = std::min<u64>(total, cap);
-    u64 *outs[2] = {out_seq, out_copies};
     if (n_write == 0 || (!out_seq && !out_copies))
         return DNAGPU_OK;
-    u64 *dev[2] = {out_seq, out_copies};
-    if (!out_on_device)
-        for (int i = 0; i < 2; i++)
-            if (outs[i])
-                RC_TRY(ps.alloc((size_t)n_write, &dev[i]));
-    HIP_TRY(launch_seqeq_select_write(c->rep, c->copies, c->n, q, tiles, dev[0], dev[1], n_write, st));
-    if (!out_on_device)
-        for (int i = 0; i < 2; i++)
-            if (outs[i])
-                HIP_TRY(hipMemcpyAsync(outs[i], dev[i], (size_t)n_write * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DNAGPU_OK;
+    OutCols<2> o;
+    RC_TRY(o.init(ctx, ps, {out_seq, out_copies}, n_write, out_on_device));
+    HIP_TRY(launch_seqeq_select_write(c->rep, c->copies, c->n, q, tiles, o.dev(0), o.dev(1), n_write, st));
+    return o.finish();
 }
 
 // Stage 5: the np >= 1 sequences from seq_first of probe against the built side

@@ -8,8 +8,6 @@ using namespace dnagpu;
 
 namespace {
 
-constexpr u64 U32_MAX64 = 0xFFFFFFFFull;
-
 // The two faces of the call.  ids != nullptr: take (segment i = sequence ids[i] of src's set); else gather (first / len).
 // All three lists are host memory, or device memory when on_device.
 struct TakeLists {
@@ -19,20 +17,6 @@ struct TakeLists {
     u64 n;
     int on_device;
 };
-
-// `count` entries of a caller's list as device memory: the list itself, or a copy in pool memory of ps
-template <typename T>
-int device_list(dnagpu_ctx *ctx, PoolScope &ps, const T *list, u64 count, int on_device, const T **dev)
-{
-    *dev = list;
-    if (!list || on_device)
-        return DNAGPU_OK;
-    T *copy = nullptr;
-    RC_TRY(ps.alloc((size_t)count, &copy));
-    HIP_TRY(hipMemcpyAsync(copy, list, (size_t)count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-    *dev = copy;
-    return DNAGPU_OK;
-}
 
 int gather_core(dnagpu_ctx *ctx, const dnagpu_dna *src, const TakeLists &in, dnagpu_dna **out)
 {

@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "../../include/dnagpu.h"
+#include "row_batch.h"
 
 static __thread char g_msg[256];
 static dnagpu_ctx *g_ctx;          /* one per process, created lazily (post-fork) */
@@ -777,8 +778,7 @@ struct CountKmersAgg {
     int k;
     bool canonical;                              /* count_kmers_agg_begin_canonical: the flush is dnagpu_acc_add_canonical */
     dnagpu_acc *acc;                             /* created on the first flush (the GPU context is lazy) */
-    uint64_t *words, n_bases, cap_words;         /* the batch: rows back to back as one packed stream */
-    uint64_t *starts, n_seqs, cap_seqs;          /* starts[0 .. n_seqs] */
+    RowBatch b;                                  /* the open batch */
     bool finished, failed;
     uint64_t top_limit;                          /* count_kmers_agg_top: serve only the first rows of ORDER BY count(*) DESC */
     int order;                                   /* count_kmers_agg_order: 0 = none, 1 = count descending, 2 = ascending */
@@ -812,76 +812,56 @@ CountKmersAgg *count_kmers_agg_begin_canonical(int k)
     return a;
 }
 
-/* n bases of src (packed, base 0 at bit 0) onto dst from base `at`; dst's bits from `at` on are zero and dst has room for
- * ceil((at + n) / 32) + 1 words */
-static void append_bases(uint64_t *dst, uint64_t at, const uint64_t *src, uint64_t n)
-{
-    const unsigned sh = (unsigned)(at & 31) * 2;
-    const uint64_t w = at >> 5, nw = (n + 31) / 32;
-    for (uint64_t i = 0; i < nw; i++) {
-        uint64_t v = src[i];
-        if (i == nw - 1 && (n & 31))
-            v &= ((uint64_t)1 << (2 * (n & 31))) - 1;                      /* nothing behind the row's last base */
-        if (sh == 0) {
-            dst[w + i] = v;
-        } else {
-            dst[w + i] |= v << sh;
-            dst[w + i + 1] = v >> (64 - sh);
-        }
-    }
-}
-
+/* rb_grow for the arrays of answers, with the ERROR */
 static bool agg_grow(void **p, uint64_t *cap, uint64_t need)
 {
-    if (need <= *cap)
+    if (rb_grow(p, cap, need))
         return true;
-    uint64_t c = *cap ? *cap : 1024;
-    while (c < need)
-        c *= 2;
-    void *q = realloc(*p, (size_t)c * sizeof(uint64_t));
-    if (!q) {
+    ereport_error("out of memory");
+    return false;
+}
+
+/* the batch as a resident table with its boundaries; rows without a base make a stream of no words.  *d is the caller's to
+ * free, also after an ERROR */
+static bool batch_upload(const RowBatch *b, dnagpu_dna **d)
+{
+    static const uint64_t none[1] = {0};
+    return ctx() != NULL && gpu_ok(dnagpu_dna_upload(g_ctx, b->n_bases ? b->words : none, b->n_bases, d)) &&
+           gpu_ok(dnagpu_dna_set_sequences(g_ctx, *d, b->starts, b->n_seqs));
+}
+
+/* The add policy of the streaming objects: a long row gets a batch of its own (the open one is flushed first), the row goes
+ * behind the batch's rows, and a batch that has reached g_agg_flush_bases is flushed.  flush(self) empties the batch. */
+static bool batch_add(RowBatch *b, const Dna *row, bool (*flush)(void *), void *self)
+{
+    if (rb_spills(b, row->length, g_agg_flush_bases) && !flush(self))
+        return false;
+    if (!rb_append(b, row->bit_sequence, row->length)) {
         ereport_error("out of memory");
         return false;
     }
-    *p = q;
-    *cap = c;
-    return true;
+    return !rb_full(b, g_agg_flush_bases) || flush(self);
 }
 
 /* the batch so far: counted, added into the accumulator, emptied */
-static bool agg_flush(CountKmersAgg *a)
+static bool agg_flush(void *self)
 {
+    CountKmersAgg *a = (CountKmersAgg *)self;
     bool ok = true;
-    if (a->n_bases > 0) {
+    if (a->b.n_bases > 0) {
         dnagpu_dna *d = NULL;
         dnagpu_hist *h = NULL;
         ok = ctx() != NULL && (a->acc || gpu_ok(dnagpu_acc_create(g_ctx, a->k, &a->acc))) &&
-             gpu_ok(dnagpu_dna_upload(g_ctx, a->words, a->n_bases, &d)) &&
-             gpu_ok(dnagpu_count_kmers_batch(g_ctx, d, a->starts, a->n_seqs, a->k, &h)) &&
+             gpu_ok(dnagpu_dna_upload(g_ctx, a->b.words, a->b.n_bases, &d)) &&
+             gpu_ok(dnagpu_count_kmers_batch(g_ctx, d, a->b.starts, a->b.n_seqs, a->k, &h)) &&
              gpu_ok(a->canonical ? dnagpu_acc_add_canonical(g_ctx, a->acc, h) : dnagpu_acc_add(g_ctx, a->acc, h));
         if (h)
             dnagpu_hist_free(g_ctx, h);
         if (d)
             dnagpu_dna_free(g_ctx, d);
     }
-    a->n_bases = 0;
-    a->n_seqs = 0;
+    rb_clear(&a->b);
     return ok;
-}
-
-/* one more row behind the batch's rows: its bases onto the packed stream, its end as the next start */
-static bool batch_append(uint64_t **words, uint64_t *n_bases, uint64_t *cap_words, uint64_t **starts, uint64_t *n_seqs,
-                         uint64_t *cap_seqs, const Dna *row)
-{
-    const uint64_t len = row->length;
-    if (!agg_grow((void **)words, cap_words, (*n_bases + len + 31) / 32 + 1) || !agg_grow((void **)starts, cap_seqs, *n_seqs + 2))
-        return false;
-    (*starts)[0] = 0;
-    if (len)
-        append_bases(*words, *n_bases, row->bit_sequence, len);
-    *n_bases += len;
-    (*starts)[++*n_seqs] = *n_bases;
-    return true;
 }
 
 bool count_kmers_agg_add(CountKmersAgg *a, const Dna *row)
@@ -890,20 +870,9 @@ bool count_kmers_agg_add(CountKmersAgg *a, const Dna *row)
         ereport_error("count_kmers_agg: row added after the aggregate finished or failed");
         return false;
     }
-    const uint64_t len = row->length;
-    if (a->n_seqs > 0 && a->n_bases + len > g_agg_flush_bases && !agg_flush(a)) {   /* a long row: a batch of its own */
+    if (!batch_add(&a->b, row, agg_flush, a))
         a->failed = true;
-        return false;
-    }
-    if (!batch_append(&a->words, &a->n_bases, &a->cap_words, &a->starts, &a->n_seqs, &a->cap_seqs, row)) {
-        a->failed = true;
-        return false;
-    }
-    if (a->n_bases >= g_agg_flush_bases && !agg_flush(a)) {
-        a->failed = true;
-        return false;
-    }
-    return true;
+    return !a->failed;
 }
 
 /* FINALFUNC's first step: the last batch, then the totals over the accumulated groups */
@@ -1013,8 +982,7 @@ void count_kmers_agg_end(CountKmersAgg *a)
         dnagpu_ranking_free(g_ctx, a->ranking);
     if (a->acc)
         dnagpu_acc_free(g_ctx, a->acc);
-    free(a->words);
-    free(a->starts);
+    rb_free(&a->b);
     free(a->keys);
     free(a->counts);
     free(a);
@@ -1157,8 +1125,7 @@ void count_kmers_join_end(CountKmersJoin *j)
 #define TK_WINDOW ((uint64_t)1 << 20)     /* stream rows per refill: a window never holds more table rows than stream rows */
 
 typedef struct TableBatch {
-    uint64_t *words, n_bases, cap_words;         /* rows back to back as one packed stream, as the aggregate packs them */
-    uint64_t *starts, n_seqs, cap_seqs;
+    RowBatch b;
     uint64_t first_seq;                          /* ordinal of the batch's first row in the table */
 } TableBatch;
 
@@ -1216,7 +1183,7 @@ bool table_kmers_add(TableKmers *t, const Dna *row)
         return false;
     }
     TableBatch *b = t->open ? &t->batches[t->n_batches - 1] : NULL;
-    if (b && b->n_seqs > 0 && b->n_bases + row->length > g_agg_flush_bases)      /* a long row: a batch of its own */
+    if (b && rb_spills(&b->b, row->length, g_agg_flush_bases))                  /* a long row: a batch of its own */
         b = NULL;
     if (!b) {
         if (t->n_batches == t->cap_batches) {
@@ -1234,12 +1201,13 @@ bool table_kmers_add(TableKmers *t, const Dna *row)
         memset(b, 0, sizeof *b);
         b->first_seq = t->n_rows;
     }
-    if (!batch_append(&b->words, &b->n_bases, &b->cap_words, &b->starts, &b->n_seqs, &b->cap_seqs, row)) {
+    if (!rb_append(&b->b, row->bit_sequence, row->length)) {
+        ereport_error("out of memory");
         t->failed = true;
         return false;
     }
     t->n_rows++;
-    t->open = b->n_bases < g_agg_flush_bases;
+    t->open = !rb_full(&b->b, g_agg_flush_bases);
     return true;
 }
 
@@ -1253,13 +1221,12 @@ static void tk_drop_device(TableKmers *t)
 /* batch t->cur onto the device with its boundaries; false = ERROR */
 static bool tk_open_batch(TableKmers *t)
 {
-    const TableBatch *b = &t->batches[t->cur];
+    const RowBatch *b = &t->batches[t->cur].b;
     t->scan_pos = 0;
     t->scan_total = b->n_bases >= (uint64_t)t->k ? b->n_bases - (uint64_t)t->k + 1 : 0;
     if (t->scan_total == 0)
         return true;
-    return ctx() != NULL && gpu_ok(dnagpu_dna_upload(g_ctx, b->words, b->n_bases, &t->dev)) &&
-           gpu_ok(dnagpu_dna_set_sequences(g_ctx, t->dev, b->starts, b->n_seqs));
+    return batch_upload(b, &t->dev);
 }
 
 bool table_kmers_next(TableKmers *t, int64_t *seq, int64_t *pos, Kmer *out)
@@ -1322,10 +1289,8 @@ void table_kmers_end(TableKmers *t)
     if (!t)
         return;
     tk_drop_device(t);
-    for (uint64_t i = 0; i < t->n_batches; i++) {
-        free(t->batches[i].words);
-        free(t->batches[i].starts);
-    }
+    for (uint64_t i = 0; i < t->n_batches; i++)
+        rb_free(&t->batches[i].b);
     free(t->batches);
     free(t->keys);
     free(t->seq);
@@ -1340,8 +1305,7 @@ struct TableHits {
     unsigned flags;
     uint64_t min_count, max_count;
     bool started, failed;
-    uint64_t *words, n_bases, cap_words;         /* the open batch, packed as table_kmers_add packs its batches */
-    uint64_t *starts, n_seqs, cap_seqs;
+    RowBatch b;                                  /* the open batch */
     uint64_t *rows, *hits, n_done, cap_rows, cap_hits;      /* the answers of the rows of the batches looked up so far */
     uint64_t next;
     uint64_t tot_rows, tot_hits, tot_seqs_hit;
@@ -1369,23 +1333,23 @@ TableHits *table_hits_begin(CountKmersAgg *set, bool canonical, int64_t min_coun
 }
 
 /* the open batch: looked up on the device, its answers appended, emptied */
-static bool th_flush(TableHits *t)
+static bool th_flush(void *self)
 {
-    const uint64_t n = t->n_seqs;
+    TableHits *t = (TableHits *)self;
+    const uint64_t n = t->b.n_seqs;
     if (n == 0)
         return true;
     if (!agg_grow((void **)&t->rows, &t->cap_rows, t->n_done + n) || !agg_grow((void **)&t->hits, &t->cap_hits, t->n_done + n))
         return false;
     bool ok = true;
-    if (t->n_bases == 0) {                                                /* empty rows only: nothing to upload */
+    if (t->b.n_bases == 0) {                                              /* empty rows only: nothing to upload */
         memset(t->rows + t->n_done, 0, (size_t)n * sizeof(uint64_t));
         memset(t->hits + t->n_done, 0, (size_t)n * sizeof(uint64_t));
     } else {
         dnagpu_dna *d = NULL;
         dnagpu_seq_hits *h = NULL;
         uint64_t r = 0, c = 0, s = 0;
-        ok = ctx() != NULL && gpu_ok(dnagpu_dna_upload(g_ctx, t->words, t->n_bases, &d)) &&
-             gpu_ok(dnagpu_dna_set_sequences(g_ctx, d, t->starts, n)) &&
+        ok = batch_upload(&t->b, &d) &&
              gpu_ok(dnagpu_table_hits(g_ctx, d, t->set, t->flags, t->min_count, t->max_count, 0, n, &h)) &&
              gpu_ok(dnagpu_seq_hits_read(g_ctx, h, 0, n, t->rows + t->n_done, t->hits + t->n_done, 0)) &&
              gpu_ok(dnagpu_seq_hits_totals(h, &r, &c, &s));
@@ -1401,8 +1365,7 @@ static bool th_flush(TableHits *t)
     }
     if (ok)
         t->n_done += n;
-    t->n_bases = 0;
-    t->n_seqs = 0;
+    rb_clear(&t->b);
     return ok;
 }
 
@@ -1412,19 +1375,9 @@ bool table_hits_add(TableHits *t, const Dna *row)
         ereport_error("table_hits: row added after the first row was served or the scan failed");
         return false;
     }
-    if (t->n_seqs > 0 && t->n_bases + row->length > g_agg_flush_bases && !th_flush(t)) {     /* a long row: a batch of its own */
+    if (!batch_add(&t->b, row, th_flush, t))
         t->failed = true;
-        return false;
-    }
-    if (!batch_append(&t->words, &t->n_bases, &t->cap_words, &t->starts, &t->n_seqs, &t->cap_seqs, row)) {
-        t->failed = true;
-        return false;
-    }
-    if (t->n_bases >= g_agg_flush_bases && !th_flush(t)) {
-        t->failed = true;
-        return false;
-    }
-    return true;
+    return !t->failed;
 }
 
 bool table_hits_next(TableHits *t, int64_t *seq, int64_t *rows, int64_t *hits)
@@ -1463,8 +1416,7 @@ void table_hits_end(TableHits *t)
 {
     if (!t)
         return;
-    free(t->words);
-    free(t->starts);
+    rb_free(&t->b);
     free(t->rows);
     free(t->hits);
     free(t);
@@ -1477,8 +1429,7 @@ struct TableProfile {
     unsigned flags;
     uint64_t width;                              /* 4^k */
     bool started, failed;
-    uint64_t *words, n_bases, cap_words;         /* the open batch, packed as table_hits_add packs its batches */
-    uint64_t *starts, n_seqs, cap_seqs;
+    RowBatch b;                                  /* the open batch */
     uint64_t *rows, n_done, cap_rows;            /* the answers of the rows of the batches profiled so far */
     uint32_t *counts;                            /* n_done * width */
     uint64_t cap_counts;                         /* in 8-byte units (agg_grow's) */
@@ -1507,9 +1458,10 @@ TableProfile *table_profile_begin(int k, bool canonical)
 }
 
 /* the open batch: profiled on the device, its answers appended, emptied */
-static bool tp_flush(TableProfile *t)
+static bool tp_flush(void *self)
 {
-    const uint64_t n = t->n_seqs;
+    TableProfile *t = (TableProfile *)self;
+    const uint64_t n = t->b.n_seqs;
     if (n == 0)
         return true;
     if (!agg_grow((void **)&t->rows, &t->cap_rows, t->n_done + n) ||
@@ -1517,21 +1469,19 @@ static bool tp_flush(TableProfile *t)
         return false;
     uint32_t *counts = t->counts + t->n_done * t->width;
     bool ok = true;
-    if (t->n_bases == 0) {                                                /* empty rows only: nothing to upload */
+    if (t->b.n_bases == 0) {                                              /* empty rows only: nothing to upload */
         memset(t->rows + t->n_done, 0, (size_t)n * sizeof(uint64_t));
         memset(counts, 0, (size_t)(n * t->width) * sizeof(uint32_t));
     } else {
         dnagpu_dna *d = NULL;
-        ok = ctx() != NULL && gpu_ok(dnagpu_dna_upload(g_ctx, t->words, t->n_bases, &d)) &&
-             gpu_ok(dnagpu_dna_set_sequences(g_ctx, d, t->starts, n)) &&
+        ok = batch_upload(&t->b, &d) &&
              gpu_ok(dnagpu_table_profile(g_ctx, d, t->k, t->flags, 0, n, counts, t->rows + t->n_done, 0));
         if (d)
             dnagpu_dna_free(g_ctx, d);
     }
     if (ok)
         t->n_done += n;
-    t->n_bases = 0;
-    t->n_seqs = 0;
+    rb_clear(&t->b);
     return ok;
 }
 
@@ -1541,19 +1491,9 @@ bool table_profile_add(TableProfile *t, const Dna *row)
         ereport_error("table_profile: row added after the first row was served or the scan failed");
         return false;
     }
-    if (t->n_seqs > 0 && t->n_bases + row->length > g_agg_flush_bases && !tp_flush(t)) {     /* a long row: a batch of its own */
+    if (!batch_add(&t->b, row, tp_flush, t))
         t->failed = true;
-        return false;
-    }
-    if (!batch_append(&t->words, &t->n_bases, &t->cap_words, &t->starts, &t->n_seqs, &t->cap_seqs, row)) {
-        t->failed = true;
-        return false;
-    }
-    if (t->n_bases >= g_agg_flush_bases && !tp_flush(t)) {
-        t->failed = true;
-        return false;
-    }
-    return true;
+    return !t->failed;
 }
 
 bool table_profile_next(TableProfile *t, int64_t *seq, int64_t *rows, int64_t *counts)
@@ -1588,8 +1528,7 @@ void table_profile_end(TableProfile *t)
 {
     if (!t)
         return;
-    free(t->words);
-    free(t->starts);
+    rb_free(&t->b);
     free(t->rows);
     free(t->counts);
     free(t);
@@ -1619,35 +1558,29 @@ bool dna_ne(const Dna *a, const Dna *b) { return !dna_equals(a, b); }
 
 /* one side of table_distinct / table_match: the rows packed back to back, ONE resident table when uploaded */
 typedef struct EqSide {
-    uint64_t *words, n_bases, cap_words;
-    uint64_t *starts, n_seqs, cap_seqs;
+    RowBatch b;
     dnagpu_dna *dev;
 } EqSide;
 
 static bool eq_side_add(EqSide *s, const Dna *row, const char *who)
 {
-    if (row->length > TABLE_MAX_BASES - s->n_bases) {
+    if (row->length > TABLE_MAX_BASES - s->b.n_bases) {
         ereport_error("%s: the rows hold more than 4294967295 bases (2^32 - 1), the limit of one resident table", who);
         return false;
     }
-    return batch_append(&s->words, &s->n_bases, &s->cap_words, &s->starts, &s->n_seqs, &s->cap_seqs, row);
-}
-
-/* the side as a resident table (n_seqs > 0); rows without a base make a stream of no words */
-static bool eq_side_upload(EqSide *s)
-{
-    static const uint64_t none[1] = {0};
-    return ctx() != NULL && gpu_ok(dnagpu_dna_upload(g_ctx, s->n_bases ? s->words : none, s->n_bases, &s->dev)) &&
-           gpu_ok(dnagpu_dna_set_sequences(g_ctx, s->dev, s->starts, s->n_seqs));
+    if (!rb_append(&s->b, row->bit_sequence, row->length)) {
+        ereport_error("out of memory");
+        return false;
+    }
+    return true;
 }
 
 static void eq_side_free(EqSide *s)
 {
     if (s->dev)
         dnagpu_dna_free(g_ctx, s->dev);
-    free(s->words);
-    free(s->starts);
-    memset(s, 0, sizeof *s);
+    rb_free(&s->b);
+    s->dev = NULL;
 }
 
 struct TableDistinct {
@@ -1680,11 +1613,11 @@ bool table_distinct_add(TableDistinct *t, const Dna *row)
 /* the whole table: classes on the device, the representatives read back */
 static bool td_run(TableDistinct *t)
 {
-    if (t->rows.n_seqs == 0)
+    if (t->rows.b.n_seqs == 0)
         return true;
     dnagpu_seq_classes *c = NULL;
     uint64_t n = 0;
-    bool ok = eq_side_upload(&t->rows) && gpu_ok(dnagpu_table_classes(g_ctx, t->rows.dev, &c));
+    bool ok = batch_upload(&t->rows.b, &t->rows.dev) && gpu_ok(dnagpu_table_classes(g_ctx, t->rows.dev, &c));
     if (ok) {
         n = dnagpu_seq_classes_distinct(c);
         t->seq = (uint64_t *)malloc((size_t)(n ? n : 1) * sizeof(uint64_t));
@@ -1769,9 +1702,9 @@ bool table_match_add_probe(TableMatch *t, const Dna *row) { return tm_add(t, &t-
 
 static bool tm_run(TableMatch *t)
 {
-    const uint64_t np = t->probe.n_seqs;
-    if (np == 0 || t->build.n_seqs == 0) {       /* nothing to ask, or nothing to find: no row */
-        t->probe.n_seqs = 0;
+    const uint64_t np = t->probe.b.n_seqs;
+    if (np == 0 || t->build.b.n_seqs == 0) {       /* nothing to ask, or nothing to find: no row */
+        t->probe.b.n_seqs = 0;
         return true;
     }
     t->match = (uint64_t *)malloc((size_t)np * sizeof(uint64_t));
@@ -1781,7 +1714,7 @@ static bool tm_run(TableMatch *t)
         return false;
     }
     dnagpu_seq_classes *c = NULL;
-    const bool ok = eq_side_upload(&t->build) && eq_side_upload(&t->probe) &&
+    const bool ok = batch_upload(&t->build.b, &t->build.dev) && batch_upload(&t->probe.b, &t->probe.dev) &&
                     gpu_ok(dnagpu_table_classes(g_ctx, t->build.dev, &c)) &&
                     gpu_ok(dnagpu_table_match(g_ctx, c, t->probe.dev, 0, np, t->match, t->copies, NULL, 0));
     if (c)
@@ -1800,9 +1733,9 @@ bool table_match_next(TableMatch *t, int64_t *probe_seq, int64_t *build_seq, int
             return false;
         }
     }
-    while (t->next < t->probe.n_seqs && t->match[t->next] == DNAGPU_MATCH_NONE)
+    while (t->next < t->probe.b.n_seqs && t->match[t->next] == DNAGPU_MATCH_NONE)
         t->next++;                               /* (an inner join: a probe row without a partner gives no row) */
-    if (t->next >= t->probe.n_seqs)
+    if (t->next >= t->probe.b.n_seqs)
         return false;
     const uint64_t i = t->next++;
     if (probe_seq)
@@ -1836,8 +1769,7 @@ struct TableScreen {
     unsigned flags;
     uint64_t min_count, max_count, min_hits, max_hits, frac_num, frac_den;
     bool started, failed;
-    uint64_t *words, n_bases, cap_words;         /* the open batch, packed as table_hits_add packs its batches */
-    uint64_t *starts, n_seqs, cap_seqs;
+    RowBatch b;                                  /* the open batch */
     uint64_t n_added;                            /* rows of the batches screened so far = the ordinal of the open batch's first row */
     uint64_t *seq, *rows, *hits, cap_seq, cap_rows, cap_hits;     /* the passing rows of the batches screened so far ... */
     Dna **out;                                   /* ... and the rows themselves (NULL once handed out) */
@@ -1890,16 +1822,7 @@ static Dna *dna_cut(const uint64_t *src, uint64_t first, uint64_t len)
         ereport_error("out of memory");
         return NULL;
     }
-    for (uint64_t j = 0; j < nw; j++) {
-        const uint64_t q = first + 32 * j, nb = len - 32 * j < 32 ? len - 32 * j : 32;
-        const unsigned sh = (unsigned)(q & 31) * 2;
-        uint64_t v = src[q >> 5] >> sh;
-        if ((q & 31) + nb > 32)                                           /* (only then: the next word holds a base of the row) */
-            v |= src[(q >> 5) + 1] << (64 - sh);
-        if (nb < 32)
-            v &= ((uint64_t)1 << (2 * nb)) - 1;
-        w[j] = v;
-    }
+    rb_cut(src, first, len, w);
     out->length = len;
     out->bit_sequence = w;
     return out;
@@ -1943,17 +1866,18 @@ static bool ts_collect(TableScreen *t, const dnagpu_dna *taken, const uint64_t *
 }
 
 /* the open batch: screened on the device, its passing rows appended, emptied */
-static bool ts_flush(TableScreen *t)
+static bool ts_flush(void *self)
 {
-    const uint64_t n = t->n_seqs;
+    TableScreen *t = (TableScreen *)self;
+    const uint64_t n = t->b.n_seqs;
     if (n == 0)
         return true;
     bool ok = true;
-    if (t->n_bases == 0) {                                                /* empty rows only: no row, no hit, nothing to upload */
+    if (t->b.n_bases == 0) {                                              /* empty rows only: no row, no hit, nothing to upload */
         if (t->min_hits == 0) {                                           /* (0 * den >= num * 0: the fraction asks nothing of them) */
             ok = ts_grow(t, n);
             for (uint64_t i = 0; ok && i < n; i++) {
-                Dna *row = dna_cut(t->words, 0, 0);
+                Dna *row = dna_cut(t->b.words, 0, 0);
                 if (!row) {
                     ok = false;
                     break;
@@ -1968,8 +1892,7 @@ static bool ts_flush(TableScreen *t)
         dnagpu_seq_hits *h = NULL;
         void *dev = NULL;
         uint64_t n_out = 0;
-        ok = ctx() != NULL && gpu_ok(dnagpu_dna_upload(g_ctx, t->words, t->n_bases, &d)) &&
-             gpu_ok(dnagpu_dna_set_sequences(g_ctx, d, t->starts, n)) &&
+        ok = batch_upload(&t->b, &d) &&
              gpu_ok(dnagpu_table_hits(g_ctx, d, t->set, t->flags, t->min_count, t->max_count, 0, n, &h)) &&
              gpu_ok(dnagpu_buffer_alloc(g_ctx, 3 * 8 * n, &dev));
         uint64_t *dv = (uint64_t *)dev;
@@ -1987,8 +1910,7 @@ static bool ts_flush(TableScreen *t)
             dnagpu_dna_free(g_ctx, d);
     }
     t->n_added += n;
-    t->n_bases = 0;
-    t->n_seqs = 0;
+    rb_clear(&t->b);
     return ok;
 }
 
@@ -1998,19 +1920,9 @@ bool table_screen_add(TableScreen *t, const Dna *row)
         ereport_error("table_screen: row added after the first row was served or the scan failed");
         return false;
     }
-    if (t->n_seqs > 0 && t->n_bases + row->length > g_agg_flush_bases && !ts_flush(t)) {     /* a long row: a batch of its own */
+    if (!batch_add(&t->b, row, ts_flush, t))
         t->failed = true;
-        return false;
-    }
-    if (!batch_append(&t->words, &t->n_bases, &t->cap_words, &t->starts, &t->n_seqs, &t->cap_seqs, row)) {
-        t->failed = true;
-        return false;
-    }
-    if (t->n_bases >= g_agg_flush_bases && !ts_flush(t)) {
-        t->failed = true;
-        return false;
-    }
-    return true;
+    return !t->failed;
 }
 
 bool table_screen_next(TableScreen *t, int64_t *seq, int64_t *rows, int64_t *hits, Dna **row)
@@ -2048,8 +1960,7 @@ void table_screen_end(TableScreen *t)
         return;
     for (uint64_t i = 0; i < t->n_pass; i++)
         dna_free(t->out[i]);
-    free(t->words);
-    free(t->starts);
+    rb_free(&t->b);
     free(t->seq);
     free(t->rows);
     free(t->hits);

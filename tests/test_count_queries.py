@@ -296,6 +296,44 @@ def test_cap_smaller_than_the_matches_and_device_outputs(ctx, pkg):
 
 
 @pytest.mark.gpu
+def test_host_select_with_a_cap_above_the_groups_and_an_output_missing(ctx, pkg):
+    """select into host arrays of more entries than there are groups: each output NULL in turn, and both; nothing is written
+    behind the matches"""
+    k, n = 9, 20_000
+    w = orc.synth_words(0xC4C0, n)
+    ok, oc = orc.count_keys(orc.generate_kmers(w, n, k, faithful=False))
+    d = ctx.upload(w, n)
+    h = ctx.count_kmers(d, k)
+    acc = ctx.accumulator(k)
+    acc.add(h)
+    cap = len(ok) + 1000
+    for q, obj in ((h, "hist"), (acc, "acc")):
+        fn = getattr(pkg.lib(), f"dnagpu_{obj}_select")
+        for lo, hi in ((1, U64_MAX), (2, 3)):
+            m = (oc >= np.uint64(lo)) & (oc <= np.uint64(hi))
+            total = int(m.sum())
+            assert 0 < total
+            for want_keys, want_counts in ((True, True), (True, False), (False, True), (False, False)):
+                keys, counts = np.full(cap, SENTINEL, dtype=np.uint64), np.full(cap, SENTINEL, dtype=np.uint64)
+                n_out = C.c_uint64()
+                assert fn(ctx.h, q.h, lo, hi, keys.ctypes.data if want_keys else None, counts.ctypes.data if want_counts else None,
+                          cap, C.byref(n_out), 0) == 0
+                what = f"{obj} select({lo}, {hi}) keys={want_keys} counts={want_counts}"
+                assert n_out.value == total, what
+                for arr, wanted in ((keys, want_keys), (counts, want_counts)):
+                    assert np.all(arr[total if wanted else 0:] == SENTINEL), f"{what}: a store it was not asked for"
+                if want_keys:
+                    assert np.array_equal(np.sort(keys[:total]), ok[m]), what
+                if want_counts:
+                    assert np.array_equal(np.sort(counts[:total]), np.sort(oc[m])), what
+                if want_keys and want_counts:
+                    assert np.array_equal(counts[:total][np.argsort(keys[:total])], oc[m]), what
+    acc.free()
+    h.free()
+    d.free()
+
+
+@pytest.mark.gpu
 def test_queries_over_histograms_of_several_parts(pkg):
     """the one-process multi-rank count on one device: histograms of several parts (and their borrowed part views); all
     three queries against the ranks' summed downloads"""

@@ -456,6 +456,43 @@ def test_poisoned_and_guarded_pool(pkg):
 
 
 @pytest.mark.gpu
+def test_sort_and_scan_edges_in_a_guarded_pool(pkg):
+    """The sort at its edges -- one key, T and T + 1 keys, T + 1 equal keys (every digit takes one value: only the last pass
+    moves anything), at k = 1, 12 and 32 -- and a scan that tests the positions behind its ranges, over two tiles of
+    candidates: cap 0 and around the total, rows only and keys only, into host arrays and into device buffers of exactly
+    min(total, cap) entries"""
+    with pkg.Context(0) as c:
+        c.set_debug(pkg.DEBUG_POISON_POOL | pkg.DEBUG_GUARD_POOL)
+        for k in (1, 12, 32):
+            _, _, col = column(0x50E7 + k, T + 1, k)
+            for name, keys in (("one key", col[:1]), ("T keys", col[:T]), ("T + 1 keys", col),
+                               ("T + 1 equal keys", np.full(T + 1, col[5], dtype=np.uint64))):
+                with c.kmer_index(keys, k) as idx:
+                    check_whole_index(idx, keys, k, f"guarded pool, k={k}, {name}")
+        k, pattern = 11, "NNNNNNNNNWS"
+        words, nb, col = column(0x9017, T + 1, k)
+        _, pos = orc.generate_kmers_contains(words, nb, k, pattern)
+        want = in_index_order(col, k, pos)
+        total = len(pos)
+        assert 2 < total < T + 1 == expected_visited(col, sets_of_pattern(pattern))
+        flt = pkg.Filter.contains(pattern)
+        with c.kmer_index(col, k) as idx:
+            for cap in (0, total - 1, total, total + 1):
+                m = min(cap, total)
+                for wants in ((True, True), (True, False), (False, True), (False, False)):
+                    got = idx.scan(flt, cap=cap, want_rows=wants[0], want_keys=wants[1])
+                    assert got[2:] == (total, T + 1), f"cap={cap} {wants}"
+                    dev = [c.buffer_alloc(8 * m) if w and m else None for w in wants]
+                    assert idx.scan(flt, cap=cap, on_device=True, out=tuple(dev)) == (total, T + 1), f"cap={cap} {wants}: device"
+                    for host, p, e, w in zip(got[:2], dev, want, wants):
+                        assert (host is None) if not w else np.array_equal(host, e[:m]), f"cap={cap} {wants}"
+                        if p is not None:
+                            assert np.array_equal(c.download_u64(p, m), e[:m]), f"cap={cap} {wants}: device"
+                            c.buffer_free(p)
+        assert pkg.lib().dnagpu_synchronize(c.h) == 0              # every guard band intact
+
+
+@pytest.mark.gpu
 def test_free_and_trim_give_the_memory_back(pkg):
     _, _, col = column(0xF4EE, 200_003, 17)
     with pkg.Context(0) as c:

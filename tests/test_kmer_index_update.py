@@ -418,6 +418,70 @@ def test_updates_in_a_poisoned_and_guarded_pool(pkg):
         assert c.device_bytes() == baseline
 
 
+@pytest.mark.gpu
+def test_delete_at_the_tile_edge_in_a_guarded_pool(pkg):
+    """an index of T + 1 entries, the compaction's second tile holding one: a list of which nothing is present, all but one
+    entry deleted -- the survivor first, last before and first behind the tile edge -- and then the survivor too"""
+    k = 11
+    _, _, col = column(0x7E1, T + 1, k)
+    strangers = np.array([T + 1, T + 2, ID_LIMIT, 1 << 40], dtype=np.uint64)
+    with pkg.Context(0) as c:
+        c.set_debug(pkg.DEBUG_POISON_POOL | pkg.DEBUG_GUARD_POOL)
+        for keep in (0, T - 1, T):                   # the survivor's place in index order
+            model = Model(k, col)
+            idx = c.kmer_index(col, k)
+            assert idx.delete(strangers) == model.delete(strangers) == 0
+            check(idx, model, "nothing listed is present")
+            order, _ = model.expected()
+            ids = np.delete(order, keep)
+            assert idx.delete(ids) == model.delete(ids) == T
+            check(idx, model, f"entry {keep} of index order kept")
+            assert idx.rows == 1 and idx.read()[0].tolist() == [int(order[keep])]
+            assert idx.delete(order[keep:keep + 1]) == model.delete(order[keep:keep + 1]) == 1
+            check(idx, model, "everything deleted")
+            assert (idx.rows, idx.distinct, idx.next_row) == (0, 0, T + 1)
+            assert pkg.lib().dnagpu_synchronize(c.h) == 0          # every guard band intact
+            idx.free()
+
+
+def index_phase_names(pkg, c):
+    """the phase names dnagpu_last_phase_times reports after a build (k = 12, 3000 random keys), an append, a delete and a
+    scan with a residual test"""
+    rng = np.random.default_rng(0x9A5E)
+    names = {}
+
+    def note(what):
+        names[what] = [name for name, _ in c.last_phase_times()]
+
+    c.set_profiling(True)
+    try:
+        with c.kmer_index(rng.integers(0, 1 << 24, 3000, dtype=np.uint64), 12) as idx:
+            note("build")
+            idx.append(rng.integers(0, 1 << 24, 500, dtype=np.uint64))
+            note("append")
+            assert idx.delete(np.arange(0, 3500, 3, dtype=np.uint64)) == 1167
+            note("delete")
+            _, _, n_out, visited = idx.scan(pkg.Filter.contains("ACNNNNNNNNNT"), cap=4000)
+            assert 0 < n_out < visited, "the scan was meant to test the positions behind its ranges"
+            note("scan")
+    finally:
+        c.set_profiling(False)
+    return names
+
+
+INDEX_PHASE_NAMES = {                              # (profiles and tools key on these names)
+    "build": ["index_pass", "index_distinct"],
+    "append": ["index_batch_sort", "index_merge", "index_distinct"],
+    "delete": ["index_mark", "index_compact", "index_distinct"],
+    "scan": ["index_ranges", "index_count", "index_write"],
+}
+
+
+@pytest.mark.gpu
+def test_phase_names_of_the_index(pkg, ctx):
+    assert index_phase_names(pkg, ctx) == INDEX_PHASE_NAMES
+
+
 # ------------------------------------------------------------------ the glue (glue/dna_glue.h: kmer_index_insert / _delete)
 
 @pytest.fixture(scope="module")

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from __graft_entry__ import ROOT, load_package
-from test_table_hits import encode_table, resident
+from test_table_hits import check_select_forms, encode_table, resident
 
 BAD_ARG = 5
 SEED = 0x5E9 << 32
@@ -364,6 +364,82 @@ def test_mixed_table_with_heavy_duplication(ctx, pkg, dbg, weak):
             assert ei.value.code == BAD_ARG
     finally:
         d.free()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [2048, 2049])
+@pytest.mark.parametrize("last", ["unique", "copy"])
+def test_selects_at_the_tile_edge(ctx, pkg, dbg, n, last):
+    """select and members over one full select tile and over one entry more -- that entry a representative of its own, or a
+    copy of sequence 0 -- in every output form (check_select_forms), with a select of nothing"""
+    rng = np.random.default_rng(SEED + 800)
+    pool = [random_text(rng, 40) for _ in range(300)]
+    texts = [pool[i] for i in rng.integers(0, 300, n)]
+    texts[n - 1] = "A" * 41 if last == "unique" else texts[0]
+    rep, copies, distinct = ref_classes(texts)
+    is_rep = rep == np.arange(n, dtype=np.uint64)
+    d = resident(ctx, texts)
+    try:
+        with ctx.table_classes(d) as c:
+            assert c.distinct == distinct
+
+            def select(lo, hi):
+                def run(cap, on_device, outs):
+                    if on_device:
+                        return None, c.select(lo, hi, cap=cap, on_device=True, out=tuple(outs))
+                    got = c.select(lo, hi, cap=cap, want=tuple(outs))
+                    return got[:2], got[2]
+                return run
+
+            for lo, hi in ((1, NONE), (2, NONE), (3, 2)):
+                want = np.flatnonzero(is_rep & (copies >= lo) & (copies <= hi)).astype(np.uint64)
+                assert (len(want) == 0) == (lo > hi)
+                check_select_forms(ctx, select(lo, hi), (want, copies[want]), f"n={n} {last}: select({lo}, {hi})")
+            assert (last == "unique") == bool(is_rep[n - 1])
+
+            def members(s):
+                def run(cap, on_device, outs):
+                    if on_device:
+                        return None, c.members(s, cap=cap, on_device=True, out=outs[0])
+                    if not outs[0]:
+                        n_out = C.c_uint64()
+                        assert pkg.lib().dnagpu_seq_classes_members(ctx.h, c.h, s, None, cap, C.byref(n_out), 0) == 0
+                        return (None,), n_out.value
+                    ids, n_out = c.members(s, cap=cap)
+                    return (ids,), n_out
+                return run
+
+            for s in (0, n - 1, int(np.argmax(copies))):
+                want = np.flatnonzero(rep == rep[s]).astype(np.uint64)
+                check_select_forms(ctx, members(s), (want,), f"n={n} {last}: members({s})")
+    finally:
+        d.free()
+
+
+def classes_phase_names(c):
+    """the phase names dnagpu_last_phase_times reports after dnagpu_table_classes over 20 reads, two of them longer than
+    65,536 bases"""
+    rng = np.random.default_rng(SEED + 900)
+    texts = [random_text(rng, 150) for _ in range(20)]
+    texts[3], texts[11] = random_text(rng, 70_000), random_text(rng, 66_000)
+    d = resident(c, texts)
+    c.set_profiling(True)
+    try:
+        with c.table_classes(d) as cl:
+            names = [name for name, _ in c.last_phase_times()]
+            assert cl.distinct == 20
+    finally:
+        c.set_profiling(False)
+        d.free()
+    return names
+
+
+CLASSES_PHASE_NAMES = ["seqeq_fingerprint", "seqeq_sort", "seqeq_verify", "seqeq_copies"]   # (profiles and tools key on these names)
+
+
+@pytest.mark.gpu
+def test_phase_names_of_the_classes(ctx):
+    assert classes_phase_names(ctx) == CLASSES_PHASE_NAMES
 
 
 @pytest.mark.gpu

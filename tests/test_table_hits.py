@@ -608,6 +608,63 @@ def test_hits_read_windows_and_every_select_shape(ctx, sets, dbg, pkg):
         assert n.value == 77
 
 
+def check_select_forms(ctx, run, wants, what):
+    """one select against the expected columns `wants` (their length = the total): caps around the total into host arrays and
+    into device buffers of exactly min(total, cap) entries, then each output missing in turn and all of them missing.
+    run(cap, on_device, outs) -> (the host columns or None, n_out): outs = one bool (host: wanted) or device pointer per column"""
+    total = len(wants[0])
+    for cap in sorted({0, max(total - 1, 0), total, total + 1}):
+        m = min(total, cap)
+        got, n_out = run(cap, False, [True] * len(wants))
+        assert n_out == total and all(np.array_equal(a, w[:m]) for a, w in zip(got, wants)), f"{what}: cap={cap}"
+        dev = [ctx.buffer_alloc(8 * m) if m else None for _ in wants]
+        assert run(cap, True, dev)[1] == total, f"{what}: cap={cap}, device outputs"
+        for p, w in zip(dev, wants):
+            if p is not None:
+                assert np.array_equal(ctx.download_u64(p, m), w[:m]), f"{what}: cap={cap}, device outputs"
+                ctx.buffer_free(p)
+    keeps = [[j != i for j in range(len(wants))] for i in range(len(wants))] + [[False] * len(wants)]
+    for keep in keeps if total else []:
+        got, n_out = run(total, False, keep)
+        assert n_out == total, f"{what}: outputs {keep}"
+        assert all((a is None) if not w else np.array_equal(a, e) for a, e, w in zip(got, wants, keep)), f"{what}: outputs {keep}"
+        dev = [ctx.buffer_alloc(8 * total) if w else None for w in keep]
+        assert run(total, True, dev)[1] == total, f"{what}: device outputs {keep}"
+        for p, e in zip(dev, wants):
+            if p is not None:
+                assert np.array_equal(ctx.download_u64(p, total), e), f"{what}: device outputs {keep}"
+                ctx.buffer_free(p)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [2048, 2049])
+def test_select_at_the_tile_edge(ctx, sets, dbg, n):
+    """select over one full select tile and over one sequence more, that one selected, in every output form
+    (check_select_forms), with a select of nothing"""
+    k = 16
+    src = source_text(SEED + 1, 30_000, k)
+    rng = np.random.default_rng(13)
+    texts = cut_table(src, rng.choice([5, 16, 17, 20, 24], n).tolist(), SEED + 13, from_src=rng.random(n) < 0.5)
+    texts[n - 1] = src[300:320]
+    sk, sc = source_groups(src, k)
+    rows, hits = ref_hits(texts, k, sk, sc)
+    strictly_between(rows, hits)
+    d = resident(ctx, texts)
+    with ctx.table_hits(d, sets(src, k)) as sh:
+        d.free()
+        for lo, hi, frac in ((1, U64_MAX, (0, 1)), (0, U64_MAX, (1, 1)), (9, 3, (0, 1))):
+            wants = ref_select(0, rows, hits, lo, hi, *frac)
+            assert (len(wants[0]) == 0) == (lo > hi) and (lo > hi or wants[0][-1] == n - 1)
+
+            def run(cap, on_device, outs):
+                if on_device:
+                    return None, sh.select(lo, hi, frac, cap=cap, on_device=True, out=tuple(outs))
+                got = sh.select(lo, hi, frac, cap=cap, want=tuple(outs))
+                return got[:3], got[3]
+
+            check_select_forms(ctx, run, wants, f"n={n}: select({lo}, {hi}, {frac})")
+
+
 @pytest.mark.gpu
 def test_glue_table_hits_over_batches(ctx, g, dbg):
     """300 short rows through the glue with a flush size that makes at least five batches: the ordinals are global, rows,
