@@ -89,7 +89,8 @@ __device__ __forceinline__ u32 sk_mix(u32 v) { return sk_mix_raw(v, 8u); }      
 //   the ~10^6 final ones (tried: final buckets of ~5 hash classes each, a third of them over sk_count's stage).
 //   d1 (< 2^b1) and d2 (< 16) therefore come from the m-mer's 30-bit VALUE, which a record's builder cuts from the tile's
 //   words at the minimum's position (once per record, not per row).
-// v_mul_u32_u24 is a full-rate instruction; the 32-bit multiply of sk_fine_word runs once per record.
+// v_mul_u32_u24 is a full-rate instruction; the 32-bit multiply of sk_fine_word runs once per record.  (It takes 24 bits
+// of each operand: of the 25 hash bits that order the m-mers, bits 7..30 enter d0 and bit 31 does not.)
 struct SkDigits {
     u32 d0, d1, d2;
 };
