@@ -236,6 +236,18 @@ void dnagpu::pool_free(dnagpu_ctx *ctx, void *p)
         }
 }
 
+int dnagpu::side_stream(dnagpu_ctx *ctx, size_t n_events)
+{
+    if (!ctx->stream2)
+        HIP_TRY(hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
+    while (ctx->sync_ev.size() < n_events) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        ctx->sync_ev.push_back(e);
+    }
+    return DNAGPU_OK;
+}
+
 HistPtr dnagpu::hist_new(u64 total, bool sorted)
 {
     HistPtr h(new (std::nothrow) dnagpu_hist());
@@ -326,10 +338,16 @@ extern "C" void dnagpu_destroy(dnagpu_ctx *ctx)
         return;
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
+    if (ctx->stream2)
+        hipStreamSynchronize(ctx->stream2);
     for (PoolBlock &b : ctx->pool)
         hipFree(b.ptr);
     for (hipEvent_t e : ctx->ev)
         hipEventDestroy(e);
+    for (hipEvent_t e : ctx->sync_ev)
+        hipEventDestroy(e);
+    if (ctx->stream2)
+        hipStreamDestroy(ctx->stream2);
     hipStreamDestroy(ctx->stream);
     if (ctx->mailbox)
         hipHostFree(ctx->mailbox);

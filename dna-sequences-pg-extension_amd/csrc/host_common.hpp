@@ -93,6 +93,11 @@ struct dnagpu_ctx {
     u64 *mailbox;
     u64 mailbox_seq = 0;      // sequence number of the last flagged read-back (read_back)
     unsigned debug_flags;     // DNAGPU_DEBUG_*
+    // A second stream of the context, for work that runs beside the main stream's inside ONE call (the record count:
+    // level 1 beside level 0), and the events the two order themselves with.  Made on first use (side_stream), kept for
+    // the life of the context.  Pool memory the side stream touches stays allocated until `stream` has waited for it.
+    hipStream_t stream2 = nullptr;
+    std::vector<hipEvent_t> sync_ev;
 };
 
 struct dnagpu_dna {
@@ -137,6 +142,8 @@ int pool_alloc(dnagpu_ctx *ctx, size_t bytes, void **out);
 // Buffers go back to the pool while kernels that use them may still be queued: every later user is
 // queued on the same stream, behind them.
 void pool_free(dnagpu_ctx *ctx, void *p);
+// ctx->stream2 and at least n_events untimed events in ctx->sync_ev: created once per context, on first use
+int side_stream(dnagpu_ctx *ctx, size_t n_events);
 
 template <typename T>
 int pool_alloc_t(dnagpu_ctx *ctx, size_t n, T **out)

@@ -1,7 +1,8 @@
 // sk_host.hip -- the host driver of the super-k-mer ("record") engine: geometry, level 0, levels 1-2, the tail that
 // counts the final buckets, and the entry points of the record exchange.  Host side only.
-// A count fills one SkParts stage by stage: level 0 (sk_level0 or sk_level0_slab), levels 1-2 (sk_levels12: the sk_l1_*
-// stages, sk_heavy_take, sk_level2) and the tail (count_sk_tail: the sk_tail_* stages over one SkTail).
+// A count fills one SkParts stage by stage: level 0 (sk_level0, or the slab sweep: sk_slab_*), levels 1-2 (sk_levels12: the
+// sk_l1_* stages, sk_heavy_take, sk_level2; behind a slab sweep sk_levels012_slab runs them, level 1 beside the sweep where
+// that pays: sk_l01_piped) and the tail (count_sk_tail: the sk_tail_* stages over one SkTail).
 #include "host_common.hpp"
 
 using namespace dnagpu;
@@ -31,7 +32,7 @@ constexpr u64 SK_BIG_LIMIT = 0xFFFFFFFFull;
 // bytes) instead of 8 -- sk_scatter1 3.6 - 3.9 instead of 4.9 - 5.2 ms at 3 Gbase (A/B on one box) -- and level 0 takes
 // the bit over (136 coarse buckets at 3 Gbase: its 16-byte stores still combine in L2, 2.2 MB of open lines per XCD).
 constexpr int SK_B1_MAX = 9;
-// From this many rows level 0 runs without its histogram sweep (sk_level0_slab).  Measured, slabs vs the exact pair:
+// From this many rows level 0 runs without its histogram sweep (sk_slab_begin).  Measured, slabs vs the exact pair:
 // 249 Mbase 2.16 vs 2.12 ms, 1 Gbase 8.31 vs 8.42, 3 Gbase 21.8 vs 22.4.
 constexpr u64 SK_SLAB_MIN_ROWS = (u64)1 << 29;
 
@@ -115,7 +116,7 @@ struct SkParts {
     SkGeom g;
     int k = 0;
     u64 n_expected = 0;         // the k-mers the records must hold (0 = not known: records received from other ranks)
-    // ---- level 0 (sk_level0, sk_level0_slab, or count_sk_received for records that arrive)
+    // ---- level 0 (sk_level0, sk_slab_begin, or count_sk_received for records that arrive)
     void *rec0 = nullptr;       // the records, coarse bucket after coarse bucket
     u64 rec0_cap = 0;           // the records rec0 has room for
     u64 n_recs = 0;             // records (after the slab sweep: slots, NULL records included)
@@ -250,11 +251,56 @@ static int sk_level0(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p, const SkRows &r
 // four tiles, evenly spaced) gives every coarse bucket's share of a chunk's records; every chunk then reserves that share
 // + 1/32 + six standard deviations + 24 slots in the bucket's region (one returning add per digit and chunk) and fills
 // them as the exact sweep fills its histogram ranges; what it does not use becomes NULL records, which level 1 skips
-// (~10 % of the slots at 3 Gbase).  *ok = false (nothing usable produced, the level-0 part of p is not filled: the caller
-// runs the exact pair) when the sampled buckets are uneven (repeats), when the regions pass 2^32 slots, or when a chunk ran
-// out of slots.  On success the coarse nodes cover their whole regions (p.lens[d] slots, NULL records included) and
-// p.n_recs / p.rec0_cap are slots.
-static int sk_level0_slab(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p, const SkRows &rows, bool *ok)
+// (~10 % of the slots at 3 Gbase).
+// Every chunk adds cap[d] to digit d's cursor, whatever it finds, so after the first c chunks of the chunk list the records
+// of digit d are the slots [start[d], start[d] + c cap[d]) of its region -- known on the host before anything runs, with
+// no read-back.  The sweep may therefore run in several launches over consecutive ranges of its chunks (sk_slab_piece),
+// all on the one slab table, and level 1 can start on a piece's records while the next piece is cut (sk_l01_piped).
+//
+// A PIPELINED sweep has SK_L0_PIECES pieces of 512 chunks each: two workgroups of sk_scatter0 per CU (half of what fits)
+// leave the registers and the LDS for one workgroup of sk_scatter1 beside them -- the only mix of the two that fits a CU; a
+// full set of 1024 leaves no room, and level 1 then only starts as the sweep drains.  At half its waves, and with a
+// neighbour, a piece runs at ~2/3 of the sweep's rate: at 3 Gbase level 0 takes 5.9 ms instead of 4.2, and hides 2.3 of
+// level 1's 3.25 ms (a kernel trace: pieces of 1.15, 1.57, 1.57, 1.56 ms, level 1 beside the last three 1.53 - 1.55 ms
+// each, its last piece 0.86 ms alone).  Measured on one box (ms per step, two runs each; before: 17.83 / 17.84): 1024 chunks
+// in 2 pieces 17.56 / 17.57, 2048 in 4 17.27 / 17.30, 3072 in 6 17.36 / 17.48 (shorter chunks: more slack per slab, more
+// NULL records), 2048 in 2 -- full sets -- 17.97 / 17.99, 1024 in 1 17.88 / 18.02.
+// It pays from SK_PIPE_MIN_ROWS rows of ONE sequence only.  The unpipelined sweep costs 1.07 ms per Grow at 0.6 and 1.2 Gbase
+// but 1.25 at 2 and 1.4 at 3 Gbase (more coarse buckets: more open lines per workgroup), the pieces ~2.0 at every size:
+// levels 0 + 1 side by side against one after the other, one box, 0.6 Gbase 1.49 vs 1.31 ms, 1.2 Gbase 2.71 vs 2.57,
+// 2 Gbase 4.83 vs 4.71, 3 Gbase 6.86 vs 7.46.  A table of 150-base reads (1.5 Gbase) lost more, 3.55 vs 3.11: tables are
+// not pipelined.  (DNAGPU_DEBUG_SLAB0 / _SLAB0_OVERFLOW pipeline every length, tables too: the tests.)
+#ifndef SK_L0_PIECES_N
+#define SK_L0_PIECES_N 4
+#endif
+constexpr u32 SK_L0_PIECES = SK_L0_PIECES_N;
+constexpr u64 SK_PIPE_MIN_ROWS = (u64)5 << 29;
+// The chunks of a sweep.  Unpipelined: 1024, one resident set of workgroups -- a chunk's share of a bucket is then ~2,400
+// records at 3 Gbase, and the six standard deviations of slack it needs are 12 % of them (with the exact pair's 4096 chunks
+// they would be 25 %).  Pipelined: SK_L0_PIECES half sets (17 %).
+constexpr u64 SK_SLAB_CHUNKS = 1024, SK_SLAB_CHUNKS_PIPED = 512 * SK_L0_PIECES;
+
+struct SkSlab {                     // a slab sweep that is ready to run (sk_slab_begin)
+    SkLevel l0;                     // l0.chunks: the chunks of rows
+    u32 *slab = nullptr;            // the slab table (see sk_scatter0_kernel)
+    std::vector<u32> cap;           // per digit: the slots a chunk reserves
+    u64 span = 0;                   // the slots of all regions
+    bool pipe = false;              // chunked for SK_L0_PIECES pieces with level 1 beside them
+};
+
+// the chunks [*a, *b) of piece i of a pipelined sweep over n_chunks chunks: the first pieces take ceil(n_chunks / pieces) each
+static void sk_piece_range(u32 n_chunks, u32 i, u32 *a, u32 *b)
+{
+    const u32 per = (n_chunks + SK_L0_PIECES - 1) / SK_L0_PIECES;
+    *a = std::min(n_chunks, i * per);
+    *b = std::min(n_chunks, (i + 1) * per);
+}
+
+// The sample, the slab table, the regions and their buffer (sl.pipe, set by the caller, decides the chunks).  *ok = false (nothing usable produced: the caller runs the exact
+// pair) when the sampled buckets are uneven (repeats) or the regions pass 2^32 slots.  Else the level-0 part of p is
+// filled as the sweep will leave it if no chunk runs out of slots (sk_slab_status): the coarse nodes cover their whole
+// regions (p.lens[d] slots, NULL records included), p.n_recs / p.rec0_cap are slots, and rec0 belongs to ps.
+static int sk_slab_begin(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p, const SkRows &rows, SkSlab &sl, bool *ok)
 {
     hipStream_t st = ctx->stream;
     const dnagpu_dna *dna = rows.dna;
@@ -264,12 +310,10 @@ static int sk_level0_slab(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p, const SkRo
     *ok = false;
     const u32 r0n = 1u << g.r0bits;
     const u64 tile = (u64)sk_tile_rows();
-    // (1024 chunks = one resident set of workgroups: a chunk's share of a bucket is then ~2,400 records, and the six
-    // standard deviations of slack it needs are 12 % of them -- with the exact pair's 4096 chunks they would be 25 %)
     Node *cur = nullptr;
     u32 chunk_rows = 0;
-    SkLevel l0;
-    RC_TRY(sk_level0_begin(ctx, ps, n, g.r0bits, 1024, &cur, &chunk_rows, &l0));
+    SkLevel &l0 = sl.l0;
+    RC_TRY(sk_level0_begin(ctx, ps, n, g.r0bits, sl.pipe ? SK_SLAB_CHUNKS_PIPED : SK_SLAB_CHUNKS, &cur, &chunk_rows, &l0));
     if (l0.n_chunks == 0)
         return DNAGPU_OK;
     // ---- the sample
@@ -279,30 +323,32 @@ static int sk_level0_slab(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p, const SkRo
     for (u32 i = 0; i < n_samp; i++)
         sampled += std::min<u64>(samp_len, n - (u64)i * samp_stride);
     Chunk *samp = nullptr;
-    u32 *est = nullptr, *slab = nullptr;
+    u32 *est = nullptr;
     Node *nodes = nullptr;
     RC_TRY(ps.alloc((size_t)n_samp, &samp));
     RC_TRY(ps.alloc((size_t)sk_max_c0(), &est));
-    RC_TRY(ps.alloc((size_t)sk_slab_words(), &slab));
+    RC_TRY(ps.alloc((size_t)sk_slab_words(), &sl.slab));
     RC_TRY(ps.alloc((size_t)r0n, &nodes));
     prof_mark(ctx, "sk_sample0");
     HIP_TRY(hipMemsetAsync(est, 0, (size_t)sk_max_c0() * sizeof(u32), st));
     HIP_TRY(launch_sk_sample_chunks(samp, n_samp, (u32)samp_stride, (u32)samp_len, (u32)n, st));
     HIP_TRY(launch_sk_level0(false, samp, n_samp, dna->words, dna->n_words, first, k, g.c0n, (u32)g.b1, (u32)g.r0bits, nullptr, nullptr,
                              nullptr, st, est, rows.marks, rows.n_mark_words));
-    HIP_TRY(launch_sk_slab_init(est, (u32)g.r0bits, chunk_rows, (u32)sampled, l0.n_chunks, slab, nodes, st));
+    HIP_TRY(launch_sk_slab_init(est, (u32)g.r0bits, chunk_rows, (u32)sampled, l0.n_chunks, sl.slab, nodes, st));
     std::vector<u32> h_est(r0n);
     RC_TRY(read_back(ctx, h_est.data(), est, (size_t)r0n * sizeof(u32)));
     // even buckets?  (a repeated stretch sends its records to the few buckets of its minimizers: see sk_l1_route)
     u64 tot = 0, span = 0, span1 = 0;
-    p.lens.assign(r0n, 0);
+    std::vector<u32> lens(r0n, 0);
+    sl.cap.assign(r0n, 0);
     for (u32 d = 0; d < r0n; d++) {
         tot += h_est[d];
-        const u64 len = (u64)sk_slab_cap(h_est[d], chunk_rows, sampled) * l0.n_chunks;
+        sl.cap[d] = sk_slab_cap(h_est[d], chunk_rows, sampled);
+        const u64 len = (u64)sl.cap[d] * l0.n_chunks;
         span += len;
         if (len > 0xFFFFFFFFull)
             return DNAGPU_OK;
-        p.lens[d] = (u32)len;
+        lens[d] = (u32)len;
         span1 += sk_spec_span((u32)len, g.b1);
     }
     if (tot == 0 || !sk_even(h_est.data(), r0n, 1.05) || span > 0xFFFFFFFFull)
@@ -310,18 +356,9 @@ static int sk_level0_slab(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p, const SkRo
     const u64 cap = std::max<u64>(span, span1 <= 0xFFFFFFFFull ? span1 : 0);
     void *rec0 = nullptr;
     RC_TRY(pool_alloc(ctx, (size_t)std::max<u64>(cap, 1) * 16, &rec0));
-    prof_mark(ctx, "sk_scatter0");
-    const hipError_t e = launch_sk_level0(true, l0.chunks, l0.n_chunks, dna->words, dna->n_words, first, k, g.c0n, (u32)g.b1,
-                                          (u32)g.r0bits, nullptr, nullptr, rec0, st, slab, rows.marks, rows.n_mark_words);
-    u32 status[2] = {1, 0};
-    int rc = e == hipSuccess ? read_back(ctx, status, slab + 18 * (size_t)sk_max_c0(), sizeof status) : DNAGPU_ERR_HIP;
-    if (rc != DNAGPU_OK || status[0] || status[1] != (u32)span || (ctx->debug_flags & DNAGPU_DEBUG_SLAB0_OVERFLOW)) {
-        pool_free(ctx, rec0);                      // (ordered behind the sweep on this stream)
-        if (e != hipSuccess)
-            set_err("sk_scatter0 (slabs): %s", hipGetErrorString(e));
-        return rc;
-    }
     ps.ptrs.push_back(rec0);
+    sl.span = span;
+    p.lens.swap(lens);
     p.rec0 = rec0;
     p.rec0_cap = cap;
     p.coarse = nodes;
@@ -329,6 +366,39 @@ static int sk_level0_slab(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p, const SkRo
     p.n_recs = span;
     *ok = true;
     return DNAGPU_OK;
+}
+
+// the chunks [a, b) of the sweep, on the main stream
+static int sk_slab_piece(dnagpu_ctx *ctx, const SkParts &p, const SkRows &rows, const SkSlab &sl, u32 a, u32 b)
+{
+    const dnagpu_dna *dna = rows.dna;
+    const SkGeom &g = p.g;
+    const hipError_t e = launch_sk_level0(true, sl.l0.chunks + a, b - a, dna->words, dna->n_words, rows.first, p.k, g.c0n, (u32)g.b1,
+                                          (u32)g.r0bits, nullptr, nullptr, p.rec0, ctx->stream, sl.slab, rows.marks, rows.n_mark_words);
+    if (e != hipSuccess) {
+        set_err("sk_scatter0 (slabs): %s", hipGetErrorString(e));
+        return DNAGPU_ERR_HIP;
+    }
+    return DNAGPU_OK;
+}
+
+// the sweep's verdict from its two status words (after the LAST piece): false when a chunk ran out of slots, or the test
+// flag says so
+static bool sk_slab_ok(const dnagpu_ctx *ctx, const SkSlab &sl, const u32 status[2])
+{
+    return !status[0] && status[1] == (u32)sl.span && !(ctx->debug_flags & DNAGPU_DEBUG_SLAB0_OVERFLOW);
+}
+
+// A sweep that is not to be used after all (a chunk ran out of slots): the level-0 part of p is as it was before
+// sk_slab_begin, and rec0 is free again for the exact pair (ordered behind the sweep on the main stream).
+static void sk_slab_give_up(PoolScope &ps, SkParts &p)
+{
+    ps.free_now(p.rec0);
+    p.rec0 = nullptr;
+    p.rec0_cap = p.n_recs = 0;
+    p.coarse = nullptr;
+    p.n_coarse = 0;
+    p.lens.clear();
 }
 
 // ---------------------------------------------------------------- levels 1 and 2
@@ -344,6 +414,7 @@ struct SkL1 {
     std::vector<u32> kc, rcn;       // kcount and d_lens on the host (sk_l1_lens_to_host)
     u64 span = 0;                   // the slots of all regions of a speculative sweep
     u32 *rstart = nullptr, *rcapv = nullptr;     // SpeculativeSampled: the regions' starts and capacities
+    u32 *sp = nullptr;              // Speculative: first region and slots per region of every coarse node (sk_l1_spec_begin)
     void *rec1 = nullptr;           // level 1's output buffer: the speculative sweep allocates it, else the exact scatter
     bool rec1_kept = false;         // p.heavy lives in rec1 (sk_heavy_take with DNAGPU_DEBUG_HEAVY_EXPAND): level 2 does not free it
 };
@@ -374,21 +445,28 @@ static int sk_l1_plan(dnagpu_ctx *ctx, PoolScope &ps, const SkParts &p, SkL1 &l1
     return DNAGPU_OK;
 }
 
-// mid-bucket k-mer and record counts to the host (the list is short), with `extra` words behind the record counts
-static int sk_l1_lens_to_host(dnagpu_ctx *ctx, SkL1 &l1, u32 extra)
+// mid-bucket k-mer and record counts to the host (the list is short), with `extra` words behind the record counts; in
+// the same wait, two more device words (more -> more_host) where the caller has some: level 0's status
+static int sk_l1_lens_to_host(dnagpu_ctx *ctx, SkL1 &l1, u32 extra, const u32 *more = nullptr, u32 *more_host = nullptr)
 {
     hipStream_t st = ctx->stream;
-    const size_t nb = (size_t)l1.lv.n_next * sizeof(u32), nb2 = nb + (size_t)extra * sizeof(u32);
-    if (nb + nb2 <= MAILBOX_BYTES - 8) {          // both lists through the pinned mailbox, one wait (its last word is read_back's flag)
+    const size_t nb = (size_t)l1.lv.n_next * sizeof(u32), nb2 = nb + (size_t)extra * sizeof(u32), nb3 = more ? 2 * sizeof(u32) : 0;
+    if (nb + nb2 + nb3 <= MAILBOX_BYTES - 8) {    // the lists through the pinned mailbox, one wait (its last word is read_back's flag)
         char *mb = reinterpret_cast<char *>(ctx->mailbox);
         HIP_TRY(hipMemcpyAsync(mb, l1.kcount, nb, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(mb + nb, l1.d_lens, nb2, hipMemcpyDeviceToHost, st));
+        if (more)
+            HIP_TRY(hipMemcpyAsync(mb + nb + nb2, more, nb3, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         memcpy(l1.kc.data(), mb, nb);
         memcpy(l1.rcn.data(), mb + nb, nb2);
+        if (more)
+            memcpy(more_host, mb + nb + nb2, nb3);
     } else {
         HIP_TRY(hipMemcpyAsync(l1.kc.data(), l1.kcount, nb, hipMemcpyDeviceToHost, st));
         RC_TRY(read_back(ctx, l1.rcn.data(), l1.d_lens, nb2));
+        if (more)
+            RC_TRY(read_back(ctx, more_host, more, nb3));
     }
     return DNAGPU_OK;
 }
@@ -403,24 +481,38 @@ static int sk_l1_lens_to_host(dnagpu_ctx *ctx, SkL1 &l1, u32 extra)
 // standard deviations + 128 slots per mid bucket, so that a heavy mid bucket gets a region of its size.  One more wait
 // for the host (the regions' total decides the buffer); a region that overflows all the same (bursts the sample missed)
 // falls back to the exact level like every speculative sweep.  Regions that do not fit rec0: Exact.
+// The part of the route decision that needs no record: can level 1 be speculative at all (*any_spec), and if so, are the
+// coarse buckets even, so that the regions follow from their sizes alone (*plain; l1.span = their slots)?  That is known
+// from p.lens -- after a slab sweep the sizes of the coarse REGIONS, so before the first row has been cut.
+static void sk_l1_route_plain(const dnagpu_ctx *ctx, const SkParts &p, SkL1 &l1, bool *any_spec, bool *plain)
+{
+    *any_spec = *plain = false;
+    if (p.lens.empty() || (ctx->debug_flags & DNAGPU_DEBUG_NO_SPEC1) || p.n_coarse > (u32)sk_max_c0() || l1.lv.n_chunks == 0)
+        return;
+    u64 span = 0;
+    const bool even = sk_even(p.lens.data(), p.n_coarse, 1.02, p.g.b1, &span);
+    if (even && !(ctx->debug_flags & DNAGPU_DEBUG_SAMPLE1)) {
+        if (span <= p.rec0_cap && span <= 0xFFFFFFFFull) {
+            l1.span = span;
+            *any_spec = *plain = true;
+        }
+        return;
+    }
+    *any_spec = true;
+}
+
 static int sk_l1_route(dnagpu_ctx *ctx, PoolScope &ps, const SkParts &p, SkL1 &l1, SkL1Route *route)
 {
     hipStream_t st = ctx->stream;
     const u32 n_coarse = p.n_coarse, n_mid = l1.lv.n_next;
     const u32 *host_lens = p.lens.data();
     *route = SkL1Route::Exact;
-    if (p.lens.empty() || (ctx->debug_flags & DNAGPU_DEBUG_NO_SPEC1) || n_coarse > (u32)sk_max_c0() || l1.lv.n_chunks == 0)
+    bool any_spec = false, plain = false;
+    sk_l1_route_plain(ctx, p, l1, &any_spec, &plain);
+    if (plain)
+        *route = SkL1Route::Speculative;
+    if (!any_spec || plain)
         return DNAGPU_OK;
-    u64 span = 0;
-    const bool even = sk_even(host_lens, n_coarse, 1.02, p.g.b1, &span);
-    const bool force_sample = (ctx->debug_flags & DNAGPU_DEBUG_SAMPLE1) != 0;
-    if (even && !force_sample) {
-        if (span <= p.rec0_cap && span <= 0xFFFFFFFFull) {
-            l1.span = span;
-            *route = SkL1Route::Speculative;
-        }
-        return DNAGPU_OK;
-    }
     std::vector<Chunk> samp;
     const u32 slen = sk_sample1_len(), sstep = slen * sk_sample1_every();
     for (u32 i = 0; i < n_coarse; i++)
@@ -461,31 +553,49 @@ static int sk_l1_route(dnagpu_ctx *ctx, PoolScope &ps, const SkParts &p, SkL1 &l
 // The speculative sweep: no histogram.  *moved = the records are in l1.rec1 and l1.kc / l1.rcn hold the mid buckets'
 // counts; false = a region overflowed (or the test flag says so): kcount is zeroed again and the exact stages run, into
 // the same rec1.
-static int sk_l1_speculative(dnagpu_ctx *ctx, PoolScope &ps, const SkParts &p, SkL1 &l1, SkL1Route route, bool *moved)
+// Its three steps: the regions, their cursors and the output buffer (sk_l1_spec_begin); the sweep, which may come in
+// several launches over disjoint ranges of records -- they reserve from the same cursors and add to the same k-mer
+// counts; the mid nodes and the verdict (sk_l1_spec_end; l0_status: see sk_l1_lens_to_host).
+static int sk_l1_spec_begin(dnagpu_ctx *ctx, PoolScope &ps, const SkParts &p, SkL1 &l1, SkL1Route route)
+{
+    const bool sampled = route == SkL1Route::SpeculativeSampled;
+    RC_TRY(ps.alloc((size_t)2 * p.n_coarse, &l1.sp));
+    u32 *status = l1.d_lens + l1.lv.n_next;       // [0] slots of all regions, [1] past 2^32, [2] overflow
+    prof_mark(ctx, "sk_spec1");
+    HIP_TRY(launch_sk_spec_regions(p.coarse, p.n_coarse, l1.sp, status, l1.gcur, ctx->stream, sampled ? l1.rstart : nullptr));
+    RC_TRY(pool_alloc(ctx, (size_t)std::max<u64>(std::max(p.n_recs, l1.span), 1) * 16, &l1.rec1));
+    ps.ptrs.push_back(l1.rec1);
+    return DNAGPU_OK;
+}
+
+static int sk_l1_spec_end(dnagpu_ctx *ctx, const SkParts &p, SkL1 &l1, SkL1Route route, bool *moved, const u32 *l0_status = nullptr,
+                          u32 *l0_status_host = nullptr)
 {
     hipStream_t st = ctx->stream;
     const bool sampled = route == SkL1Route::SpeculativeSampled;
     const u32 n_mid = l1.lv.n_next;
     u32 *const rstart = sampled ? l1.rstart : nullptr, *const rcapv = sampled ? l1.rcapv : nullptr;
-    u32 *sp = nullptr;
-    RC_TRY(ps.alloc((size_t)2 * p.n_coarse, &sp));
-    u32 *status = l1.d_lens + n_mid;              // [0] slots of all regions, [1] past 2^32, [2] overflow
-    prof_mark(ctx, "sk_spec1");
-    HIP_TRY(launch_sk_spec_regions(p.coarse, p.n_coarse, sp, status, l1.gcur, st, rstart));
-    RC_TRY(pool_alloc(ctx, (size_t)std::max<u64>(std::max(p.n_recs, l1.span), 1) * 16, &l1.rec1));
-    ps.ptrs.push_back(l1.rec1);
-    prof_mark(ctx, "sk_scatter1");
-    HIP_TRY(launch_sk_scatter1_spec(p.coarse, l1.lv.chunks, l1.lv.n_chunks, p.rec0, l1.rec1, l1.gcur, sp, l1.kcount, status + 2, st,
-                                    rstart, rcapv));
-    HIP_TRY(launch_sk_spec_nodes(p.coarse, p.n_coarse, sp, l1.gcur, l1.lv.next, status + 2, st, rstart, rcapv));
+    u32 *status = l1.d_lens + n_mid;
+    HIP_TRY(launch_sk_spec_nodes(p.coarse, p.n_coarse, l1.sp, l1.gcur, l1.lv.next, status + 2, st, rstart, rcapv));
     HIP_TRY(launch_sk_node_lens(l1.lv.next, n_mid, l1.d_lens, st));
-    RC_TRY(sk_l1_lens_to_host(ctx, l1, 3));
+    RC_TRY(sk_l1_lens_to_host(ctx, l1, 3, l0_status, l0_status_host));
     const u32 *stw = l1.rcn.data() + n_mid;
     *moved = !((!sampled && stw[0] != (u32)l1.span) || (!sampled && stw[1]) || stw[2] ||
                (ctx->debug_flags & DNAGPU_DEBUG_SPEC1_OVERFLOW));
     if (!*moved)
         HIP_TRY(hipMemsetAsync(l1.kcount, 0, (size_t)std::max<u32>(n_mid, 1) * sizeof(u32), st));
     return DNAGPU_OK;
+}
+
+static int sk_l1_speculative(dnagpu_ctx *ctx, PoolScope &ps, const SkParts &p, SkL1 &l1, SkL1Route route, bool *moved)
+{
+    const bool sampled = route == SkL1Route::SpeculativeSampled;
+    RC_TRY(sk_l1_spec_begin(ctx, ps, p, l1, route));
+    prof_mark(ctx, "sk_scatter1");
+    HIP_TRY(launch_sk_scatter1_spec(p.coarse, l1.lv.chunks, l1.lv.n_chunks, p.rec0, l1.rec1, l1.gcur, l1.sp, l1.kcount,
+                                    l1.d_lens + l1.lv.n_next + 2, ctx->stream, sampled ? l1.rstart : nullptr,
+                                    sampled ? l1.rcapv : nullptr));
+    return sk_l1_spec_end(ctx, p, l1, route, moved);
 }
 
 // The exact histogram: the mid buckets' nodes from its prefix, and their k-mer and record counts on the host before any
@@ -631,15 +741,10 @@ static int sk_level2(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p, SkL1 &l1, const
 // Levels 1 and 2 over the coarse nodes of p (records of rec0, which this takes over).  On success the levels-1-2 part of
 // p is filled: the final buckets, and the heavy mid buckets that were taken out of the record path as a whole (p.heavy:
 // only with DNAGPU_DEBUG_HEAVY_EXPAND).  DNAGPU_SK_SKEWED (sk_l1_census): p.n_kmers is set, nothing has moved.
-static int sk_levels12(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p)
+// sk_levels12_planned: the same with level 1 planned already (sk_l1_plan); sk_levels12_rest: what follows the speculative
+// sweep (moved: it has left the records in l1.rec1).
+static int sk_levels12_rest(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p, SkL1 &l1, bool moved)
 {
-    SkL1 l1;
-    SkL1Route route;
-    RC_TRY(sk_l1_plan(ctx, ps, p, l1));
-    RC_TRY(sk_l1_route(ctx, ps, p, l1, &route));
-    bool moved = false;
-    if (route != SkL1Route::Exact)
-        RC_TRY(sk_l1_speculative(ctx, ps, p, l1, route, &moved));
     if (!moved)
         RC_TRY(sk_l1_histogram(ctx, p, l1));
     std::vector<u32> heavy_idx;
@@ -650,6 +755,150 @@ static int sk_levels12(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p)
     if (!heavy_idx.empty())
         RC_TRY(sk_heavy_take(ctx, ps, p, l1, heavy_idx, &split));
     return sk_level2(ctx, ps, p, l1, split);
+}
+
+static int sk_levels12_planned(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p, SkL1 &l1)
+{
+    SkL1Route route;
+    RC_TRY(sk_l1_route(ctx, ps, p, l1, &route));
+    bool moved = false;
+    if (route != SkL1Route::Exact)
+        RC_TRY(sk_l1_speculative(ctx, ps, p, l1, route, &moved));
+    return sk_levels12_rest(ctx, ps, p, l1, moved);
+}
+
+static int sk_levels12(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p)
+{
+    SkL1 l1;
+    RC_TRY(sk_l1_plan(ctx, ps, p, l1));
+    return sk_levels12_planned(ctx, ps, p, l1);
+}
+
+// ---------------------------------------------------------------- levels 0 and 1 side by side
+
+// The side stream of a call, from its first launch there until the main stream has been made to wait for it (joined): a
+// return before that -- an error -- waits for it on the host, since the scope's pool memory goes back on return.
+struct SideWork {
+    hipStream_t s, main;
+    bool joined = false;
+    SideWork(hipStream_t side, hipStream_t main_stream) : s(side), main(main_stream) {}
+    ~SideWork()
+    {
+        if (!joined) {
+            (void)hipStreamSynchronize(s);
+            (void)hipStreamSynchronize(main);
+        }
+    }
+};
+
+// Level 0 (slab sweep) and the plain speculative level 1, piece by piece: sk_scatter0 uses under a third of the memory
+// bandwidth and sk_scatter1 little of the vector units, so piece i of level 1 runs on the side stream while piece i + 1
+// of level 0 is cut on the main stream.  Level 1 is planned over the whole regions BEFORE the sweep (its regions, cursors
+// and k-mer counts are those of the unpipelined level); piece i's launch gets nodes of its own -- node d = the slots
+// that the chunks of level-0 piece i reserve in region d (see SK_L0_PIECES), with the planned node's split, child_base and
+// chunk_base, i.e. the same regions, cursors and counters -- and chunks over them, built on the host.  The main stream
+// waits for the side stream behind the last piece; level 0's status comes back with level 1's lens (one wait).
+// *slab_ok: the sweep is usable (else everything level 1 did here is dropped with it: sk_slab_give_up, and rec1 is free
+// again); *moved: as sk_l1_speculative.
+static int sk_l01_piped(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p, const SkRows &rows, const SkSlab &sl, SkL1 &l1, bool *slab_ok,
+                        bool *moved)
+{
+    hipStream_t st = ctx->stream;
+    const u32 n_coarse = p.n_coarse, chunk_recs = l1.chunk_recs;
+    RC_TRY(side_stream(ctx, SK_L0_PIECES + 1));
+    RC_TRY(sk_l1_spec_begin(ctx, ps, p, l1, SkL1Route::Speculative));
+    std::vector<Node> planned(n_coarse), pn;
+    RC_TRY(read_back(ctx, planned.data(), p.coarse, (size_t)n_coarse * sizeof(Node)));
+    std::vector<Chunk> pc;
+    u32 first_chunk[SK_L0_PIECES + 1];
+    for (u32 i = 0; i < SK_L0_PIECES; i++) {
+        u32 a = 0, b = 0;
+        sk_piece_range(sl.l0.n_chunks, i, &a, &b);
+        first_chunk[i] = (u32)pc.size();
+        for (u32 d = 0; d < n_coarse; d++) {
+            Node nd = planned[d];
+            nd.start += sl.cap[d] * a;
+            nd.len = sl.cap[d] * (b - a);
+            pn.push_back(nd);
+            for (u32 off = 0; nd.split && off < nd.len; off += chunk_recs) {
+                Chunk c;
+                c.node = d;
+                c.off = off;
+                c.len = std::min(chunk_recs, nd.len - off);
+                c.pad = 0;
+                pc.push_back(c);
+            }
+        }
+    }
+    first_chunk[SK_L0_PIECES] = (u32)pc.size();
+    Node *d_pn = nullptr;
+    Chunk *d_pc = nullptr;
+    RC_TRY(alloc1(ps, pn.size(), &d_pn));
+    RC_TRY(alloc1(ps, pc.size(), &d_pc));
+    SideWork side(ctx->stream2, st);             // (pn / pc are host vectors: an early way out waits for their copies too)
+    HIP_TRY(hipMemcpyAsync(d_pn, pn.data(), pn.size() * sizeof(Node), hipMemcpyHostToDevice, st));
+    if (!pc.empty())
+        HIP_TRY(hipMemcpyAsync(d_pc, pc.data(), pc.size() * sizeof(Chunk), hipMemcpyHostToDevice, st));
+    u32 *status1 = l1.d_lens + l1.lv.n_next;
+    prof_mark(ctx, "sk_scatter0");
+    for (u32 i = 0; i < SK_L0_PIECES; i++) {
+        u32 a = 0, b = 0;
+        sk_piece_range(sl.l0.n_chunks, i, &a, &b);
+        RC_TRY(sk_slab_piece(ctx, p, rows, sl, a, b));
+        HIP_TRY(hipEventRecord(ctx->sync_ev[i], st));
+        HIP_TRY(hipStreamWaitEvent(side.s, ctx->sync_ev[i], 0));
+        HIP_TRY(launch_sk_scatter1_spec(d_pn + (size_t)i * n_coarse, d_pc + first_chunk[i], first_chunk[i + 1] - first_chunk[i], p.rec0,
+                                        l1.rec1, l1.gcur, l1.sp, l1.kcount, status1 + 2, side.s, nullptr, nullptr));
+    }
+    prof_mark(ctx, "sk_scatter1");                // (from here: what of level 1 the sweep did not hide)
+    HIP_TRY(hipEventRecord(ctx->sync_ev[SK_L0_PIECES], side.s));
+    HIP_TRY(hipStreamWaitEvent(st, ctx->sync_ev[SK_L0_PIECES], 0));
+    side.joined = true;
+    u32 status0[2] = {1, 0};
+    RC_TRY(sk_l1_spec_end(ctx, p, l1, SkL1Route::Speculative, moved, sl.slab + 18 * (size_t)sk_max_c0(), status0));
+    *slab_ok = sk_slab_ok(ctx, sl, status0);
+    if (!*slab_ok) {
+        ps.free_now(l1.rec1);
+        l1.rec1 = nullptr;
+        *moved = false;
+    }
+    return DNAGPU_OK;
+}
+
+// Level 0 as a slab sweep and levels 1-2 behind it.  *done = false: the slabs gave up (sk_slab_begin, or a chunk ran out of
+// slots) and p is as it was -- the caller runs the exact pair and sk_levels12 over the whole sequence; nothing of what
+// level 1 did here is kept.  Level 1 is planned before the sweep; where the sweep is long enough for it to pay (see
+// SK_PIPE_MIN_ROWS) and level 1's route is the plain speculative one (even regions, no DNAGPU_DEBUG_NO_SPEC1 / _SAMPLE1),
+// the two levels run side by side (sk_l01_piped), else one after the other.
+static int sk_levels012_slab(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p, const SkRows &rows, bool *done)
+{
+    *done = false;
+    SkSlab sl;
+    sl.pipe = (ctx->debug_flags & (DNAGPU_DEBUG_SLAB0 | DNAGPU_DEBUG_SLAB0_OVERFLOW)) || (!rows.marks && rows.n >= SK_PIPE_MIN_ROWS);
+    bool ok = false;
+    RC_TRY(sk_slab_begin(ctx, ps, p, rows, sl, &ok));
+    if (!ok)
+        return DNAGPU_OK;
+    SkL1 l1;
+    RC_TRY(sk_l1_plan(ctx, ps, p, l1));
+    bool any_spec = false, plain = false, moved = false;
+    sk_l1_route_plain(ctx, p, l1, &any_spec, &plain);
+    const bool piped = sl.pipe && plain;
+    if (piped) {
+        RC_TRY(sk_l01_piped(ctx, ps, p, rows, sl, l1, &ok, &moved));
+    } else {
+        prof_mark(ctx, "sk_scatter0");
+        RC_TRY(sk_slab_piece(ctx, p, rows, sl, 0, sl.l0.n_chunks));
+        u32 status0[2] = {1, 0};
+        RC_TRY(read_back(ctx, status0, sl.slab + 18 * (size_t)sk_max_c0(), sizeof status0));
+        ok = sk_slab_ok(ctx, sl, status0);
+    }
+    if (!ok) {
+        sk_slab_give_up(ps, p);
+        return DNAGPU_OK;
+    }
+    *done = true;
+    return piped ? sk_levels12_rest(ctx, ps, p, l1, moved) : sk_levels12_planned(ctx, ps, p, l1);
 }
 
 // ---------------------------------------------------------------- the tail: counting the final buckets
@@ -930,8 +1179,8 @@ static int count_sk_tail(dnagpu_ctx *ctx, PoolScope &ps, const SkParts &p, u64 n
     return sk_tail_finish(ctx, ps, t, n, h);
 }
 
-// The whole count of rows of a sequence: level 0 (the slab sweep from SK_SLAB_MIN_ROWS rows, else -- or where the slabs
-// give up -- the exact pair), levels 1-2, the tail.
+// The whole count of rows of a sequence: level 0 (the slab sweep from SK_SLAB_MIN_ROWS rows, with levels 1-2 behind or
+// beside it: sk_levels012_slab; else -- or where the slabs give up -- the exact pair and sk_levels12), the tail.
 int dnagpu::count_sk(dnagpu_ctx *ctx, const SkRows &rows, int k, dnagpu_hist *h, u64 n_kmers_expected)
 {
     PoolScope ps(ctx);
@@ -939,13 +1188,14 @@ int dnagpu::count_sk(dnagpu_ctx *ctx, const SkRows &rows, int k, dnagpu_hist *h,
     p.g = sk_geometry(ctx, std::max<u64>(n_kmers_expected, 1), k);
     p.k = k;
     p.n_expected = n_kmers_expected;
-    bool slabs = false;
+    bool done = false;
     const unsigned dbg = ctx->debug_flags;
     if (!(dbg & DNAGPU_DEBUG_NO_SLAB0) && (rows.n >= SK_SLAB_MIN_ROWS || (dbg & (DNAGPU_DEBUG_SLAB0 | DNAGPU_DEBUG_SLAB0_OVERFLOW))))
-        RC_TRY(sk_level0_slab(ctx, ps, p, rows, &slabs));
-    if (!slabs)
+        RC_TRY(sk_levels012_slab(ctx, ps, p, rows, &done));
+    if (!done) {
         RC_TRY(sk_level0(ctx, ps, p, rows, true));
-    RC_TRY(sk_levels12(ctx, ps, p));
+        RC_TRY(sk_levels12(ctx, ps, p));
+    }
     return count_sk_tail(ctx, ps, p, n_kmers_expected, h);
 }
 
