@@ -19,9 +19,14 @@ hash        of an m-mer value v, in 32-bit arithmetic: (v & 0xFFFFFF) * 0x9E3779
 digits      d0 = ((g >> 16) * c0) >> 16 with g = (hash bits 7..30) * 0x9E3779 in 32 bits, c0 = dnagpu_sk_buckets(...)
             (sk_digit_word multiplies with the 24-bit multiply: of the 25 ordering bits the top one does not enter d0);
             f = v * 0x9E3779B1 in 32 bits, d2 = (f >> 19) & 15, d1 = (f >> 23) & (2^b1 - 1).
-            b1 is not exposed by the C-ABI and the geometry that chooses it is not restated here.  d1 is checked as "a function
-            of v, equal to f >> 23 masked to ONE width b1 <= 9 common to all records of a call": infer_b1() takes the
-            smallest width that holds every d1 seen, and the caller compares every record's d1 with d1_of(v, that width).
+            b1 is not exposed by the C-ABI.  d1 is checked as "a function of v, equal to f >> 23 masked to ONE width
+            b1 <= 9 common to all records of a call": infer_b1() takes the smallest width that holds every d1 seen, and the
+            caller compares every record's d1 with d1_of(v, that width).
+
+The second half restates the HOST's rules of levels 1 and 2 (sk_host.hip, sk_level1_kernels.hip) -- geometry(), spec_cap(),
+chunk_len(), even(), received_cap(), route(), heavy() -- and crafted_stream() makes record streams that put a chosen number
+of records into a chosen (coarse bucket, d1, d2): tests/test_sk_levels12.py feeds them to dnagpu_count_records.  These ARE
+written from the host code, one function per rule, each with the values worked out by hand that its test asserts.
 """
 import numpy as np
 
@@ -228,3 +233,299 @@ def mmer_at(d, off):
     up = np.where(s > 0, d.pay_hi << ((U64(64) - s) & U64(63)), U64(0))
     out = np.where(lo_part, (d.lo >> s) | up, d.pay_hi >> np.where(lo_part, 0, sh - 64).astype(np.uint64))
     return (out & U64((1 << (2 * m)) - 1)).astype(np.uint32)
+
+
+# ------------------------------------------------------------------ the host's rules of levels 1 and 2
+
+SK_LEAF_MEAN = 2500                    # planned k-mers per final bucket (sk_host.hip)
+SK_B1_MAX = 9                          # level 1 splits a coarse bucket at most 512 ways
+SK_MAX_C0 = 256                        # most coarse buckets (sk_device.hpp)
+SK_MID_LIMIT = 1 << 27                 # k-mers beyond which a mid bucket is heavy (unforced)
+SK_MID_RECORDS = 1 << 16               # records beyond which a mid bucket is heavy (unforced)
+SK1_TILE = 8192                        # records of a tile of sk_scatter1
+SK1_STAGE = SK1_TILE // 2 + 64         # records its stage holds: the half split of a full tile
+SKR_TILE = 8192                        # records of a tile of sk_regroup: longer mid buckets take the LONG kernel
+# dnagpu_set_debug flags that the rules below read (dnagpu.h; the GPU tie test compares them with the binding's)
+DEBUG_FORCE_SUPERKMER, DEBUG_HEAVY_EXPAND, DEBUG_NO_SPEC1, DEBUG_SPEC1_OVERFLOW, DEBUG_SAMPLE1 = 2, 4, 16, 32, 512
+
+
+class Geometry:
+    """b1, c0n, r0bits, mid_limit of one (global_rows, k, forced); n_coarse = 2^r0bits, R = 2^b1"""
+
+    def __repr__(self):
+        return f"Geometry(b1={self.b1}, c0n={self.c0n}, r0bits={self.r0bits}, mid_limit={self.mid_limit})"
+
+
+def geometry(global_rows, k, forced=False):
+    """restates sk_geometry (sk_host.hip).  By hand, k = 31 (leaf mean 2500): 40 000 rows -> 16 final, 1 mid bucket, b1 = 1,
+    c0n = 1; 160 000 -> 64, 4, b1 = 2, c0n = 1; 10 300 000 -> 4120, 258, b1 = 9, c0n = 1; 21 000 000 -> 8400, 525, b1 = 9,
+    c0n = 2.  r0bits = 1 in all four (never 0: one coarse bucket still has two coarse nodes, the second empty).
+    forced (DNAGPU_DEBUG_FORCE_SUPERKMER): mid_limit = 3 (rows / (c0n 2^b1) + 1); k = 23, 40 000 rows: leaf mean 225 * 10,
+    17 final, 2 mid buckets, b1 = 1, c0n = 1, mid_limit = 3 * 20 001 = 60 003."""
+    g = Geometry()
+    leaf_mean = min(SK_LEAF_MEAN, 225 * (k - mlen(k) + 2))
+    n_final = max(global_rows // leaf_mean, 16)
+    n_mid = (n_final + 15) // 16
+    g.b1 = 1
+    while g.b1 < SK_B1_MAX and (1 << g.b1) < n_mid:
+        g.b1 += 1
+    g.c0n = min((n_mid + (1 << g.b1) - 1) >> g.b1, SK_MAX_C0)
+    g.r0bits = 1
+    while (1 << g.r0bits) < g.c0n:
+        g.r0bits += 1
+    g.mid_limit = 3 * (global_rows // (g.c0n << g.b1) + 1) if forced else SK_MID_LIMIT
+    g.n_coarse, g.R = 1 << g.r0bits, 1 << g.b1
+    return g
+
+
+def spec_cap(length, R):
+    """restates sk_spec_cap (sk_level1_kernels.hip): the slots of one region of a speculative level 1.  By hand:
+    (8192, 2): 9216 / 2 + 79 = 4687 -> 4680; (40000, 4): 45000 / 4 + 79 = 11329 -> 11328; (60000, 512): 67500 / 512 = 131,
+    + 79 = 210 -> 208."""
+    return (((length + (length >> 3)) // R) + 72 + 7) & ~7
+
+
+def spec_span(length, bits):
+    """restates sk_spec_span: the slots of all 2^bits regions of a coarse bucket of `length` records (none for none)"""
+    return spec_cap(length, 1 << bits) << bits if length else 0
+
+
+def chunk_len(n_recs, target=4096, tile=SK1_TILE):
+    """restates sk_chunk_len (sk_host.hip): ~target chunks of whole tiles, four tiles at least.  By hand: up to
+    4096 * 32768 = 134 217 728 records the quotient is at most 32768 = four tiles, one more record gives five tiles."""
+    length = max(4 * tile, (n_recs + target - 1) // target)
+    return (length + tile - 1) // tile * tile
+
+
+def even(lens, tol=1.02):
+    """restates sk_even (sk_host.hip), in double precision as there: big * used <= tol * total + 64 * used.  By hand:
+    [20946, 20000]: 41892 <= 1.02 * 40946 + 128 = 41892.92 holds; [20947, 20000]: 41894 <= 41893.94 does not."""
+    lens = [int(x) for x in lens]
+    tot, big, used = sum(lens), max(lens, default=0), sum(1 for x in lens if x)
+    return float(big) * float(used) <= tol * float(tot) + 64.0 * float(used)
+
+
+def received_cap(blen, b1):
+    """restates sk_received_cap (sk_host.hip): the records the landing buffer of dnagpu_count_records has room for -- the
+    records or, where they stay below 2^32, the regions of a speculative level 1, whichever is more"""
+    n = sum(int(x) for x in blen)
+    span = sum(spec_span(min(int(x), 0xFFFFFFFF), b1) for x in blen)
+    return max(n, span) if span <= 0xFFFFFFFF else n
+
+
+def route(lens, flags, b1=SK_B1_MAX):
+    """restates sk_l1_route_plain (sk_host.hip) as dnagpu_count_records meets it (the coarse buckets' lengths are known and
+    the landing buffer is received_cap): "Exact" under DNAGPU_DEBUG_NO_SPEC1 or without records (no chunk), "Speculative" for
+    even buckets whose regions fit, "Sampled" for uneven ones or under DNAGPU_DEBUG_SAMPLE1 (the regions then come from
+    sk_sample1; whether the sweep is speculative after it is decided by their total)."""
+    lens = [int(x) for x in lens]
+    if (flags & DEBUG_NO_SPEC1) or not any(lens):
+        return "Exact"
+    if even(lens, 1.02) and not (flags & DEBUG_SAMPLE1):
+        span = sum(spec_span(x, b1) for x in lens)
+        return "Speculative" if span <= received_cap(lens, b1) and span <= 0xFFFFFFFF else "Exact"
+    return "Sampled"
+
+
+def heavy(kmers, records, mid_limit, forced):
+    """restates is_heavy of sk_l1_census (sk_host.hip): a mid bucket of more than mid_limit k-mers or -- unforced -- more than
+    SK_MID_RECORDS records"""
+    return kmers > mid_limit or (not forced and records > SK_MID_RECORDS)
+
+
+# ------------------------------------------------------------------ crafted record streams
+
+def record_fields(records):
+    """-> (d1, d2, length, null) per record, without cutting the k-mers (decode does that)"""
+    hi = np.ascontiguousarray(records, dtype=np.uint64).reshape(-1, 2)[:, 1]
+    return (((hi >> U64(D1_SHIFT)) & U64(D1_MASK)).astype(np.int64), ((hi >> U64(D2_SHIFT)) & U64(D2_MASK)).astype(np.int64),
+            ((hi >> U64(LEN_SHIFT)) & U64(31)).astype(np.int64) + 1, (hi >> U64(REC_NULL_BIT)) != 0)
+
+
+def _pack_payload(codes):
+    """(n, nb) 2-bit codes -> the two payload words of n records over all nb bases"""
+    c = np.asarray(codes).astype(np.uint64) & U64(3)
+    lo = np.zeros(len(c), dtype=np.uint64)
+    hi = np.zeros(len(c), dtype=np.uint64)
+    for i in range(c.shape[1]):
+        if i < 32:
+            lo |= c[:, i] << U64(2 * i)
+        else:
+            hi |= c[:, i] << U64(2 * (i - 32))
+    return lo, hi
+
+
+def encode_windows(lo, hi, length, k, d1, d2, null=False):
+    """encode(codes[:length + k - 1], k, d1, d2, multi=True, null=null) for many records at once: lo / hi = the payload words
+    of the whole strings (_pack_payload), cut to the record's bases here.  -> the flat uint64 array of the records.
+    (crafted_stream holds a sample of every stream against encode itself.)"""
+    length = np.asarray(length, dtype=np.int64)
+    if len(length) and not (1 <= length.min() and length.max() <= lmax(k)):
+        raise ValueError(f"records of {int(length.min())} .. {int(length.max())} k-mers at k = {k}")
+    nb2 = 2 * (length + k - 1)
+    lo_m = np.where(nb2 >= 64, ~U64(0), (U64(1) << np.minimum(nb2, 63).astype(np.uint64)) - U64(1))
+    hi_m = (U64(1) << np.clip(nb2 - 64, 0, 63).astype(np.uint64)) - U64(1)
+    out = np.empty((len(length), 2), dtype=np.uint64)
+    out[:, 0] = lo & lo_m
+    out[:, 1] = (hi & hi_m) | U64(1 << REC_MULTI_BIT) | ((length - 1).astype(np.uint64) << U64(LEN_SHIFT)) | \
+        (np.asarray(d1).astype(np.uint64) << U64(D1_SHIFT)) | (np.asarray(d2).astype(np.uint64) << U64(D2_SHIFT)) | \
+        (U64(1 << REC_NULL_BIT) if null else U64(0))
+    return out.reshape(-1)
+
+
+def _clashing(kmers, triple, owner):
+    """the owners (an id per k-mer) of k-mers whose value also occurs under another triple"""
+    order = np.argsort(kmers, kind="stable")
+    ks, ts = kmers[order], triple[order]
+    clash = (ks[1:] == ks[:-1]) & (ts[1:] != ts[:-1])
+    return np.unique(owner[order][1:][clash])
+
+
+def check_contract(records, bucket_of_record, k):
+    """The engine's contract on a stream: no k-mer value occurs under two different (coarse bucket, d1, d2) -- equal k-mers
+    must meet in ONE final bucket.  NULL records do not count.  Raises ValueError naming the first offending record."""
+    w = np.ascontiguousarray(records, dtype=np.uint64).reshape(-1, 2)
+    live = np.flatnonzero((w[:, 1] >> U64(REC_NULL_BIT)) == 0)
+    dec = decode(w[live], k)
+    triple = (np.asarray(bucket_of_record, dtype=np.int64)[live] << 13) | (dec.d1.astype(np.int64) << 4) | dec.d2.astype(np.int64)
+    bad = _clashing(dec.kmers, triple[dec.kmer_rec], dec.kmer_rec)
+    if len(bad):
+        raise ValueError(f"{len(bad)} records hold a k-mer that also occurs under another (bucket, d1, d2); first: record {int(live[bad[0]])}")
+
+
+def _lengths(want, n, lm, rng):
+    if want is None:
+        want = (1, lm)
+    if isinstance(want, tuple):
+        return rng.integers(want[0], want[1] + 1, n).astype(np.int64)
+    if np.ndim(want) == 0:
+        return np.full(n, int(want), dtype=np.int64)
+    out = np.asarray(want, dtype=np.int64)
+    if len(out) != n:
+        raise ValueError(f"{len(out)} lengths for {n} records")
+    return out
+
+
+def _interleaved(bucket, cls, run):
+    """the order that deals every bucket's records out class by class, `run` records at a time (a class that has run out is
+    passed over): run = 8192 over d1 gives tiles of one digit each, run = 1 over d2 gives every lane another d2"""
+    n = len(bucket)
+    by = np.lexsort((np.arange(n), cls, bucket))
+    b, c = bucket[by], cls[by]
+    new = np.ones(n, dtype=bool)
+    new[1:] = (b[1:] != b[:-1]) | (c[1:] != c[:-1])
+    first = np.flatnonzero(new)
+    r = np.arange(n) - np.repeat(first, np.diff(np.append(first, n)))
+    return by[np.lexsort((r, c, r // run, b))]
+
+
+def crafted_stream(k, spec, rng):
+    """A record stream with a chosen number of records in chosen (coarse bucket, d1, d2) -> (records: uint64[2n],
+    bucket_of_record: int64[n], truth_kmers: uint64[...]).  The records of a coarse bucket lie together, the buckets in
+    ascending order (one piece per bucket for dnagpu_count_records).  spec is a dict:
+      "groups"  [(bucket, d1, d2, n, lengths)]: n records for that final bucket; lengths = their k-mers: one number, (lo, hi)
+                for uniform draws, an array of n, or None for 1 .. lmax(k)
+      "copies"  (default 8) a group of n records draws its payload from a pool of ceil(n / copies) random "reads" of its own,
+                record i from read i mod pool: every read is used `copies` times (windows from its first base, so copies of
+                different lengths share their common k-mers)
+      "order"   of the real records inside every bucket: "shuffled" (default), "digit" (sorted by d1, then d2), "tiles"
+                (SK1_TILE records of one d1, then of the next: tile-interleaved), "lanes" (record i has the i-th d2 in turn),
+                "runs64" (64 records of one d2, 64 of the next), or a function (bucket, d1, d2, rng) -> permutation of the
+                records (given per record, grouped as listed) that keeps the buckets together and ascending
+      "nulls"   {bucket: positions}: NULL records (bit 63; random payload, digits and length) at these positions of the
+                bucket's final layout, the real records filling the others in their order
+    All records have SK_REC_MULTI set (nothing is claimed about their minimum m-mers: d1 and d2 are free).
+    The engine's contract -- no k-mer value under two different (bucket, d1, d2) -- is established here: the k-mers of all
+    reads (decode of the reads as records of lmax k-mers) are compared, and every read that holds a k-mer of another group
+    is drawn again, until none does (at k = 20 random reads do collide).  crafted_stream.redrawn counts the reads redrawn
+    by the last call.  A few records of every stream are held against encode()."""
+    groups = spec["groups"]
+    copies, order = int(spec.get("copies", 8)), spec.get("order", "shuffled")
+    lm = lmax(k)
+    nb_full = lm + k - 1
+    G = len(groups)
+    g_bucket = np.array([g[0] for g in groups], dtype=np.int64).reshape(G)
+    g_d1 = np.array([g[1] for g in groups], dtype=np.int64).reshape(G)
+    g_d2 = np.array([g[2] for g in groups], dtype=np.int64).reshape(G)
+    g_n = np.array([g[3] for g in groups], dtype=np.int64).reshape(G)
+    if G and (g_d1.min() < 0 or g_d1.max() > D1_MASK or g_d2.min() < 0 or g_d2.max() > D2_MASK or g_n.min() < 0):
+        raise ValueError("digits or counts out of range")
+    if len(set(zip(g_bucket.tolist(), g_d1.tolist(), g_d2.tolist()))) != G:
+        raise ValueError("a (bucket, d1, d2) listed twice")
+    n_real = int(g_n.sum())
+    grp = np.repeat(np.arange(G), g_n)
+    if G and all(g[4] is groups[0][4] for g in groups) and (groups[0][4] is None or np.ndim(groups[0][4]) == 0 or
+                                                               isinstance(groups[0][4], tuple)):
+        length = _lengths(groups[0][4], n_real, lm, rng)       # (one rule for all groups: one draw)
+    else:
+        length = np.concatenate([_lengths(g[4], int(g[3]), lm, rng) for g in groups]) if G else np.zeros(0, dtype=np.int64)
+    # ---- the pool of reads, group by group, free of k-mers shared between groups
+    g_pool = (g_n + copies - 1) // copies
+    pool_first = np.concatenate([[0], np.cumsum(g_pool)])
+    pool_grp = np.repeat(np.arange(G), g_pool)
+    codes = rng.integers(0, 4, (int(pool_first[-1]), nb_full), dtype=np.uint8)
+    pool_triple = (g_bucket << 13 | g_d1 << 4 | g_d2)[pool_grp]
+    crafted_stream.redrawn = 0
+    while True:
+        plo, phi = _pack_payload(codes)
+        dec = decode(encode_windows(plo, phi, np.full(len(codes), lm), k, g_d1[pool_grp], g_d2[pool_grp]), k)
+        bad = _clashing(dec.kmers, pool_triple[dec.kmer_rec], dec.kmer_rec)
+        if not len(bad):
+            break
+        codes[bad] = rng.integers(0, 4, (len(bad), nb_full), dtype=np.uint8)
+        crafted_stream.redrawn += len(bad)
+    rank = np.arange(n_real) - np.repeat(np.concatenate([[0], np.cumsum(g_n)])[:-1], g_n)
+    read = pool_first[grp] + rank % np.maximum(g_pool[grp], 1)
+    # ---- the order of the real records
+    bucket, d1, d2 = g_bucket[grp], g_d1[grp], g_d2[grp]
+    if callable(order):
+        perm = np.asarray(order(bucket, d1, d2, rng), dtype=np.int64)
+        if not np.array_equal(np.sort(perm), np.arange(n_real)) or np.any(np.diff(bucket[perm]) < 0):
+            raise ValueError("order: not a permutation that keeps the buckets together and ascending")
+    elif order == "shuffled":
+        perm = np.lexsort((rng.random(n_real), bucket))
+    elif order == "digit":
+        perm = np.lexsort((np.arange(n_real), d2, d1, bucket))
+    elif order == "tiles":
+        perm = _interleaved(bucket, d1, SK1_TILE)
+    elif order == "lanes":
+        perm = _interleaved(bucket, d2, 1)
+    elif order == "runs64":
+        perm = _interleaved(bucket, d2, 64)
+    else:
+        raise ValueError(f"order {order!r}")
+    real = encode_windows(plo[read[perm]], phi[read[perm]], length[perm], k, d1[perm], d2[perm]).reshape(-1, 2)
+    for i in rng.integers(0, max(n_real, 1), min(n_real, 4)):
+        j = perm[i]
+        want = encode(codes[read[j]][:length[j] + k - 1], k, d1=int(d1[j]), d2=int(d2[j]), multi=True)
+        if (int(real[i, 0]), int(real[i, 1])) != want:
+            raise AssertionError(f"record {int(i)} differs from encode()")
+    real_bucket = bucket[perm]
+    # ---- NULL records
+    nulls = {int(b): np.unique(np.asarray(p, dtype=np.int64)) for b, p in spec.get("nulls", {}).items() if len(p)}
+    if not nulls:
+        records, bucket_of_record = real, real_bucket
+    else:
+        parts, bparts = [], []
+        for b in sorted(set(real_bucket.tolist()) | set(nulls)):
+            mine = real[real_bucket == b]
+            pos = nulls.get(b, np.zeros(0, dtype=np.int64))
+            total = len(mine) + len(pos)
+            if len(pos) and (pos[0] < 0 or pos[-1] >= total):
+                raise ValueError(f"NULL positions outside bucket {b}'s {total} records")
+            nlo, nhi = _pack_payload(rng.integers(0, 4, (len(pos), nb_full), dtype=np.uint8))
+            out = np.empty((total, 2), dtype=np.uint64)
+            is_null = np.zeros(total, dtype=bool)
+            is_null[pos] = True
+            out[is_null] = encode_windows(nlo, nhi, rng.integers(1, lm + 1, len(pos)), k, rng.integers(0, D1_MASK + 1, len(pos)),
+                                          rng.integers(0, D2_MASK + 1, len(pos)), null=True).reshape(-1, 2)
+            out[~is_null] = mine
+            parts.append(out)
+            bparts.append(np.full(total, b, dtype=np.int64))
+        records, bucket_of_record = np.concatenate(parts), np.concatenate(bparts)
+    live = (records[:, 1] >> U64(REC_NULL_BIT)) == 0
+    truth = decode(records[live], k).kmers
+    return np.ascontiguousarray(records).reshape(-1), bucket_of_record, truth
+
+
+crafted_stream.redrawn = 0

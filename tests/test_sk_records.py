@@ -386,9 +386,10 @@ def test_level0_shards(ctx, pkg, k):
 
 # ------------------------------------------------------------------ dnagpu_count_records on crafted streams
 
-def count_stream(ctx, recs, pieces_of, k, rows, truth_kmers, what, profile=False):
+def count_stream(ctx, recs, pieces_of, k, rows, truth_kmers, what, profile=False, unique=None):
     """uploads the records (2n words), counts pieces_of(device pointer) -> [(pointer, n, bucket)], compares the histogram
-    with np.unique of truth_kmers.  -> the phase names if profile"""
+    with np.unique of truth_kmers (unique: that result, np.unique(truth_kmers, return_counts=True), where the caller counts
+    one stream several times and has it already).  -> the phase names if profile"""
     buf = ctx.buffer_alloc(max(recs.nbytes, 16))
     try:
         ctx.upload_u64(buf, recs)
@@ -401,7 +402,7 @@ def count_stream(ctx, recs, pieces_of, k, rows, truth_kmers, what, profile=False
             if profile:
                 ctx.set_profiling(False)
         try:
-            ok, oc = np.unique(np.asarray(truth_kmers, dtype=np.uint64), return_counts=True)
+            ok, oc = unique if unique is not None else np.unique(np.asarray(truth_kmers, dtype=np.uint64), return_counts=True)
             assert h.total == len(truth_kmers), f"{what}: total {h.total}, {len(truth_kmers)} k-mers"
             check_hist_unordered(h, ok, oc.astype(np.uint64), what)
         finally:
