@@ -34,6 +34,7 @@ DEBUG_RANK_SMALL = 1024               # rank: a class limit of 4 counts and sort
 DEBUG_JOIN_PARTITION = 2048           # dnagpu_acc_join: the partition path for any sizes
 DEBUG_JOIN_DIRECT = 4096              # dnagpu_acc_join: the direct path for any sizes
 DEBUG_WEAK_FINGERPRINT = 8192         # equal sequences: 2-bit fingerprints (several verify rounds, run walks in the match)
+DEBUG_EARLY_L2 = 16384                # record count: level 2 behind its device-side gate after a level 1 with sampled regions too
 MATCH_NONE = (1 << 64) - 1            # dnagpu_table_match: no sequence of the built table equals this one
 JOIN_INNER = 0                        # JOIN .. ON a.kmer = b.kmer; INTERSECT
 JOIN_ANTI = 1                         # EXCEPT; NOT IN; NOT EXISTS

@@ -653,8 +653,8 @@ __global__ __launch_bounds__(SCAN_BLOCK) void scan_apply_kernel(const u32 *in, u
     }
 }
 
-// up to four scans of the same length in the three launches of one (blockIdx.y = which array): the selections of the
-// record engine scan four flag / size arrays over the final buckets back to back
+// up to six scans of the same length in the three launches of one (blockIdx.y = which array): the selection of the
+// record engine scans six flag / size arrays over the final buckets at a time
 __global__ __launch_bounds__(SCAN_BLOCK) void scan_reduce_multi_kernel(ScanSet set, u64 n, u64 tmp_stride)
 {
     __shared__ u32 sh4[4];
@@ -747,7 +747,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void scan_apply_multi_kernel(ScanSet se
 
 hipError_t launch_scan_u32_multi(const ScanSet &set, int n_arrays, u64 n, hipStream_t s)
 {
-    if (n_arrays < 1 || n_arrays > 4)
+    if (n_arrays < 1 || n_arrays > SCAN_SET_MAX)
         return hipErrorInvalidValue;
     if (n == 0) {
         for (int a = 0; a < n_arrays; a++)

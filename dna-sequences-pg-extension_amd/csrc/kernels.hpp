@@ -62,12 +62,13 @@ hipError_t launch_kmer_strand(const u64 *keys, u64 n, int k, int canonical, u64 
 // exclusive scan of n u32 values (in != out allowed, in == out allowed); *total receives the sum.
 // tmp must hold scan_tmp_words(n) u32 values.
 u64 scan_tmp_words(u64 n);
-// up to four exclusive scans of the same length n in three launches: in[a] -> out[a] (in == out allowed), *total[a] = the
+// up to six exclusive scans of the same length n in three launches: in[a] -> out[a] (in == out allowed), *total[a] = the
 // sum (may be null); tmp holds n_arrays x scan_tmp_words(n) words
+constexpr int SCAN_SET_MAX = 6;
 struct ScanSet {
-    const u32 *in[4];
-    u32 *out[4];
-    u32 *total[4];
+    const u32 *in[SCAN_SET_MAX];
+    u32 *out[SCAN_SET_MAX];
+    u32 *total[SCAN_SET_MAX];
     u32 *tmp;
 };
 hipError_t launch_scan_u32_multi(const ScanSet &set, int n_arrays, u64 n, hipStream_t s);
@@ -563,12 +564,49 @@ hipError_t launch_sk_sampled_regions(const Node *nodes, const Chunk *samples, u3
 // every mid bucket's records regrouped by d2 from src into the same range of dst; out_nodes[16 i + j] = final bucket:
 // start / len in records, child_base = its k-mers
 int sk_regroup_tile();   // records one workgroup regroups in one go; longer mid buckets need any_long (a second kernel)
-hipError_t launch_sk_regroup(const Node *mids, u32 n_mids, const void *src, void *dst, Node *out_nodes, bool any_long, hipStream_t s);
+// gate != null: a workgroup of the one-tile kernel returns at once unless *gate == 0 (the launch went out before the host
+// had seen level 1's verdict: launch_sk_l1_gate)
+hipError_t launch_sk_regroup(const Node *mids, u32 n_mids, const void *src, void *dst, Node *out_nodes, bool any_long, hipStream_t s,
+                             const u32 *gate = nullptr);
+// The gate of an early level 2: *gate = 0 exactly when the one-tile regroup is all that level 2 has to do, else the reasons
+// why not.  Host and device judge a mid bucket with the one function; the host recomputes the word from what it read back.
+enum : u32 {
+    SK_GATE_SPEC = 1,       // the speculative sweep's status words: a wrong span, regions past 2^32, a region overflowed
+    SK_GATE_SLAB = 2,       // level 0's slab status words: a chunk ran out of slots, or a wrong span
+    SK_GATE_LONG = 4,       // a mid bucket of more than one regroup tile
+    SK_GATE_HEAVY = 8,      // a heavy mid bucket (k-mers over mid_limit, records over rec_limit)
+    SK_GATE_KMERS = 16,     // the k-mers found are not the expected ones, or pass 2^32
+};
+struct SkGateIn {
+    const u32 *lens, *kcount;   // records and k-mers per mid bucket (n_mid each)
+    u32 n_mid;
+    const u32 *status1;         // the sweep's three status words
+    u32 span1, sampled;         // the slots its regions must span (not checked for sampled regions)
+    const u32 *status0;         // level 0's two slab status words, or null
+    u32 span0;
+    u64 mid_limit, n_expected;  // (n_expected 0: not known)
+    u32 rec_limit, tile;
+};
+__host__ __device__ inline u32 sk_gate_bucket(u32 len, u32 kmers, u64 mid_limit, u32 rec_limit, u32 tile)
+{
+    return (len > tile ? (u32)SK_GATE_LONG : 0u) | ((kmers > mid_limit || len > rec_limit) ? (u32)SK_GATE_HEAVY : 0u);
+}
+__host__ __device__ inline u32 sk_gate_status(const u32 *st1, u32 span1, u32 sampled, const u32 *st0, u32 span0)
+{
+    u32 g = 0;
+    if ((!sampled && (st1[0] != span1 || st1[1])) || st1[2])
+        g |= SK_GATE_SPEC;
+    if (st0 && (st0[0] || st0[1] != span0))
+        g |= SK_GATE_SLAB;
+    return g;
+}
+hipError_t launch_sk_l1_gate(const SkGateIn &in, u32 *gate, hipStream_t s);
 
 // ---------------------------------------------------------------- sk_tail_kernels.hip
 int sk_count_cap();       // most k-mers a final bucket may hold to be counted from its records
+// (f_over3 / k_over3: flag and k-mers of the buckets of class "over", which are all of the expansion's when none is big)
 hipError_t launch_sk_select_flags(const Node *fin, u32 n_fin, u32 cap, u32 big_limit, u32 *f_small, u32 *f_big, u32 *k_range,
-                                  u32 *k_big, hipStream_t s);
+                                  u32 *k_big, u32 *f_over3, u32 *k_over3, hipStream_t s);
 hipError_t launch_sk_select_lists(const Node *fin, u32 n_fin, u32 cap, u32 big_limit, const u32 *p_small, const u32 *p_big,
                                   const u32 *kb_range, u32 *list_small, u32 *off_small, u32 *list_big, u32 *off_big, hipStream_t s);
 // buckets that go through the expansion: too many k-mers for sk_count_big, or given up by it (big_status[p] != 0)

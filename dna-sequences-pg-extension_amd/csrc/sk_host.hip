@@ -65,9 +65,6 @@ static ScanSet scan_set(std::initializer_list<u32 *> in, std::initializer_list<u
     return ss;
 }
 
-// the same in place
-static ScanSet scans_in_place(std::initializer_list<u32 *> arr, u32 *totals, u32 *tmp) { return scan_set(arr, arr, totals, tmp); }
-
 struct SkLevel {                                 // what one forced partition level leaves behind
     Node *next;
     u32 n_next;
@@ -280,6 +277,35 @@ constexpr u64 SK_PIPE_MIN_ROWS = (u64)5 << 29;
 // they would be 25 %).  Pipelined: SK_L0_PIECES half sets (17 %).
 constexpr u64 SK_SLAB_CHUNKS = 1024, SK_SLAB_CHUNKS_PIPED = 512 * SK_L0_PIECES;
 
+// The side stream of a call, from its first launch there until the main stream has been made to wait for it, or the host
+// has waited for it (joined): a return before that -- an error -- waits for it on the host, since the scope's pool memory
+// goes back on return.
+struct SideWork {
+    hipStream_t s, main;
+    bool joined = false;
+    SideWork(hipStream_t side, hipStream_t main_stream) : s(side), main(main_stream) {}
+    ~SideWork()
+    {
+        if (!joined) {
+            (void)hipStreamSynchronize(s);
+            (void)hipStreamSynchronize(main);
+        }
+    }
+};
+// The events of ctx->sync_ev (side_stream): one per piece of a pipelined level 0, one for the join behind them, and one
+// that orders the side stream behind the main one where the host reads something back beside the main stream's work.
+constexpr size_t SK_EV_JOIN = SK_L0_PIECES, SK_EV_POST = SK_L0_PIECES + 1, SK_EVENTS = SK_L0_PIECES + 2;
+
+// The side stream behind everything queued on the main stream so far: a read-back posted there now travels while the
+// main stream goes on, and the host waits for the side stream alone (never for the main one, which is busy by then).
+static int side_behind_main(dnagpu_ctx *ctx)
+{
+    RC_TRY(side_stream(ctx, SK_EVENTS));
+    HIP_TRY(hipEventRecord(ctx->sync_ev[SK_EV_POST], ctx->stream));
+    HIP_TRY(hipStreamWaitEvent(ctx->stream2, ctx->sync_ev[SK_EV_POST], 0));
+    return DNAGPU_OK;
+}
+
 struct SkSlab {                     // a slab sweep that is ready to run (sk_slab_begin)
     SkLevel l0;                     // l0.chunks: the chunks of rows
     u32 *slab = nullptr;            // the slab table (see sk_scatter0_kernel)
@@ -417,6 +443,10 @@ struct SkL1 {
     u32 *sp = nullptr;              // Speculative: first region and slots per region of every coarse node (sk_l1_spec_begin)
     void *rec1 = nullptr;           // level 1's output buffer: the speculative sweep allocates it, else the exact scatter
     bool rec1_kept = false;         // p.heavy lives in rec1 (sk_heavy_take with DNAGPU_DEBUG_HEAVY_EXPAND): level 2 does not free it
+    // level 2 launched behind the device-side gate, before the host had level 1's verdict (sk_l2_early)
+    u32 *gate = nullptr;            // the gate word
+    Node *fn_early = nullptr;       // the final buckets' nodes of that launch
+    bool early_open = false;        // the gate was 0: the regroup ran, sk_level2 only takes fn_early over
 };
 
 // Which way level 1 goes.  With the coarse buckets' record counts on the host (p.lens) and room in rec0 (p.rec0_cap),
@@ -447,21 +477,37 @@ static int sk_l1_plan(dnagpu_ctx *ctx, PoolScope &ps, const SkParts &p, SkL1 &l1
 
 // mid-bucket k-mer and record counts to the host (the list is short), with `extra` words behind the record counts; in
 // the same wait, two more device words (more -> more_host) where the caller has some: level 0's status
-static int sk_l1_lens_to_host(dnagpu_ctx *ctx, SkL1 &l1, u32 extra, const u32 *more = nullptr, u32 *more_host = nullptr)
+// sk_l1_lens_fit: the lists go through the pinned mailbox.  Then they may travel on another stream than the main one
+// (`on`: the caller has ordered it behind what writes them) and only that stream is waited for; `gate` (one more word ->
+// *gate_host) travels with them.
+static bool sk_l1_lens_fit(const SkL1 &l1, u32 extra)
 {
-    hipStream_t st = ctx->stream;
+    return 2 * (size_t)l1.lv.n_next * sizeof(u32) + ((size_t)extra + 3) * sizeof(u32) <= MAILBOX_BYTES - 8;
+}
+
+static int sk_l1_lens_to_host(dnagpu_ctx *ctx, SkL1 &l1, u32 extra, const u32 *more = nullptr, u32 *more_host = nullptr,
+                              hipStream_t on = nullptr, const u32 *gate = nullptr, u32 *gate_host = nullptr)
+{
+    hipStream_t st = on ? on : ctx->stream;
     const size_t nb = (size_t)l1.lv.n_next * sizeof(u32), nb2 = nb + (size_t)extra * sizeof(u32), nb3 = more ? 2 * sizeof(u32) : 0;
-    if (nb + nb2 + nb3 <= MAILBOX_BYTES - 8) {    // the lists through the pinned mailbox, one wait (its last word is read_back's flag)
+    if (sk_l1_lens_fit(l1, extra)) {    // the lists through the pinned mailbox, one wait (its last word is read_back's flag)
         char *mb = reinterpret_cast<char *>(ctx->mailbox);
         HIP_TRY(hipMemcpyAsync(mb, l1.kcount, nb, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(mb + nb, l1.d_lens, nb2, hipMemcpyDeviceToHost, st));
         if (more)
             HIP_TRY(hipMemcpyAsync(mb + nb + nb2, more, nb3, hipMemcpyDeviceToHost, st));
+        if (gate)
+            HIP_TRY(hipMemcpyAsync(mb + nb + nb2 + nb3, gate, sizeof(u32), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         memcpy(l1.kc.data(), mb, nb);
         memcpy(l1.rcn.data(), mb + nb, nb2);
         if (more)
             memcpy(more_host, mb + nb + nb2, nb3);
+        if (gate)
+            memcpy(gate_host, mb + nb + nb2 + nb3, sizeof(u32));
+    } else if (on || gate) {
+        set_err("sk_l1_lens_to_host: lists too long for the mailbox on a side stream");
+        return DNAGPU_ERR_INTERNAL;
     } else {
         HIP_TRY(hipMemcpyAsync(l1.kc.data(), l1.kcount, nb, hipMemcpyDeviceToHost, st));
         RC_TRY(read_back(ctx, l1.rcn.data(), l1.d_lens, nb2));
@@ -568,8 +614,66 @@ static int sk_l1_spec_begin(dnagpu_ctx *ctx, PoolScope &ps, const SkParts &p, Sk
     return DNAGPU_OK;
 }
 
-static int sk_l1_spec_end(dnagpu_ctx *ctx, const SkParts &p, SkL1 &l1, SkL1Route route, bool *moved, const u32 *l0_status = nullptr,
-                          u32 *l0_status_host = nullptr)
+// The records of a mid bucket from which the census calls it heavy (the forced engine of the tests: never by its records)
+static u32 sk_mid_rec_limit(unsigned debug_flags) { return (debug_flags & DNAGPU_DEBUG_FORCE_SUPERKMER) ? 0xFFFFFFFFu : SK_MID_RECORDS; }
+
+// LEVEL 2 BEHIND A GATE.  Between the speculative sweep and level 2 the host reads the mid buckets' counts and decides --
+// 0.2 ms at 3 Gbase in which the device ran 9 us of kernels.  On random sequence the decision is always the same: the
+// sweep stands, no mid bucket is heavy or longer than a tile, and sk_regroup<false> over all of them is level 2.  So a
+// one-workgroup kernel takes that decision on the device (one word: launch_sk_l1_gate), the regroup is queued right
+// behind it and does nothing unless the word is 0, and the lists travel to the host on the side stream meanwhile.  The
+// host recomputes the word from what it read (sk_gate_host) -- a difference is an error, never a second or a missing
+// regroup -- and goes on as before; with the word 0 sk_level2 finds its work done (l1.early_open).
+// The gate must be on the device: the regroup writes into rec0, which the exact level 1 that follows an overflow reads.
+// Not launched early: under the debug flags that force a fall-back or the older heavy path (those paths stay as they
+// were), with lists too long for the mailbox (the wait would be the main stream's), and after a level 1 with SAMPLED
+// regions: uneven coarse buckets are repeats, their heavy and long mid buckets shut the gate, and a shut gate is not free
+// -- the gate kernel, 75 K workgroups that return at once, the host's second pass over the lists: 3 Gbase with a tiled
+// 1000-base motif, sk_scatter1's phase 2.87 - 2.95 ms before and 3.02 - 3.06 with the early launch, one box.
+// (DNAGPU_DEBUG_EARLY_L2 launches early there too: the tests of the gate's verdict on such buckets.)
+static bool sk_l2_early_allowed(const dnagpu_ctx *ctx, const SkL1 &l1, bool sampled)
+{
+    return !(ctx->debug_flags & (DNAGPU_DEBUG_SPEC1_OVERFLOW | DNAGPU_DEBUG_SLAB0_OVERFLOW | DNAGPU_DEBUG_HEAVY_EXPAND)) &&
+           (!sampled || (ctx->debug_flags & DNAGPU_DEBUG_EARLY_L2)) && l1.lv.n_next > 0 && sk_l1_lens_fit(l1, 3);
+}
+
+static SkGateIn sk_gate_in(const dnagpu_ctx *ctx, const SkParts &p, const SkL1 &l1, bool sampled, const u32 *lens, const u32 *kcount,
+                           const u32 *status1, const u32 *status0, u32 span0)
+{
+    SkGateIn gi;
+    memset(&gi, 0, sizeof gi);
+    gi.lens = lens;
+    gi.kcount = kcount;
+    gi.n_mid = l1.lv.n_next;
+    gi.status1 = status1;
+    gi.span1 = (u32)l1.span;
+    gi.sampled = sampled ? 1u : 0u;
+    gi.status0 = status0;
+    gi.span0 = span0;
+    gi.mid_limit = p.g.mid_limit;
+    gi.n_expected = p.n_expected;
+    gi.rec_limit = sk_mid_rec_limit(ctx->debug_flags);
+    gi.tile = (u32)sk_regroup_tile();
+    return gi;
+}
+
+// the gate word from the host's copies of what the gate kernel read (gi's pointers are host memory)
+static u32 sk_gate_host(const SkGateIn &gi)
+{
+    u32 g = sk_gate_status(gi.status1, gi.span1, gi.sampled, gi.status0, gi.span0);
+    u64 run = 0;
+    for (u32 i = 0; i < gi.n_mid; i++) {
+        run += gi.kcount[i];
+        g |= sk_gate_bucket(gi.lens[i], gi.kcount[i], gi.mid_limit, gi.rec_limit, gi.tile);
+    }
+    if ((gi.n_expected != 0 && run != gi.n_expected) || run > 0xFFFFFFFFull)
+        g |= SK_GATE_KMERS;
+    return g;
+}
+
+// (span0: the slots level 0's slab status must report, with l0_status)
+static int sk_l1_spec_end(dnagpu_ctx *ctx, PoolScope &ps, const SkParts &p, SkL1 &l1, SkL1Route route, bool *moved,
+                          const u32 *l0_status = nullptr, u32 *l0_status_host = nullptr, u32 span0 = 0)
 {
     hipStream_t st = ctx->stream;
     const bool sampled = route == SkL1Route::SpeculativeSampled;
@@ -578,7 +682,36 @@ static int sk_l1_spec_end(dnagpu_ctx *ctx, const SkParts &p, SkL1 &l1, SkL1Route
     u32 *status = l1.d_lens + n_mid;
     HIP_TRY(launch_sk_spec_nodes(p.coarse, p.n_coarse, l1.sp, l1.gcur, l1.lv.next, status + 2, st, rstart, rcapv));
     HIP_TRY(launch_sk_node_lens(l1.lv.next, n_mid, l1.d_lens, st));
-    RC_TRY(sk_l1_lens_to_host(ctx, l1, 3, l0_status, l0_status_host));
+    const bool early = sk_l2_early_allowed(ctx, l1, sampled);
+    if (early) {
+        RC_TRY(ps.alloc(1, &l1.gate));
+        RC_TRY(ps.alloc((size_t)n_mid * 16, &l1.fn_early));
+        HIP_TRY(launch_sk_l1_gate(sk_gate_in(ctx, p, l1, sampled, l1.d_lens, l1.kcount, status, l0_status, span0), l1.gate, st));
+        RC_TRY(side_behind_main(ctx));
+        SideWork side(ctx->stream2, st);
+        const size_t mark_at = ctx->ev_names.size();
+        prof_mark(ctx, "sk_regroup");
+        HIP_TRY(launch_sk_regroup(l1.lv.next, n_mid, l1.rec1, p.rec0, l1.fn_early, false, st, l1.gate));
+        u32 gate_dev = 0;
+        RC_TRY(sk_l1_lens_to_host(ctx, l1, 3, l0_status, l0_status_host, side.s, l1.gate, &gate_dev));
+        side.joined = true;                      // (the host has waited for the side stream)
+        const u32 *stw = l1.rcn.data() + n_mid;
+        const u32 gate_host =
+            sk_gate_host(sk_gate_in(ctx, p, l1, sampled, l1.rcn.data(), l1.kc.data(), stw, l0_status ? l0_status_host : nullptr, span0));
+        if (gate_host != gate_dev) {
+            set_err("super-k-mer level 2: the device's gate word is %u, the host's verdict %u", gate_dev, gate_host);
+            return DNAGPU_ERR_INTERNAL;
+        }
+        l1.early_open = gate_dev == 0;
+        if (!l1.early_open) {                    // the launch did nothing: its phase belongs to the one before it
+            if (ctx->ev_names.size() > mark_at && mark_at > 0)
+                ctx->ev_names[mark_at] = ctx->ev_names[mark_at - 1];
+            ps.free_now(l1.fn_early);
+            l1.fn_early = nullptr;
+        }
+    } else {
+        RC_TRY(sk_l1_lens_to_host(ctx, l1, 3, l0_status, l0_status_host));
+    }
     const u32 *stw = l1.rcn.data() + n_mid;
     *moved = !((!sampled && stw[0] != (u32)l1.span) || (!sampled && stw[1]) || stw[2] ||
                (ctx->debug_flags & DNAGPU_DEBUG_SPEC1_OVERFLOW));
@@ -595,7 +728,7 @@ static int sk_l1_speculative(dnagpu_ctx *ctx, PoolScope &ps, const SkParts &p, S
     HIP_TRY(launch_sk_scatter1_spec(p.coarse, l1.lv.chunks, l1.lv.n_chunks, p.rec0, l1.rec1, l1.gcur, l1.sp, l1.kcount,
                                     l1.d_lens + l1.lv.n_next + 2, ctx->stream, sampled ? l1.rstart : nullptr,
                                     sampled ? l1.rcapv : nullptr));
-    return sk_l1_spec_end(ctx, p, l1, route, moved);
+    return sk_l1_spec_end(ctx, ps, p, l1, route, moved);
 }
 
 // The exact histogram: the mid buckets' nodes from its prefix, and their k-mer and record counts on the host before any
@@ -717,19 +850,27 @@ static int sk_heavy_take(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p, SkL1 &l1, c
 
 // Level 2: every mid bucket regrouped by d2 (rec1 -> rec0): 16 final buckets each, the children of the split heavy
 // buckets behind them.  Fills p.recs / p.fin / p.n_fin; rec1 goes back to the pool unless p.heavy lives in it.
+// The phase "sk_regroup" is marked once per regroup that did work: here, or where it was launched early.
 static int sk_level2(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p, SkL1 &l1, const SkSplit &split)
 {
     hipStream_t st = ctx->stream;
     const u32 n_mid = l1.lv.n_next, n_split = split.lv.n_next;
-    Node *fn = nullptr;
-    RC_TRY(ps.alloc((size_t)n_mid * 16 + n_split, &fn));
-    prof_mark(ctx, "sk_regroup");
-    bool any_long = false;                       // (mid buckets of more than one regroup tile: repeats)
-    for (u32 i = 0; i < n_mid && !any_long; i++)
-        any_long = l1.rcn[i] > (u32)sk_regroup_tile();
-    HIP_TRY(launch_sk_regroup(l1.lv.next, n_mid, l1.rec1, p.rec0, fn, any_long, st));
-    if (n_split)
-        HIP_TRY(launch_sk_heavy_finals(split.lv.next, n_split, split.kcount, fn + (size_t)n_mid * 16, st));
+    Node *fn = l1.fn_early;
+    if (l1.early_open) {                         // (sk_l1_spec_end: the regroup ran behind its gate, and it was all of level 2)
+        if (n_split) {
+            set_err("super-k-mer level 2: heavy mid buckets behind an open gate");
+            return DNAGPU_ERR_INTERNAL;
+        }
+    } else {
+        RC_TRY(ps.alloc((size_t)n_mid * 16 + n_split, &fn));
+        prof_mark(ctx, "sk_regroup");
+        bool any_long = false;                   // (mid buckets of more than one regroup tile: repeats)
+        for (u32 i = 0; i < n_mid && !any_long; i++)
+            any_long = l1.rcn[i] > (u32)sk_regroup_tile();
+        HIP_TRY(launch_sk_regroup(l1.lv.next, n_mid, l1.rec1, p.rec0, fn, any_long, st));
+        if (n_split)
+            HIP_TRY(launch_sk_heavy_finals(split.lv.next, n_split, split.kcount, fn + (size_t)n_mid * 16, st));
+    }
     if (!l1.rec1_kept)
         ps.free_now(l1.rec1);
     p.recs = p.rec0;
@@ -776,27 +917,13 @@ static int sk_levels12(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p)
 
 // ---------------------------------------------------------------- levels 0 and 1 side by side
 
-// The side stream of a call, from its first launch there until the main stream has been made to wait for it (joined): a
-// return before that -- an error -- waits for it on the host, since the scope's pool memory goes back on return.
-struct SideWork {
-    hipStream_t s, main;
-    bool joined = false;
-    SideWork(hipStream_t side, hipStream_t main_stream) : s(side), main(main_stream) {}
-    ~SideWork()
-    {
-        if (!joined) {
-            (void)hipStreamSynchronize(s);
-            (void)hipStreamSynchronize(main);
-        }
-    }
-};
-
 // Level 0 (slab sweep) and the plain speculative level 1, piece by piece: sk_scatter0 uses under a third of the memory
 // bandwidth and sk_scatter1 little of the vector units, so piece i of level 1 runs on the side stream while piece i + 1
 // of level 0 is cut on the main stream.  Level 1 is planned over the whole regions BEFORE the sweep (its regions, cursors
 // and k-mer counts are those of the unpipelined level); piece i's launch gets nodes of its own -- node d = the slots
 // that the chunks of level-0 piece i reserve in region d (see SK_L0_PIECES), with the planned node's split, child_base and
-// chunk_base, i.e. the same regions, cursors and counters -- and chunks over them, built on the host.  The main stream
+// chunk_base, i.e. the same regions, cursors and counters -- and chunks over them, built on the host WHILE the first
+// piece of level 0 runs (the planned nodes come back on the side stream, the lists go up on it).  The main stream
 // waits for the side stream behind the last piece; level 0's status comes back with level 1's lens (one wait).
 // *slab_ok: the sweep is usable (else everything level 1 did here is dropped with it: sk_slab_give_up, and rec1 is free
 // again); *moved: as sk_l1_speculative.
@@ -805,11 +932,43 @@ static int sk_l01_piped(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p, const SkRows
 {
     hipStream_t st = ctx->stream;
     const u32 n_coarse = p.n_coarse, chunk_recs = l1.chunk_recs;
-    RC_TRY(side_stream(ctx, SK_L0_PIECES + 1));
+    RC_TRY(side_stream(ctx, SK_EVENTS));
     RC_TRY(sk_l1_spec_begin(ctx, ps, p, l1, SkL1Route::Speculative));
     std::vector<Node> planned(n_coarse), pn;
-    RC_TRY(read_back(ctx, planned.data(), p.coarse, (size_t)n_coarse * sizeof(Node)));
     std::vector<Chunk> pc;
+    // The first piece of level 0 needs nothing of level 1's launch lists: it is cut while the planned nodes travel to the
+    // host on the side stream, the host builds the lists, and they travel back there (the level-1 launches follow them
+    // on that stream).
+    const size_t planned_bytes = (size_t)n_coarse * sizeof(Node);
+    if (planned_bytes > MAILBOX_BYTES - 8) {
+        set_err("sk_l01_piped: %u coarse nodes do not fit the mailbox", n_coarse);
+        return DNAGPU_ERR_INTERNAL;
+    }
+    // (their device copies are allocated before anything runs beside the main stream: what the pool does to a fresh block
+    // under its debug flags is queued on the main stream.  The chunks: as if every node were split.)
+    size_t pc_room = 0;
+    for (u32 i = 0; i < SK_L0_PIECES; i++) {
+        u32 a = 0, b = 0;
+        sk_piece_range(sl.l0.n_chunks, i, &a, &b);
+        for (u32 d = 0; d < n_coarse; d++)
+            pc_room += ((size_t)sl.cap[d] * (b - a) + chunk_recs - 1) / chunk_recs;
+    }
+    Node *d_pn = nullptr;
+    Chunk *d_pc = nullptr;
+    RC_TRY(alloc1(ps, (size_t)SK_L0_PIECES * n_coarse, &d_pn));
+    RC_TRY(alloc1(ps, pc_room, &d_pc));
+    RC_TRY(side_behind_main(ctx));
+    SideWork side(ctx->stream2, st);             // (pn / pc are host vectors: an early way out waits for their copies too)
+    prof_mark(ctx, "sk_scatter0");
+    {
+        u32 a = 0, b = 0;
+        sk_piece_range(sl.l0.n_chunks, 0, &a, &b);
+        RC_TRY(sk_slab_piece(ctx, p, rows, sl, a, b));
+        HIP_TRY(hipEventRecord(ctx->sync_ev[0], st));
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->mailbox, p.coarse, planned_bytes, hipMemcpyDeviceToHost, side.s));
+    HIP_TRY(hipStreamSynchronize(side.s));
+    memcpy(planned.data(), ctx->mailbox, planned_bytes);
     u32 first_chunk[SK_L0_PIECES + 1];
     for (u32 i = 0; i < SK_L0_PIECES; i++) {
         u32 a = 0, b = 0;
@@ -831,31 +990,31 @@ static int sk_l01_piped(dnagpu_ctx *ctx, PoolScope &ps, SkParts &p, const SkRows
         }
     }
     first_chunk[SK_L0_PIECES] = (u32)pc.size();
-    Node *d_pn = nullptr;
-    Chunk *d_pc = nullptr;
-    RC_TRY(alloc1(ps, pn.size(), &d_pn));
-    RC_TRY(alloc1(ps, pc.size(), &d_pc));
-    SideWork side(ctx->stream2, st);             // (pn / pc are host vectors: an early way out waits for their copies too)
-    HIP_TRY(hipMemcpyAsync(d_pn, pn.data(), pn.size() * sizeof(Node), hipMemcpyHostToDevice, st));
+    if (pc.size() > pc_room) {
+        set_err("sk_l01_piped: %zu chunks planned, room for %zu", pc.size(), pc_room);
+        return DNAGPU_ERR_INTERNAL;
+    }
+    HIP_TRY(hipMemcpyAsync(d_pn, pn.data(), pn.size() * sizeof(Node), hipMemcpyHostToDevice, side.s));
     if (!pc.empty())
-        HIP_TRY(hipMemcpyAsync(d_pc, pc.data(), pc.size() * sizeof(Chunk), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_pc, pc.data(), pc.size() * sizeof(Chunk), hipMemcpyHostToDevice, side.s));
     u32 *status1 = l1.d_lens + l1.lv.n_next;
-    prof_mark(ctx, "sk_scatter0");
     for (u32 i = 0; i < SK_L0_PIECES; i++) {
-        u32 a = 0, b = 0;
-        sk_piece_range(sl.l0.n_chunks, i, &a, &b);
-        RC_TRY(sk_slab_piece(ctx, p, rows, sl, a, b));
-        HIP_TRY(hipEventRecord(ctx->sync_ev[i], st));
+        if (i > 0) {                             // (piece 0 is on its way)
+            u32 a = 0, b = 0;
+            sk_piece_range(sl.l0.n_chunks, i, &a, &b);
+            RC_TRY(sk_slab_piece(ctx, p, rows, sl, a, b));
+            HIP_TRY(hipEventRecord(ctx->sync_ev[i], st));
+        }
         HIP_TRY(hipStreamWaitEvent(side.s, ctx->sync_ev[i], 0));
         HIP_TRY(launch_sk_scatter1_spec(d_pn + (size_t)i * n_coarse, d_pc + first_chunk[i], first_chunk[i + 1] - first_chunk[i], p.rec0,
                                         l1.rec1, l1.gcur, l1.sp, l1.kcount, status1 + 2, side.s, nullptr, nullptr));
     }
     prof_mark(ctx, "sk_scatter1");                // (from here: what of level 1 the sweep did not hide)
-    HIP_TRY(hipEventRecord(ctx->sync_ev[SK_L0_PIECES], side.s));
-    HIP_TRY(hipStreamWaitEvent(st, ctx->sync_ev[SK_L0_PIECES], 0));
+    HIP_TRY(hipEventRecord(ctx->sync_ev[SK_EV_JOIN], side.s));
+    HIP_TRY(hipStreamWaitEvent(st, ctx->sync_ev[SK_EV_JOIN], 0));
     side.joined = true;
     u32 status0[2] = {1, 0};
-    RC_TRY(sk_l1_spec_end(ctx, p, l1, SkL1Route::Speculative, moved, sl.slab + 18 * (size_t)sk_max_c0(), status0));
+    RC_TRY(sk_l1_spec_end(ctx, ps, p, l1, SkL1Route::Speculative, moved, sl.slab + 18 * (size_t)sk_max_c0(), status0, (u32)sl.span));
     *slab_ok = sk_slab_ok(ctx, sl, status0);
     if (!*slab_ok) {
         ps.free_now(l1.rec1);
@@ -908,7 +1067,9 @@ struct SkTail {
     // ---- sk_tail_select: flags (then their scans) per final bucket, and the lists of the small buckets (at most
     // sk_count_cap() k-mers: sk_count's) and the big ones
     u32 *f_small = nullptr, *f_big = nullptr, *k_range = nullptr, *f_over = nullptr;
-    u32 *scan_tmp = nullptr, *totals = nullptr;   // (four scans at a time; eight totals)
+    u32 *f_over3 = nullptr, *p_over3 = nullptr, *k_over3 = nullptr;   // the buckets of class "over": flags, their scan, their k-mers (scanned)
+    u32 n_over3 = 0, over_keys3 = 0;              // (with no big bucket they are the over buckets: sk_tail_select_over)
+    u32 *scan_tmp = nullptr, *totals = nullptr;   // (six scans at a time; eight totals)
     u32 *list_small = nullptr, *off_small = nullptr, *list_big = nullptr, *off_big = nullptr;
     u32 n_small = 0, n_big = 0, big_kmers = 0;
     u64 small_keys = 0;         // the output slots of the small and big buckets: one per k-mer, in bucket order
@@ -942,19 +1103,29 @@ static int sk_tail_select(dnagpu_ctx *ctx, PoolScope &ps, const SkParts &p, u64 
     RC_TRY(ps.alloc((size_t)n_fin, &t.f_small));
     RC_TRY(ps.alloc((size_t)n_fin, &t.f_big));
     RC_TRY(ps.alloc((size_t)n_fin, &t.k_range));
-    RC_TRY(ps.alloc((size_t)scan_tmp_words(n_fin) * 4, &t.scan_tmp));     // (four scans at a time: launch_scan_u32_multi)
+    RC_TRY(ps.alloc((size_t)scan_tmp_words(n_fin) * SCAN_SET_MAX, &t.scan_tmp));     // (six scans at a time: launch_scan_u32_multi)
     RC_TRY(ps.alloc(8, &t.totals));
     RC_TRY(ps.alloc((size_t)n_fin, &t.list_small));
     RC_TRY(ps.alloc((size_t)n_fin, &t.off_small));
     RC_TRY(ps.alloc((size_t)n_fin, &t.f_over));     // (first: the k-mers of the big buckets, summed)
-    HIP_TRY(launch_sk_select_flags(p.fin, n_fin, (u32)sk_count_cap(), (u32)SK_BIG_LIMIT, t.f_small, t.f_big, t.k_range, t.f_over, st));
-    HIP_TRY(launch_scan_u32_multi(scans_in_place({t.f_small, t.f_big, t.k_range, t.f_over}, t.totals, t.scan_tmp), 4, n_fin, st));
-    u32 ht[4] = {0, 0, 0, 0};
+    RC_TRY(ps.alloc((size_t)n_fin, &t.f_over3));
+    RC_TRY(ps.alloc((size_t)n_fin, &t.p_over3));
+    RC_TRY(ps.alloc((size_t)n_fin, &t.k_over3));
+    HIP_TRY(launch_sk_select_flags(p.fin, n_fin, (u32)sk_count_cap(), (u32)SK_BIG_LIMIT, t.f_small, t.f_big, t.k_range, t.f_over,
+                                   t.f_over3, t.k_over3, st));
+    // the over buckets of class 3 in the same sweep and the same wait: with no big bucket (uniform sequence, most inputs)
+    // that is the whole second selection.  (Their flags stay as they are, the scan goes to p_over3: sk_over_list reads both.)
+    HIP_TRY(launch_scan_u32_multi(scan_set({t.f_small, t.f_big, t.k_range, t.f_over, t.f_over3, t.k_over3},
+                                           {t.f_small, t.f_big, t.k_range, t.f_over, t.p_over3, t.k_over3}, t.totals, t.scan_tmp),
+                                  6, n_fin, st));
+    u32 ht[6] = {0, 0, 0, 0, 0, 0};
     RC_TRY(read_back(ctx, ht, t.totals, sizeof ht));
     t.n_small = ht[0];
     t.n_big = ht[1];
     t.small_keys = ht[2];
     t.big_kmers = ht[3];
+    t.n_over3 = ht[4];
+    t.over_keys3 = ht[5];
     // a big bucket that sk_count_big gives up on is counted again through the expansion: its groups land behind the
     // ranges while its own range stays padding, so the arrays hold up to n + the big buckets' k-mers
     t.out_cap = n + t.big_kmers;
@@ -1019,6 +1190,14 @@ static int sk_tail_select_over(dnagpu_ctx *ctx, PoolScope &ps, const SkParts &p,
     const u32 n_fin = p.n_fin;
     u32 *f_over_raw = nullptr, *k_over = nullptr, *over_kbase = nullptr;
     prof_mark(ctx, "sk_select_over");
+    if (t.n_big == 0) {                          // no big bucket: class 3 is all of it, and sk_tail_select has scanned it
+        t.n_over = t.n_over3;
+        t.over_keys = t.over_keys3;
+        RC_TRY(alloc1(ps, t.n_over, &t.over_nodes));
+        RC_TRY(alloc1(ps, t.n_over, &over_kbase));
+        HIP_TRY(launch_sk_over_list(p.fin, n_fin, t.f_over3, t.p_over3, t.k_over3, t.over_nodes, over_kbase, st));
+        return DNAGPU_OK;
+    }
     RC_TRY(ps.alloc((size_t)n_fin, &f_over_raw));
     RC_TRY(ps.alloc((size_t)n_fin, &k_over));
     HIP_TRY(launch_sk_over_flags(p.fin, n_fin, (u32)sk_count_cap(), (u32)SK_BIG_LIMIT, t.f_big, t.big_status, f_over_raw, k_over, st));

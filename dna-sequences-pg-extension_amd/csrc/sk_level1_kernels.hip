@@ -462,7 +462,7 @@ constexpr int SKR_TILE = SKR_NT * SKR_ITEMS;
 template <bool LONG>
 __global__ __launch_bounds__(SKR_NT, 8) void sk_regroup_kernel(const Node *__restrict__ mids, u32 n_mids,
                                                             const ull2_t *__restrict__ src_all, ull2_t *__restrict__ dst_all,
-                                                            Node *__restrict__ out_nodes)
+                                                            Node *__restrict__ out_nodes, const u32 *__restrict__ gate)
 {
     __shared__ u32 rc[64][17], kc[64][17], qc[64][17];   // per-lane copies of the 16 record / k-mer / quad counters
     __shared__ u32 gpos[16], tcnt[17];
@@ -471,6 +471,10 @@ __global__ __launch_bounds__(SKR_NT, 8) void sk_regroup_kernel(const Node *__res
     unsigned short *idx = reinterpret_cast<unsigned short *>(stage);
     const u32 i = blockIdx.x;
     if (i >= n_mids)
+        return;
+    // launched before the host knew whether level 1 stands (launch_sk_l1_gate): if it does not, rec0 -- dst here -- is
+    // still the input of the exact level 1, and nothing may be written
+    if (!LONG && gate && *gate)
         return;
     const int tid = threadIdx.x, lane = tid & 63;
     const Node nd = mids[i];
@@ -654,8 +658,62 @@ __global__ __launch_bounds__(SKR_NT, 8) void sk_regroup_kernel(const Node *__res
     }
 }
 
+// The gate word of an early level 2 (kernels.hpp: SkGateIn): one workgroup over the mid buckets' record and k-mer counts
+// and the status words of the sweeps before it.
+__global__ __launch_bounds__(1024) void sk_l1_gate_kernel(SkGateIn in, u32 *__restrict__ gate)
+{
+    __shared__ u32 wbits[16];
+    __shared__ u64 wsum[16];
+    u32 g = 0;
+    u64 run = 0;
+    // four buckets per load where both lists are 16-byte aligned (pool memory is), several loads in flight: one workgroup
+    // reads 75 K buckets at 3 Gbase, and the regroup waits behind it
+    const bool vec = ((reinterpret_cast<uintptr_t>(in.lens) | reinterpret_cast<uintptr_t>(in.kcount)) & 15) == 0;
+    const u32 n4 = vec ? in.n_mid / 4 : 0;
+    const uint4 *lens4 = reinterpret_cast<const uint4 *>(in.lens), *kc4 = reinterpret_cast<const uint4 *>(in.kcount);
+#pragma unroll 4
+    for (u32 q = threadIdx.x; q < n4; q += 1024) {
+        const uint4 l = lens4[q], c = kc4[q];
+        run += (u64)c.x + c.y + c.z + c.w;
+        g |= sk_gate_bucket(l.x, c.x, in.mid_limit, in.rec_limit, in.tile) | sk_gate_bucket(l.y, c.y, in.mid_limit, in.rec_limit, in.tile) |
+             sk_gate_bucket(l.z, c.z, in.mid_limit, in.rec_limit, in.tile) | sk_gate_bucket(l.w, c.w, in.mid_limit, in.rec_limit, in.tile);
+    }
+    for (u32 i = 4 * n4 + threadIdx.x; i < in.n_mid; i += 1024) {
+        const u32 kmers = in.kcount[i];
+        run += kmers;
+        g |= sk_gate_bucket(in.lens[i], kmers, in.mid_limit, in.rec_limit, in.tile);
+    }
+    for (int o = 32; o; o >>= 1) {
+        g |= __shfl_xor(g, o);
+        run += __shfl_xor(run, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        wbits[threadIdx.x >> 6] = g;
+        wsum[threadIdx.x >> 6] = run;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        g = 0;
+        run = 0;
+        for (int w = 0; w < 16; w++) {
+            g |= wbits[w];
+            run += wsum[w];
+        }
+        g |= sk_gate_status(in.status1, in.span1, in.sampled, in.status0, in.span0);
+        if ((in.n_expected != 0 && run != in.n_expected) || run > 0xFFFFFFFFull)
+            g |= SK_GATE_KMERS;
+        *gate = g;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // launchers
+hipError_t launch_sk_l1_gate(const SkGateIn &in, u32 *gate, hipStream_t s)
+{
+    hipLaunchKernelGGL(sk_l1_gate_kernel, dim3(1), dim3(1024), 0, s, in, gate);
+    return hipGetLastError();
+}
+
 hipError_t launch_sk_hist1(const Node *nodes, const Chunk *chunks, u32 n_chunks, const void *recs, u32 *hist, u32 *kcount,
                            hipStream_t s, bool by_d2)
 {
@@ -731,15 +789,16 @@ hipError_t launch_sk_spec_nodes(const Node *nodes, u32 n_nodes, const u32 *spec,
 
 int sk_regroup_tile() { return SKR_TILE; }
 
-hipError_t launch_sk_regroup(const Node *mids, u32 n_mids, const void *src, void *dst, Node *out_nodes, bool any_long, hipStream_t s)
+hipError_t launch_sk_regroup(const Node *mids, u32 n_mids, const void *src, void *dst, Node *out_nodes, bool any_long, hipStream_t s,
+                             const u32 *gate)
 {
     if (n_mids == 0)
         return hipSuccess;
     hipLaunchKernelGGL(sk_regroup_kernel<false>, dim3(n_mids), dim3(SKR_NT), 0, s, mids, n_mids, reinterpret_cast<const ull2_t *>(src),
-                       reinterpret_cast<ull2_t *>(dst), out_nodes);
+                       reinterpret_cast<ull2_t *>(dst), out_nodes, gate);
     if (any_long)
         hipLaunchKernelGGL(sk_regroup_kernel<true>, dim3(n_mids), dim3(SKR_NT), 0, s, mids, n_mids, reinterpret_cast<const ull2_t *>(src),
-                           reinterpret_cast<ull2_t *>(dst), out_nodes);
+                           reinterpret_cast<ull2_t *>(dst), out_nodes, nullptr);
     return hipGetLastError();
 }
 

@@ -978,6 +978,10 @@ uint64_t dnagpu_kmer_index_next_row(const dnagpu_kmer_index *idx);
  * that at small sizes different sequences share fingerprints: the several verify rounds of the build and the run walk of the
  * match (tests).  Results are identical with and without it. */
 #define DNAGPU_DEBUG_WEAK_FINGERPRINT 8192u
+/* DNAGPU_DEBUG_EARLY_L2: the record count queues level 2 behind its device-side gate after a level 1 with
+ * SAMPLED regions too.  By itself it does so only after the plain speculative level: uneven coarse buckets mean repeats, whose
+ * heavy and long mid buckets shut the gate, and a shut gate costs ~0.1 ms.  (Tests: the gate's verdict on such buckets.) */
+#define DNAGPU_DEBUG_EARLY_L2 16384u
 int dnagpu_set_debug(dnagpu_ctx *ctx, unsigned flags);
 
 /* ---- instrumentation ------------------------------------------------------------------------
