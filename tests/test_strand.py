@@ -14,6 +14,7 @@ import pytest
 
 import oracle as orc
 from __graft_entry__ import ROOT, load_package
+from acc_model import splitmix64 as splitmix64_np
 
 ONES = np.uint64(0xFFFFFFFFFFFFFFFF)
 EVEN = 0x5555555555555555
@@ -524,13 +525,6 @@ def test_canonical_add_into_a_resident_accumulator(ctx):
     assert np.array_equal(gk[order], have_k) and np.array_equal(gc[order], have_c)
     for o in hists + [h3, acc]:
         o.free()
-
-
-def splitmix64_np(x):
-    x = np.asarray(x, dtype=np.uint64) + np.uint64(0x9E3779B97F4A7C15)
-    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    return x ^ (x >> np.uint64(31))
 
 
 def per_partition(keys, pbits):
