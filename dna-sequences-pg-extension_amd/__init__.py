@@ -45,7 +45,11 @@ from .binding import (  # noqa: F401
     STRAND_REVCOMP,
     SeqClasses,
     SeqHits,
+    TEXT_FASTA,
+    TEXT_LINES,
+    TEXT_MORE,
     TOP_MAX,
+    TextReport,
     MULTI_AUTO,
     MULTI_COPY,
     MULTI_RCCL,
@@ -64,4 +68,5 @@ from .binding import (  # noqa: F401
     profile_width,
     seq_equal_geometry,
     strerror,
+    text_geometry,
 )

@@ -1,6 +1,7 @@
 """ctypes binding of include/dnagpu.h (libdnagpu.so).  One method per C entry point; numpy arrays
 in and out; errors raise DnaGpuError carrying the status code and the reference's message text."""
 import ctypes as C
+import dataclasses
 import os
 
 import numpy as np
@@ -48,6 +49,9 @@ SPECTRUM_MAX_BINS = 1 << 20
 TOP_MAX = 1 << 20
 ORDER_COUNT_DESC = 0                  # ORDER BY count(*) DESC (test.sql:95)
 ORDER_COUNT_ASC = 1                   # ORDER BY count(*): the rarest first
+TEXT_LINES = 1                        # dnagpu_table_from_text: one sequence per line (COPY ... WITH (FORMAT text))
+TEXT_FASTA = 2                        # ... '>' header lines open records
+TEXT_MORE = 1                         # ... flags: a chunk of a longer file, the unfinished last record is held back
 U64_MAX = 2 ** 64 - 1
 
 
@@ -82,6 +86,23 @@ class JoinStats(C.Structure):
 
     def as_tuple(self):
         return tuple(int(getattr(self, n)) for n, _ in self._fields_)
+
+
+class _TextReportC(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("bases", C.c_uint64), ("consumed", C.c_uint64), ("bad_pos", C.c_uint64),
+                ("bad_record", C.c_uint64), ("bad_char", C.c_char), ("reserved", C.c_char * 7)]
+
+
+@dataclasses.dataclass
+class TextReport:
+    """dnagpu_text_report.  bad_pos / bad_record are None where the C struct holds ~0, bad_char is b"" where it holds 0"""
+    records: int
+    bases: int
+    consumed: int
+    bad_pos: object = None
+    bad_record: object = None
+    bad_char: bytes = b""
+    record_pos: object = None         # uint64[min(records, cap)] when asked for (host), else None
 
 
 class _PhaseTimes(C.Structure):
@@ -219,6 +240,9 @@ def lib():
     L.dnagpu_profile_width.restype = C.c_uint64
     L.dnagpu_table_profile.argtypes = [vp, vp, C.c_int, C.c_uint, C.c_uint64, C.c_uint64, vp, vp, C.c_int]
     L.dnagpu_profile_geometry.argtypes = [u64p, u64p]
+    L.dnagpu_table_from_text.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_uint, C.POINTER(vp), vp, C.c_uint64,
+                                         C.POINTER(_TextReportC)]
+    L.dnagpu_text_geometry.argtypes = [u64p]
     L.dnagpu_dna_equals.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]
     L.dnagpu_table_classes.argtypes = [vp, vp, C.POINTER(vp)]
     for f in ("sequences", "distinct"):
@@ -332,6 +356,13 @@ def abi_version():
 def profile_width(k):
     """columns of a profile: 4^k for k in 1 .. 6, otherwise 0 (dnagpu_profile_width; needs no device)"""
     return int(lib().dnagpu_profile_width(k))
+
+
+def text_geometry():
+    """the bytes of text one workgroup of dnagpu_table_from_text sweeps (needs no device)"""
+    t = C.c_uint64()
+    _chk(lib().dnagpu_text_geometry(C.byref(t)))
+    return t.value
 
 
 def profile_geometry():
@@ -1096,6 +1127,35 @@ class Context:
     def pack_device(self, dev_text, n_bases):
         """the same from n_bases characters already in device memory (any byte alignment)"""
         return self._pack(C.cast(C.c_void_p(dev_text), C.c_char_p), n_bases, 1)
+
+    def _table_from_text(self, text, n_bytes, on_device, format, more, pos_ptr, cap):
+        h, rep = C.c_void_p(), _TextReportC()
+        rc = lib().dnagpu_table_from_text(self.h, text, n_bytes, on_device, format, TEXT_MORE if more else 0, C.byref(h), pos_ptr,
+                                          cap, C.byref(rep))
+        none = lambda v: None if v == U64_MAX else int(v)
+        report = TextReport(int(rep.records), int(rep.bases), int(rep.consumed), none(rep.bad_pos), none(rep.bad_record),
+                            rep.bad_char if rep.bad_char != b"\0" else b"")
+        if rc != OK:
+            e = DnaGpuError(rc)
+            e.report = report
+            raise e
+        return Dna(self, h), report
+
+    def table_from_text(self, data, format=TEXT_LINES, more=False, record_pos=False):
+        """the raw bytes of a text file of sequences -- TEXT_LINES: one per line, TEXT_FASTA: '>' headers open records -- as
+        a resident table -> (Dna, TextReport); record_pos: True for every record's byte offset in report.record_pos, or a cap.
+        An input error raises DnaGpuError with the report as .report (dnagpu_table_from_text)"""
+        b = bytes(data)
+        cap = 0 if record_pos is False else (len(b) + 1 if record_pos is True else int(record_pos))
+        pos = np.empty(max(cap, 1), dtype=np.uint64)
+        d, report = self._table_from_text(b if b else None, len(b), 0, format, more, pos.ctypes.data if cap else None, cap)
+        if record_pos is not False:
+            report.record_pos = pos[:min(cap, report.records)].copy()
+        return d, report
+
+    def table_from_text_device(self, ptr, n_bytes, format=TEXT_LINES, more=False, dev_record_pos=None, record_cap=0):
+        """the same from n_bytes of device memory at any byte alignment; dev_record_pos: record_cap uint64 of device memory"""
+        return self._table_from_text(ptr, n_bytes, 1, format, more, dev_record_pos, record_cap)
 
     def unpack(self, dna, first=0, count=None):
         if count is None:

@@ -5,6 +5,7 @@
 // positions are 4-5 words, so the input side is served by L1 broadcasts; the design target is the
 // store side: every wave-instruction writes 1 KiB of consecutive keys (16 B per lane).
 #include "kernels.hpp"
+#include "text_math.hpp"
 
 namespace dnagpu {
 
@@ -384,14 +385,7 @@ hipError_t launch_hist_summary(const u64 *keys, const u32 *counts, u64 n, u64 *r
 // text <-> packed forms (the steps either side of the path: encode_dna dna.c:114-128 with the
 // validation of dna.c:159-171, decode_dna dna.c:135-152, decode_kmer dna.c:428-452)
 
-// 'A','T','C','G' -> 0,1,2,3 (dna.c:120-123); anything else -> 4
-__device__ __forceinline__ u32 base_code(u32 c)
-{
-    u32 t = (c >> 1) & 3;                        // A=0 C=1 T=2 G=3
-    u32 code = ((t & 1) << 1) | (t >> 1);        // A=0 T=1 C=2 G=3
-    u32 expect = (0x47544341u >> (8 * t)) & 0xff;   // "ACTG"[t]
-    return c == expect ? code : 4u;
-}
+// (base_code, the class of a character, is text_math.hpp's: the table loader of text_kernels.hip shares it)
 
 // one thread per output word: 32 characters in, one packed word out; the position of the first
 // invalid character (what the reference reports) is kept with an atomic minimum

@@ -305,6 +305,38 @@ hipError_t launch_take_starts(const u32 *scan, u64 n, u64 total, u64 *out_starts
 hipError_t launch_take_copy(const u64 *src, const u64 *seg_first, const uint8_t *seg_flip, const u64 *out_starts, u64 n, u64 total,
                             u64 *out, hipStream_t s);
 
+// ---- a text file of sequences into a resident table (text_kernels.hip; the masks of a lane's bytes, the
+// error word and the cut are text_math.hpp's).  All per-tile arrays have n_tiles = text_tiles(n_bytes) entries and are
+// written whole; offsets stored per tile are offset + 1, 0 = none.
+// *cut = where a chunk that more text follows is cut (text_is_cut): LINES one past the last '\n' or 0, FASTA the last
+// header's '>' or n
+hipError_t launch_text_cut(const unsigned char *text, u64 n, int format, u64 *cut, hipStream_t s);
+// FASTA: per tile the last line start ((tile + 1) << 1 | it begins a header) and the last header
+hipError_t launch_text_heads(const unsigned char *text, const u64 *lim, u32 n_tiles, u32 *last_start, u32 *last_header, hipStream_t s);
+// out[i] = max(in[0 .. i)), out[0] = 0; n <= 2^19 + 1; in != out
+hipError_t launch_text_max_scan(const u32 *in, u32 *out, u32 n, hipStream_t s);
+struct TextSweep {
+    const unsigned char *text;
+    const u64 *lim;               // device: the bytes of text that count (res + 3)
+    int format;                   // TEXT_FORMAT_*
+    u32 n_tiles;
+    const u32 *in_state;          // FASTA: max scan of last_start
+    const u32 *header_before;     // FASTA: max scan of last_header
+    u32 *keep_t, *rec_t;          // bases kept / records begun per tile; scanned in place before launch_text_pack
+    u32 *last_seq, *first_header, *seq_before;      // FASTA, for launch_text_finish
+    u64 *res;                     // res[0]: the minimum error word (text_error_key), TEXT_NO_ERROR before the launch
+};
+hipError_t launch_text_sweep(const TextSweep &a, hipStream_t s);
+// FASTA: records without sequence whose two headers lie in different tiles, or that the end of the text closes
+// (seq_before_t: max scan of a.last_seq)
+hipError_t launch_text_finish(const TextSweep &a, const u32 *last_header, const u32 *seq_before_t, hipStream_t s);
+// out2[0] = the record the byte at e belongs to (~0: before the first), out2[1] = the byte; rec_base = the scanned rec_t
+hipError_t launch_text_rank(const unsigned char *text, const u64 *lim, int format, const u32 *rec_base, u64 e, u64 *out2, hipStream_t s);
+// words[0 .. ceil(n_bases / 32)) (cleared here), starts[0 .. n_records], record_pos[0 .. min(n_records, record_cap)) (null:
+// not wanted) from the scanned tile counts
+hipError_t launch_text_pack(const TextSweep &a, u64 n_bases, u64 n_records, u64 *words, u64 *starts, u64 *record_pos, u64 record_cap,
+                            hipStream_t s);
+
 // ---- equal sequences (seqeq_kernels.hip; classes, items, realigned word and fingerprint are
 // seqeq_math.hpp's).  A table, or a window of one: starts = seq_starts + seq_first, n + 1 entries.
 struct SeqTable {

@@ -186,6 +186,18 @@ def lib():
         L.table_screen_failed.argtypes = [vp]
         L.table_screen_end.restype = None
         L.table_screen_end.argtypes = [vp]
+        L.copy_dna_begin.restype = vp
+        L.copy_dna_begin.argtypes = [C.c_int]
+        L.copy_dna_feed.restype = C.c_bool
+        L.copy_dna_feed.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_bool]
+        L.copy_dna_next.restype = C.c_bool
+        L.copy_dna_next.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
+        L.copy_dna_failed.restype = C.c_bool
+        L.copy_dna_failed.argtypes = [vp]
+        L.copy_dna_end.restype = None
+        L.copy_dna_end.argtypes = [vp]
+        L.dna_glue_set_copy_chunk_bytes.restype = None
+        L.dna_glue_set_copy_chunk_bytes.argtypes = [C.c_uint64]
         L.kmer_index_create.restype = vp
         L.kmer_index_create.argtypes = [C.POINTER(_Kmer), C.c_uint64]
         L.kmer_index_rows.restype = C.c_uint64
@@ -718,6 +730,44 @@ def table_screen(rows, set_agg, canonical=False, min_count=1, max_count=None, mi
         return np.array(seq, dtype=np.int64), np.array(nrows, dtype=np.int64), np.array(hits, dtype=np.int64), out
     finally:
         lib().table_screen_end(t)
+
+
+def set_copy_chunk_bytes(n):
+    """bytes per chunk of copy_dna (dna_glue_set_copy_chunk_bytes; default 2^26)"""
+    lib().dna_glue_set_copy_chunk_bytes(int(n))
+
+
+def copy_dna(pieces, format=1):
+    """COPY ... FROM a text file: pieces = the file's bytes in order, in pieces of any size; format 1 = one sequence per line,
+    2 = FASTA -> ([dna], [line]) in file order, line = the 1-based row of the whole file.  An input ERROR raises GlueError with
+    the reference's message and .line = the row of the whole file it belongs to"""
+    c = lib().copy_dna_begin(int(format))
+    if not c:
+        raise _err()
+    try:
+        rows, lines = [], []
+        p, ln = C.c_void_p(), C.c_int64()
+
+        def drain():
+            while lib().copy_dna_next(c, C.byref(p), C.byref(ln)):
+                rows.append(dna(p=p.value))
+                lines.append(ln.value)
+
+        def check(ok):
+            if not ok:
+                e = _err()
+                lib().copy_dna_next(c, None, C.byref(ln))
+                e.line = ln.value
+                raise e
+        for piece in pieces:
+            b = bytes(piece)
+            check(lib().copy_dna_feed(c, b, len(b), False))
+            drain()
+        check(lib().copy_dna_feed(c, None, 0, True))
+        drain()
+        return rows, lines
+    finally:
+        lib().copy_dna_end(c)
 
 
 class kmer_index:

@@ -1835,34 +1835,47 @@ static bool ts_grow(TableScreen *t, uint64_t more)
            agg_grow((void **)&t->hits, &t->cap_hits, need) && agg_grow((void **)&t->out, &t->cap_out, need);
 }
 
+/* the first n sequences of a resident table as values of their own: out[0 .. n), cut from one download of the stream and of
+ * its starts.  On failure none of them stays allocated. */
+static bool table_rows(const dnagpu_dna *table, uint64_t n, Dna **out)
+{
+    const uint64_t total = dnagpu_dna_length(table);
+    uint64_t *words = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)((total + 31) / 32 + 1));
+    uint64_t *starts = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(n + 1));
+    bool ok = words && starts;
+    if (!ok)
+        ereport_error("out of memory");
+    ok = ok && gpu_ok(dnagpu_dna_download(g_ctx, table, words)) && gpu_ok(dnagpu_dna_sequence_starts(g_ctx, table, 0, n + 1, starts, 0));
+    uint64_t made = 0;
+    for (; ok && made < n; made++) {
+        out[made] = dna_cut(words, starts[made], starts[made + 1] - starts[made]);
+        if (!out[made])
+            break;
+    }
+    if (made < n) {
+        ok = false;
+        while (made > 0)
+            dna_free(out[--made]);
+    }
+    free(words);
+    free(starts);
+    return ok;
+}
+
 /* the n_out passing rows of the open batch: their ids, rows and hits from the select's device buffers (n entries apart), the
  * rows themselves from the taken table */
 static bool ts_collect(TableScreen *t, const dnagpu_dna *taken, const uint64_t *dev, uint64_t n, uint64_t n_out)
 {
     if (!ts_grow(t, n_out))
         return false;
-    const uint64_t total = dnagpu_dna_length(taken);
-    uint64_t *words = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)((total + 31) / 32 + 1));
-    uint64_t *starts = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(n_out + 1));
-    bool ok = words && starts;
-    if (!ok)
-        ereport_error("out of memory");
-    ok = ok && gpu_ok(dnagpu_buffer_download(g_ctx, dev, n_out * 8, t->seq + t->n_pass)) &&
-         gpu_ok(dnagpu_buffer_download(g_ctx, dev + n, n_out * 8, t->rows + t->n_pass)) &&
-         gpu_ok(dnagpu_buffer_download(g_ctx, dev + 2 * n, n_out * 8, t->hits + t->n_pass)) &&
-         gpu_ok(dnagpu_dna_download(g_ctx, taken, words)) && gpu_ok(dnagpu_dna_sequence_starts(g_ctx, taken, 0, n_out + 1, starts, 0));
-    for (uint64_t i = 0; ok && i < n_out; i++) {
-        Dna *row = dna_cut(words, starts[i], starts[i + 1] - starts[i]);
-        if (!row) {
-            ok = false;
-            break;
-        }
-        t->seq[t->n_pass] += t->n_added;                                  /* the ordinal of the add call */
-        t->out[t->n_pass++] = row;
-    }
-    free(words);
-    free(starts);
-    return ok;
+    if (!gpu_ok(dnagpu_buffer_download(g_ctx, dev, n_out * 8, t->seq + t->n_pass)) ||
+        !gpu_ok(dnagpu_buffer_download(g_ctx, dev + n, n_out * 8, t->rows + t->n_pass)) ||
+        !gpu_ok(dnagpu_buffer_download(g_ctx, dev + 2 * n, n_out * 8, t->hits + t->n_pass)) ||
+        !table_rows(taken, n_out, t->out + t->n_pass))
+        return false;
+    for (uint64_t i = 0; i < n_out; i++)
+        t->seq[t->n_pass++] += t->n_added;                                /* the ordinal of the add call */
+    return true;
 }
 
 /* the open batch: screened on the device, its passing rows appended, emptied */
@@ -1966,6 +1979,147 @@ void table_screen_end(TableScreen *t)
     free(t->hits);
     free(t->out);
     free(t);
+}
+
+/* ------------------------------------------------------------------ COPY ... FROM a text file: copy_dna */
+
+static uint64_t g_copy_chunk_bytes = (uint64_t)64 << 20;
+
+void dna_glue_set_copy_chunk_bytes(uint64_t n) { g_copy_chunk_bytes = n ? n : 1; }
+
+#define COPY_MAX_CHUNK ((uint64_t)UINT32_MAX)    /* dnagpu_table_from_text's limit for one call */
+
+struct CopyDna {
+    int format;
+    bool failed, finished;
+    char *buf;                                   /* the bytes fed and not yet accounted for by a load */
+    uint64_t len, cap, chunk;
+    Dna **rows;                                  /* the rows loaded and not yet served (NULL once handed out) */
+    uint64_t cap_rows, n_rows, next;
+    uint64_t first_line;                         /* rows of the whole file before rows[0] */
+    int64_t bad_line;                            /* after an input ERROR: the 1-based row of the whole file it belongs to, else 0 */
+};
+
+CopyDna *copy_dna_begin(int format)
+{
+    if (format != DNAGPU_TEXT_LINES && format != DNAGPU_TEXT_FASTA) {
+        ereport_error("copy_dna: the format must be 1 (one sequence per line) or 2 (FASTA)");
+        return NULL;
+    }
+    CopyDna *c = (CopyDna *)calloc(1, sizeof *c);
+    if (!c) {
+        ereport_error("out of memory");
+        return NULL;
+    }
+    c->format = format;
+    c->chunk = g_copy_chunk_bytes < COPY_MAX_CHUNK ? g_copy_chunk_bytes : COPY_MAX_CHUNK;
+    return c;
+}
+
+/* the first n bytes of the buffer through dnagpu_table_from_text; the rows appended, the bytes accounted for dropped */
+static bool copy_load(CopyDna *c, uint64_t n, bool more)
+{
+    dnagpu_dna *d = NULL;
+    dnagpu_text_report rep;
+    if (!ctx())
+        return false;
+    const int rc = dnagpu_table_from_text(g_ctx, c->buf, n, 0, c->format, more ? DNAGPU_TEXT_MORE : 0u, &d, NULL, 0, &rep);
+    if (rc != DNAGPU_OK) {
+        if (rep.bad_pos != UINT64_MAX) {                                  /* an input error: the reference's message verbatim */
+            ereport_error("%s", dnagpu_last_error());
+            c->bad_line = rep.bad_record == UINT64_MAX ? 0 : (int64_t)(c->first_line + c->n_rows + rep.bad_record + 1);
+            return false;
+        }
+        return gpu_ok(rc);
+    }
+    if (c->next == c->n_rows) {                                           /* everything served: the array starts over */
+        c->first_line += c->n_rows;
+        c->n_rows = c->next = 0;
+    }
+    bool ok = agg_grow((void **)&c->rows, &c->cap_rows, c->n_rows + rep.records) &&
+              (rep.records == 0 || table_rows(d, rep.records, c->rows + c->n_rows));
+    dnagpu_dna_free(g_ctx, d);
+    if (!ok)
+        return false;
+    c->n_rows += rep.records;
+    if (rep.consumed && c->len > rep.consumed)
+        memmove(c->buf, c->buf + rep.consumed, (size_t)(c->len - rep.consumed));
+    c->len -= rep.consumed;
+    if (more && rep.consumed == 0) {                                      /* a record longer than the chunk */
+        if (c->chunk >= COPY_MAX_CHUNK) {
+            ereport_error("copy_dna: a record is longer than 2^32 - 1 bytes");
+            return false;
+        }
+        c->chunk = c->chunk > COPY_MAX_CHUNK / 2 ? COPY_MAX_CHUNK : 2 * c->chunk;
+    }
+    return true;
+}
+
+bool copy_dna_feed(CopyDna *c, const char *bytes, size_t n, bool last)
+{
+    if (c->failed || c->finished) {
+        ereport_error("copy_dna: bytes fed after the last ones or after the load failed");
+        return false;
+    }
+    if (n && !bytes) {
+        ereport_error("copy_dna: the bytes are missing");
+        return false;
+    }
+    if (c->len + n > c->cap) {
+        uint64_t cap = c->cap ? c->cap : 4096;
+        while (cap < c->len + n)
+            cap *= 2;
+        char *grown = (char *)realloc(c->buf, (size_t)cap);
+        if (!grown) {
+            ereport_error("out of memory");
+            c->failed = true;
+            return false;
+        }
+        c->buf = grown;
+        c->cap = cap;
+    }
+    if (n)
+        memcpy(c->buf + c->len, bytes, n);
+    c->len += n;
+    while (!c->failed && c->len >= c->chunk)
+        c->failed = !copy_load(c, c->chunk, true);
+    if (!c->failed && last) {
+        c->failed = !copy_load(c, c->len, false);
+        c->finished = true;
+    }
+    return !c->failed;
+}
+
+bool copy_dna_next(CopyDna *c, Dna **row, int64_t *line)
+{
+    if (c->failed) {
+        if (line)
+            *line = c->bad_line;
+        return false;
+    }
+    if (c->next >= c->n_rows)
+        return false;
+    const uint64_t i = c->next++;
+    if (line)
+        *line = (int64_t)(c->first_line + i + 1);
+    if (row) {
+        *row = c->rows[i];                                                /* the caller's from here on */
+        c->rows[i] = NULL;
+    }
+    return true;
+}
+
+bool copy_dna_failed(const CopyDna *c) { return c->failed; }
+
+void copy_dna_end(CopyDna *c)
+{
+    if (!c)
+        return;
+    for (uint64_t i = 0; i < c->n_rows; i++)
+        dna_free(c->rows[i]);
+    free(c->rows);
+    free(c->buf);
+    free(c);
 }
 
 /* ------------------------------------------------------------------ the index over a stored kmer column */

@@ -281,6 +281,29 @@ bool table_screen_next(TableScreen *t, int64_t *seq, int64_t *rows, int64_t *hit
 bool table_screen_failed(const TableScreen *t);
 void table_screen_end(TableScreen *t);
 
+/* ---- COPY dna_sequences (sequence) FROM '...' WITH (FORMAT text) (test.sql:128-130), and the same from a FASTA file: the
+ * bytes of the file go in as they are read, the rows come out ----
+ * begin: format = 1 (one sequence per line) or 2 (FASTA: '>' header lines open records), dnagpu_table_from_text's formats.
+ * feed = the next bytes of the file, in order, in pieces of any size; last = these are the file's last bytes (n may be 0).
+ *   The bytes are buffered; every full chunk (dna_glue_set_copy_chunk_bytes, default 64 MiB) is split, validated and packed
+ *   on the device (dnagpu_table_from_text with DNAGPU_TEXT_MORE), the unfinished record at its end is carried over to the
+ *   next chunk, and a record longer than the chunk doubles the chunk; the remainder is loaded without the flag on `last`.
+ * next = one loaded row, in file order, as a malloc'd Dna (dna_free it; row may be NULL); line = its 1-based row of the whole
+ *   file (may be NULL).  Rows can be fetched between feeds or after the last.  false = no row is waiting, or an ERROR:
+ *   copy_dna_failed.
+ * An input ERROR -- from feed -- carries the reference's message verbatim ("Invalid character in DNA sequence: %c", "DNA
+ *   sequence cannot be empty"; FASTA: "sequence data before the first header"); after it next returns false with line = the
+ *   1-based row of the whole file the error belongs to (0: before the first record), as COPY names the line, and no further
+ *   row is served. */
+typedef struct CopyDna CopyDna;
+CopyDna *copy_dna_begin(int format);
+bool copy_dna_feed(CopyDna *c, const char *bytes, size_t n, bool last);
+bool copy_dna_next(CopyDna *c, Dna **row, int64_t *line);
+bool copy_dna_failed(const CopyDna *c);
+void copy_dna_end(CopyDna *c);
+/* bytes per chunk of copy_dna (default 2^26); tests use small values to force many chunks */
+void dna_glue_set_copy_chunk_bytes(uint64_t n);
+
 /* ---- CREATE INDEX ... ON kmer_data_t USING spgist (kmer_sequence spgist_kmer_ops) and the index scans of `=`, `^@` and `@>`
  * over the stored column (dna--1.0.sql:304-314; test.sql:156-270) ----
  * create: column[i] = the kmer of heap row i; the keys go to the device once and are sorted there (dnagpu_kmer_index_build).

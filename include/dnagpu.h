@@ -291,6 +291,61 @@ int dnagpu_dna_take(dnagpu_ctx *ctx, const dnagpu_dna *table,
                     uint64_t n_ids, int on_device, dnagpu_dna **out);
 int dnagpu_dna_sequence_starts(dnagpu_ctx *ctx, const dnagpu_dna *dna, uint64_t first, uint64_t count,
                                uint64_t *out_starts, int out_on_device);
+/* ---- a text file of sequences as a resident table (COPY dna_sequences (sequence) FROM '...' WITH (FORMAT text),
+ * test.sql:128-130) ----
+ * dnagpu_table_from_text: the raw bytes of a file -- DNAGPU_TEXT_LINES: one sequence per line; DNAGPU_TEXT_FASTA: '>' header
+ *   lines open records -- are split, validated and packed on the device.  text is host memory, or device memory at any
+ *   byte alignment when text_on_device != 0; no byte at or beyond text + n_bytes is read.
+ * Result: a new owned dnagpu_dna (dnagpu_dna_free), exactly what dnagpu_dna_take returns.  Its stream is the records' bases
+ *   back to back, ceil(bases / 32) words, the bits behind the last base zero.  It holds a resident sequence set of `records`
+ *   sequences (the marks and records + 1 starts), so every entry point that takes a resident table takes it.  records == 0
+ *   -- empty text, or with DNAGPU_TEXT_MORE a chunk that holds no finished record -- gives 0 bases and no set.
+ * Characters: only A T C G are bases (validate_dna_sequence, dna.c:159-171).  A lower-case letter, N, a space, a tab, a
+ *   backslash, and a '\r' that is not directly followed by '\n' are invalid characters.  A line ends at '\n'; a '\r'
+ *   directly before that '\n' belongs to the terminator.
+ * LINES: every line is a record; a last line without a terminator is a record, and text that ends in '\n' has no extra
+ *   empty record.  An empty line is the reference's "DNA sequence cannot be empty" (dna.c:160-161): DNAGPU_ERR_DNA_EMPTY,
+ *   reported at the offset of the line's first byte, which is its terminator.
+ * FASTA: a line whose first byte is '>' is a header; the whole line is ignored and no byte of it is validated.  A header
+ *   opens a record; the bases of the non-header lines that follow are joined into it; blank lines are ignored.  A record
+ *   with no base is DNAGPU_ERR_DNA_EMPTY, reported at its '>'.  A base or an invalid character before the
+ *   first header is DNAGPU_ERR_BAD_ARG at that byte ("sequence data before the first header").
+ * Errors: every input error has a byte offset, and the one with the lowest offset wins (COPY stops at the first bad row).
+ *   report (may be NULL) gets bad_pos, bad_record and bad_char; dnagpu_last_error() is the reference's message verbatim,
+ *   "Invalid character in DNA sequence: %c" or "DNA sequence cannot be empty".  On every error *out is left as it was and
+ *   nothing stays allocated; out_record_pos may then hold anything, and records / bases / consumed of the report are 0.
+ * DNAGPU_TEXT_MORE: text is a chunk of a longer file, and its unfinished last record is held back.  LINES: only lines that
+ *   end in '\n' are records, and consumed is one past the last '\n' (0: there is none).  FASTA: the record that the last
+ *   header opens is held back, and consumed is the offset of that header's '>'; a chunk with no header and no sequence byte
+ *   has consumed = n_bytes.  Bytes at or beyond consumed raise no error.  The caller prepends text[consumed ..] to the next
+ *   chunk, and passes the file's last chunk without the flag.  consumed == 0 over a full chunk means that the record is longer
+ *   than the chunk: the caller enlarges the chunk (to at most 2^32 - 1 bytes) and calls again.
+ * out_record_pos (may be NULL with record_cap == 0): entry r is the byte offset of record r's first byte -- in FASTA its '>',
+ *   so the caller reads the name from its own text.  At most record_cap entries are written.  It is host memory, or device
+ *   memory when text_on_device != 0.
+ * Checks, in order: a NULL ctx or out, a NULL text with n_bytes > 0, or a NULL out_record_pos with record_cap > 0, is
+ *   DNAGPU_ERR_BAD_ARG; a format other than 1 or 2, or flags other than 0 or 1, is DNAGPU_ERR_BAD_ARG; n_bytes > 2^32 - 1 is
+ *   DNAGPU_ERR_TOO_LARGE (the scans are 32-bit and a resident table holds at most 2^32 - 1 bases: larger files go chunk by
+ *   chunk with DNAGPU_TEXT_MORE).  These need no device.  Then the input errors above, then DNAGPU_ERR_OOM.  The call
+ *   waits for its work.
+ * dnagpu_text_geometry: *tile_bytes = the bytes one workgroup sweeps (the edge shapes of the tests); needs no device. */
+#define DNAGPU_TEXT_LINES 1   /* one sequence per line: COPY ... WITH (FORMAT text), test.sql:128-130 */
+#define DNAGPU_TEXT_FASTA 2   /* '>' header lines open records; the sequence lines of a record are joined */
+#define DNAGPU_TEXT_MORE  1u  /* flags: text is a chunk of a longer file; the unfinished last record is held back */
+typedef struct dnagpu_text_report {
+    uint64_t records;     /* sequences in the result */
+    uint64_t bases;       /* bases in the result */
+    uint64_t consumed;    /* bytes of text the result accounts for (== n_bytes without MORE) */
+    uint64_t bad_pos;     /* on an input error: byte offset it is reported at, else ~0 */
+    uint64_t bad_record;  /* on an input error: 0-based record it belongs to (~0: before the first record), else ~0 */
+    char     bad_char;    /* DNAGPU_ERR_DNA_INVALID_CHAR: the character, else 0 */
+    char     reserved[7];
+} dnagpu_text_report;
+int dnagpu_table_from_text(dnagpu_ctx *ctx, const char *text, uint64_t n_bytes, int text_on_device,
+                           int format, unsigned flags, dnagpu_dna **out,
+                           uint64_t *out_record_pos, uint64_t record_cap,
+                           dnagpu_text_report *report);
+int dnagpu_text_geometry(uint64_t *tile_bytes);
 /* Same over an arbitrary array of n keys of k bases already in device memory.  dev_keys is used as
  * scratch and its contents are unspecified afterwards. */
 int dnagpu_count_keys(dnagpu_ctx *ctx, uint64_t *dev_keys, uint64_t n, int k, dnagpu_hist **out);
