@@ -52,6 +52,9 @@ ORDER_COUNT_ASC = 1                   # ORDER BY count(*): the rarest first
 TEXT_LINES = 1                        # dnagpu_table_from_text: one sequence per line (COPY ... WITH (FORMAT text))
 TEXT_FASTA = 2                        # ... '>' header lines open records
 TEXT_MORE = 1                         # ... flags: a chunk of a longer file, the unfinished last record is held back
+TEXT_FASTQ = 3                        # dnagpu_reads_from_text only: strict four-line records
+AMBIG_ERROR, AMBIG_DROP, AMBIG_SPLIT = 0, 1, 2      # dnagpu_reads_from_text: what an IUPAC ambiguity letter does
+READS_MORE, READS_FOLD_CASE = 1, 2    # ... flags
 U64_MAX = 2 ** 64 - 1
 
 
@@ -103,6 +106,33 @@ class TextReport:
     bad_record: object = None
     bad_char: bytes = b""
     record_pos: object = None         # uint64[min(records, cap)] when asked for (host), else None
+
+
+class _ReadsOptionsC(C.Structure):
+    _fields_ = [("format", C.c_int), ("ambiguous", C.c_int), ("flags", C.c_uint), ("reserved", C.c_uint), ("min_bases", C.c_uint64)]
+
+
+class _ReadsReportC(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("records", "sequences", "bases", "consumed", "ambiguous", "dropped", "short_out",
+                                          "bad_pos", "bad_record")] + [("bad_char", C.c_char), ("reserved", C.c_char * 7)]
+
+
+@dataclasses.dataclass
+class ReadsReport:
+    """dnagpu_reads_report.  bad_pos / bad_record are None where the C struct holds ~0, bad_char is b"" where it holds 0"""
+    records: int
+    sequences: int
+    bases: int
+    consumed: int
+    ambiguous: int
+    dropped: int
+    short_out: int
+    bad_pos: object = None
+    bad_record: object = None
+    bad_char: bytes = b""
+    record_pos: object = None         # uint64[min(records, cap)] when asked for (host), else None
+    src_record: object = None         # uint64[min(sequences, cap)] each when asked for (host), else None
+    src_offset: object = None
 
 
 class _PhaseTimes(C.Structure):
@@ -243,6 +273,8 @@ def lib():
     L.dnagpu_table_from_text.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_uint, C.POINTER(vp), vp, C.c_uint64,
                                          C.POINTER(_TextReportC)]
     L.dnagpu_text_geometry.argtypes = [u64p]
+    L.dnagpu_reads_from_text.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(_ReadsOptionsC), C.POINTER(vp), vp, C.c_uint64,
+                                         vp, vp, C.c_uint64, C.POINTER(_ReadsReportC)]
     L.dnagpu_dna_equals.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]
     L.dnagpu_table_classes.argtypes = [vp, vp, C.POINTER(vp)]
     for f in ("sequences", "distinct"):
@@ -1156,6 +1188,51 @@ class Context:
     def table_from_text_device(self, ptr, n_bytes, format=TEXT_LINES, more=False, dev_record_pos=None, record_cap=0):
         """the same from n_bytes of device memory at any byte alignment; dev_record_pos: record_cap uint64 of device memory"""
         return self._table_from_text(ptr, n_bytes, 1, format, more, dev_record_pos, record_cap)
+
+    def _reads_from_text(self, text, n_bytes, on_device, format, ambiguous, fold_case, min_bases, more, pos_ptr, cap, rec_ptr,
+                         off_ptr, seq_cap):
+        h, rep = C.c_void_p(), _ReadsReportC()
+        opt = _ReadsOptionsC(format, ambiguous, (READS_MORE if more else 0) | (READS_FOLD_CASE if fold_case else 0), 0, min_bases)
+        rc = lib().dnagpu_reads_from_text(self.h, text, n_bytes, on_device, C.byref(opt), C.byref(h), pos_ptr, cap, rec_ptr, off_ptr,
+                                          seq_cap, C.byref(rep))
+        none = lambda v: None if v == U64_MAX else int(v)
+        report = ReadsReport(int(rep.records), int(rep.sequences), int(rep.bases), int(rep.consumed), int(rep.ambiguous),
+                             int(rep.dropped), int(rep.short_out), none(rep.bad_pos), none(rep.bad_record),
+                             rep.bad_char if rep.bad_char != b"\0" else b"")
+        if rc != OK:
+            e = DnaGpuError(rc)
+            e.report = report
+            raise e
+        return Dna(self, h), report
+
+    def reads_from_text(self, data, format=TEXT_FASTQ, ambiguous=AMBIG_ERROR, fold_case=False, min_bases=0, more=False,
+                        record_pos=False, source=False):
+        """the raw bytes of a FASTQ (TEXT_FASTQ), FASTA or one-per-line file as a resident table -> (Dna, ReadsReport).
+        ambiguous: AMBIG_ERROR / AMBIG_DROP / AMBIG_SPLIT, what an IUPAC ambiguity letter does; fold_case: lower case counts as
+        upper; min_bases: shorter sequences are left out.  record_pos: True for every source record's byte offset in
+        report.record_pos, or a cap; source: True for report.src_record / report.src_offset of every sequence, or a cap.
+        An input error raises DnaGpuError with the report as .report (dnagpu_reads_from_text)"""
+        b = bytes(data)
+        cap = 0 if record_pos is False else (len(b) + 1 if record_pos is True else int(record_pos))
+        seq_cap = 0 if source is False else (len(b) + 1 if source is True else int(source))
+        pos = np.empty(max(cap, 1), dtype=np.uint64)
+        rec, off = np.empty(max(seq_cap, 1), dtype=np.uint64), np.empty(max(seq_cap, 1), dtype=np.uint64)
+        d, report = self._reads_from_text(b if b else None, len(b), 0, format, ambiguous, fold_case, min_bases, more,
+                                          pos.ctypes.data if cap else None, cap, rec.ctypes.data if seq_cap else None,
+                                          off.ctypes.data if seq_cap else None, seq_cap)
+        if record_pos is not False:
+            report.record_pos = pos[:min(cap, report.records)].copy()
+        if source is not False:
+            report.src_record = rec[:min(seq_cap, report.sequences)].copy()
+            report.src_offset = off[:min(seq_cap, report.sequences)].copy()
+        return d, report
+
+    def reads_from_text_device(self, ptr, n_bytes, format=TEXT_FASTQ, ambiguous=AMBIG_ERROR, fold_case=False, min_bases=0,
+                               more=False, dev_record_pos=None, record_cap=0, dev_src_record=None, dev_src_offset=None, seq_cap=0):
+        """the same from n_bytes of device memory at any byte alignment; dev_record_pos: record_cap uint64 of device memory,
+        dev_src_record / dev_src_offset: seq_cap uint64 of device memory each"""
+        return self._reads_from_text(ptr, n_bytes, 1, format, ambiguous, fold_case, min_bases, more, dev_record_pos, record_cap,
+                                     dev_src_record, dev_src_offset, seq_cap)
 
     def unpack(self, dna, first=0, count=None):
         if count is None:

@@ -337,6 +337,52 @@ hipError_t launch_text_rank(const unsigned char *text, const u64 *lim, int forma
 hipError_t launch_text_pack(const TextSweep &a, u64 n_bases, u64 n_records, u64 *words, u64 *starts, u64 *record_pos, u64 record_cap,
                             hipStream_t s);
 
+// ---- FASTQ and real FASTA into a resident table (reads_kernels.hip).  The per-tile arrays are as above;
+// the stages in order: FASTQ launch_reads_newlines -> launch_scan_u32 -> launch_reads_fastq_cut (LINES / FASTA:
+// launch_text_cut, launch_text_heads and its two maximum scans) -> launch_reads_sweep -> FASTA launch_text_finish, SPLIT the
+// maximum scans of last_keep / last_brk and launch_reads_finish -> the additive scans, in place -> launch_reads_pack.
+struct ReadsSweep {
+    const unsigned char *text;
+    const u64 *lim;               // device: the bytes of text that count (res + 3)
+    int format;                   // TEXT_FORMAT_*
+    int ambiguous;                // READS_AMBIG_*
+    int fold;                     // DNAGPU_READS_FOLD_CASE
+    u32 n_tiles;
+    const u32 *in_state, *header_before;            // FASTA: as TextSweep's
+    const u32 *line_base;                           // FASTQ: the '\n' before every tile
+    u32 *keep_t, *rec_t;          // bases kept / records begun per tile
+    u32 *last_seq, *first_header, *seq_before;      // FASTA, for launch_text_finish
+    u32 *piece_t, *sc_t;          // SPLIT: piece starts / sequence characters per tile
+    u32 *last_keep, *last_brk, *undecided;          // SPLIT: for launch_reads_finish
+    const u32 *keep_before_t, *brk_before_t;        // SPLIT: the maximum scans of last_keep / last_brk
+    u64 *res;                     // res[0]: the minimum error word, res[4]: += the ambiguity letters of sequence lines
+};
+struct ReadsPack {
+    u64 n_bases, n_seqs, n_records;
+    u64 *words, *starts;          // ceil(n_bases / 32) words (cleared by the launcher), n_seqs + 1 starts
+    u64 *record_pos;              // null: not wanted
+    u64 record_cap;
+    u32 *rec_amb;                 // DROP: ambiguity letters per record, zero before the launch; else null
+    u32 *rec_sc;                  // SPLIT: per record
+    u64 *src_record, *src_offset; // SPLIT: per sequence
+};
+hipError_t launch_reads_newlines(const unsigned char *text, u64 n, u32 n_tiles, u32 *nl_t, hipStream_t s);
+// *lim = the cut (more), or res[0] takes the truncated record's error word (not more, lines no multiple of four)
+hipError_t launch_reads_fastq_cut(const unsigned char *text, u64 n, u32 n_tiles, const u32 *nl_t, const u32 *nl_base, const u32 *total,
+                                  bool more, u64 *lim, u64 *res, hipStream_t s);
+// out3 = {record of the byte at e, the byte, the role of its line}
+hipError_t launch_reads_fastq_rank(const unsigned char *text, u64 n, const u32 *nl_base, u64 e, u64 *out3, hipStream_t s);
+hipError_t launch_reads_sweep(const ReadsSweep &a, hipStream_t s);
+hipError_t launch_reads_finish(const ReadsSweep &a, hipStream_t s);
+hipError_t launch_reads_pack(const ReadsSweep &a, const ReadsPack &p, hipStream_t s);
+hipError_t launch_reads_offsets(const u64 *src_record, u64 *src_offset, const u32 *rec_sc, u64 n, hipStream_t s);
+hipError_t launch_reads_identity(u64 *src_record, u64 *src_offset, u64 n, hipStream_t s);
+// flags[i] = sequence i stays; res2[0] += dropped for an ambiguity letter, res2[1] += shorter than min_bases
+hipError_t launch_reads_select(const u64 *starts, const u32 *rec_amb, u64 n, u64 min_bases, u32 *flags, u64 *res2, hipStream_t s);
+// rank: the scanned flags; len32: zero before the launch
+hipError_t launch_reads_move(const u64 *starts, const u64 *src_record, const u64 *src_offset, const u32 *flags, const u32 *rank, u64 n,
+                             u64 *seg_first, u32 *len32, u64 *src_record_out, u64 *src_offset_out, hipStream_t s);
+
 // ---- equal sequences (seqeq_kernels.hip; classes, items, realigned word and fingerprint are
 // seqeq_math.hpp's).  A table, or a window of one: starts = seq_starts + seq_first, n + 1 entries.
 struct SeqTable {

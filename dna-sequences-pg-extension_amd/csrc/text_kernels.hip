@@ -15,66 +15,9 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
-#include "text_math.hpp"
+#include "text_device.hpp"
 
 namespace dnagpu {
-
-// ---- one lane's chunk: the TEXT_CHUNK bytes at byte b of the n bytes at text.  16-byte loads where the chunk is whole and
-// the address allows, bytes otherwise; no byte at or beyond text + n is read, and bytes beyond n count as no character.
-__device__ __forceinline__ TextChunk text_load(const unsigned char *__restrict__ text, u64 n, u64 b)
-{
-    TextChunk c = {};
-    if (b >= n)
-        return c;
-    const u64 left = n - b;
-    c.valid = text_low_bits(left >= TEXT_CHUNK ? TEXT_CHUNK : (u32)left);
-    u32 w[8];
-    if (left >= TEXT_CHUNK && (reinterpret_cast<uintptr_t>(text + b) & 15) == 0) {
-        const uint4 *p = reinterpret_cast<const uint4 *>(text + b);
-        const uint4 lo = p[0], hi = p[1];
-        w[0] = lo.x; w[1] = lo.y; w[2] = lo.z; w[3] = lo.w;
-        w[4] = hi.x; w[5] = hi.y; w[6] = hi.z; w[7] = hi.w;
-    } else {
-#pragma unroll
-        for (u32 q = 0; q < 8; q++) {
-            u32 v = 0;
-            for (u32 r = 0; r < 4; r++)
-                if (q * 4 + r < left)
-                    v |= (u32)text[b + q * 4 + r] << (8 * r);
-            w[q] = v;
-        }
-    }
-#pragma unroll
-    for (u32 j = 0; j < TEXT_CHUNK; j++)
-        text_chunk_byte(c, j, (w[j >> 2] >> (8 * (j & 3))) & 0xff);
-    c.prev_nl = b == 0 || text[b - 1] == '\n';
-    c.next_nl = left > TEXT_CHUNK && text[b + TEXT_CHUNK] == '\n';
-    return c;
-}
-
-// the maximum of v over the threads before this one (0 for thread 0), by the TEXT_THREADS threads of the workgroup;
-// wmax: one word of LDS per wave.  Synchronises.
-__device__ __forceinline__ u32 text_block_max_before(u32 v, u32 *wmax)
-{
-    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u32 inc = v;
-#pragma unroll
-    for (u32 off = 1; off < 64; off <<= 1) {
-        const u32 o = __shfl_up(inc, off);
-        if (lane >= off)
-            inc = inc > o ? inc : o;
-    }
-    u32 ex = __shfl_up(inc, 1);
-    if (lane == 0)
-        ex = 0;
-    if (lane == 63)
-        wmax[wave] = inc;
-    __syncthreads();
-    for (u32 w = 0; w < wave; w++)
-        ex = ex > wmax[w] ? ex : wmax[w];
-    __syncthreads();
-    return ex;
-}
 
 // What the two sweeps make of a lane's chunk, alike: the bases kept, the records begun, and their ranks inside the tile.
 struct TextLane {
@@ -220,58 +163,14 @@ __global__ __launch_bounds__(TEXT_THREADS) void text_sweep_kernel(const unsigned
             err = text_error_key(b + j, (invalid >> j) & 1 ? TEXT_ERR_CHAR : TEXT_ERR_EMPTY);
         }
     } else {
-        // positions inside the tile + 1 (0: none): the last header and the last kept base before this chunk
-        const u32 seq = l.keep | invalid;
-        const u32 at = tid * TEXT_CHUNK + 1;
-        const u32 hkey = l.headers ? at + text_top_bit(l.headers) : 0u;
-        const u32 qkey = l.keep ? at + text_top_bit(l.keep) : 0u;
-        const u32 h_before = text_block_max_before(hkey, s.wmax), q_before = text_block_max_before(qkey, s.wmax);
-        const bool seen = header_before[tile] != 0 || h_before != 0;
-        if (seq) {
-            const u32 j = (u32)__builtin_ctz(seq);
-            if (!seen && !(l.headers & text_low_bits(j)))
-                err = text_error_key(b + j, TEXT_ERR_ORPHAN);
-        }
-        if (err == TEXT_NO_ERROR && invalid)
-            err = text_error_key(b + (u32)__builtin_ctz(invalid), TEXT_ERR_CHAR);
-        // every header closes the record before it: empty when no base lies between the two headers
-        u32 hs = l.headers;
-        while (hs) {
-            const u32 j = (u32)__builtin_ctz(hs);
-            const u32 below = text_low_bits(j);
-            const u32 ph = l.headers & below ? at + text_top_bit(l.headers & below) : h_before;
-            const u32 pq = l.keep & below ? at + text_top_bit(l.keep & below) : q_before;
-            if (ph) {
-                if (pq < ph) {
-                    const u64 e = text_error_key(tile_at + ph - 1, TEXT_ERR_EMPTY);
-                    err = e < err ? e : err;
-                }
-            } else {                                 // the tile's first header: the record before it began in another tile
-                first_header[tile] = (u32)(b + j + 1);
-                seq_before[tile] = pq ? (u32)(tile_at + pq) : 0u;
-            }
-            hs &= hs - 1;
-        }
-        if (tid == TEXT_THREADS - 1) {
-            const u32 q = q_before > qkey ? q_before : qkey;
-            last_seq[tile] = q ? (u32)(tile_at + q) : 0u;
-            if (!(h_before | hkey)) {
-                first_header[tile] = 0;
-                seq_before[tile] = 0;
-            }
-        }
+        err = text_fasta_records(l.headers, l.keep, l.keep | invalid, invalid, b, tile_at, tile, header_before[tile] != 0, s.wmax,
+                                 last_seq, first_header, seq_before);
     }
     if (tid == 0) {
         keep_t[tile] = l.keep_tile;
         rec_t[tile] = l.rec_tile;
     }
-#pragma unroll
-    for (u32 off = 32; off > 0; off >>= 1) {
-        const u64 o = __shfl_down(err, off);
-        err = o < err ? o : err;
-    }
-    if ((tid & 63) == 0 && err != TEXT_NO_ERROR)
-        atomicMin(&res[0], (unsigned long long)err);
+    text_error_min(err, res);
 }
 
 // ---- FASTA, across tiles: the record that the first header of a tile closes, and the record the end of the text closes.
@@ -343,21 +242,14 @@ __global__ __launch_bounds__(TEXT_THREADS) void text_pack_kernel(const unsigned 
                                                                  u64 *__restrict__ record_pos, u64 record_cap)
 {
     __shared__ TextLds s;
-    __shared__ unsigned long long packed[TEXT_TILE_BYTES / 32 + 2];
+    __shared__ unsigned long long packed[TEXT_PACKED_WORDS];
     const u32 tid = threadIdx.x, tile = blockIdx.x;
     const u64 n = *lim, b = (u64)tile * TEXT_TILE_BYTES + (u64)tid * TEXT_CHUNK;
-    for (u32 i = tid; i < TEXT_TILE_BYTES / 32 + 2; i += TEXT_THREADS)
+    for (u32 i = tid; i < TEXT_PACKED_WORDS; i += TEXT_THREADS)
         packed[i] = 0;
     const TextLane l = text_lane<FASTA>(text, n, b, FASTA && (in_state[tile] & 1), s);     // (synchronises: packed is zero)
     const u64 out_at = keep_base[tile];              // the result's base this tile's first kept base becomes
-    const u32 lead = (u32)(out_at & 31);
-    if (l.keep) {
-        const u64 v = text_compact(l.c.codes, l.keep);
-        const u32 q = lead + l.keep_before, sh = 2 * (q & 31);
-        atomicOr(&packed[q >> 5], (unsigned long long)(v << sh));
-        if ((q & 31) + (u32)__popc(l.keep) > 32)
-            atomicOr(&packed[(q >> 5) + 1], (unsigned long long)(v >> (64 - sh)));      // (sh > 0 here)
-    }
+    text_pack_lane(packed, out_at, l.keep_before, l.c.codes, l.keep);
     u32 rec = l.rec, r = 0;
     while (rec) {
         const u32 j = (u32)__builtin_ctz(rec);
@@ -370,17 +262,7 @@ __global__ __launch_bounds__(TEXT_THREADS) void text_pack_kernel(const unsigned 
     if (tile == 0 && tid == 0)
         starts[n_records] = n_bases;
     __syncthreads();
-    const u32 n_words = (lead + l.keep_tile + 31) / 32;
-    const u64 w0 = out_at >> 5;
-    for (u32 i = tid; i < n_words; i += TEXT_THREADS) {
-        const unsigned long long v = packed[i];
-        if (i == 0 || i == n_words - 1) {
-            if (v)
-                atomicOr(reinterpret_cast<unsigned long long *>(&words[w0 + i]), v);
-        } else {
-            words[w0 + i] = v;
-        }
-    }
+    text_pack_flush(packed, out_at, l.keep_tile, words);
 }
 
 // ---------------------------------------------------------------- launchers

@@ -128,4 +128,97 @@ inline u64 text_more_cut(const unsigned char *text, u64 n, int format)      // t
     return text_no_cut(n, format);
 }
 
+// ================================================================ dnagpu_reads_from_text
+// The general entry reads the same chunks.  What it adds: FASTQ (the role of a line is its index mod 4), the IUPAC
+// ambiguity letters as a class of their own, lower-case bases, and the starts of the pieces a record is cut into.
+constexpr int TEXT_FORMAT_FASTQ = 3;                               // DNAGPU_TEXT_FASTQ
+constexpr int READS_AMBIG_ERROR = 0, READS_AMBIG_DROP = 1, READS_AMBIG_SPLIT = 2;      // DNAGPU_AMBIG_*
+
+// The error word of the general entry is text_error_key's with one more kind.  TEXT_ERR_ORPHAN stands for every "a record
+// does not open as it must" (FASTA: data before the first header; FASTQ: no '@', no '+' -- the line's role tells which),
+// so that at equal offsets it comes before TEXT_ERR_TRUNC.
+constexpr u32 TEXT_ERR_TRUNC = 3;        // FASTQ without MORE: the lines are no multiple of four
+
+// N R Y K M S W B D H V as bits of letter - 'A'
+constexpr u32 READS_AMBIG_LETTERS = (1u << ('N' - 'A')) | (1u << ('R' - 'A')) | (1u << ('Y' - 'A')) | (1u << ('K' - 'A')) |
+                                    (1u << ('M' - 'A')) | (1u << ('S' - 'A')) | (1u << ('W' - 'A')) | (1u << ('B' - 'A')) |
+                                    (1u << ('D' - 'A')) | (1u << ('H' - 'A')) | (1u << ('V' - 'A'));
+// DNAGPU_READS_FOLD_CASE: a lower-case letter counts as its upper case; every other byte is itself
+__host__ __device__ __forceinline__ u32 reads_fold(u32 byte, bool fold)
+{
+    return fold && byte >= 'a' && byte <= 'z' ? byte - 32 : byte;
+}
+__host__ __device__ __forceinline__ bool reads_is_ambig(u32 byte)      // byte: folded already
+{
+    return byte >= 'A' && byte <= 'Z' && ((READS_AMBIG_LETTERS >> (byte - 'A')) & 1);
+}
+
+struct ReadsChunk {
+    TextChunk c;     // (base and codes: after folding)
+    u32 amb;         // ambiguity letters
+    u32 at, plus;    // '@', '+'
+};
+__host__ __device__ __forceinline__ void reads_chunk_byte(ReadsChunk &r, u32 j, u32 byte, bool fold)
+{
+    const u32 up = reads_fold(byte, fold);
+    text_chunk_byte(r.c, j, up);
+    r.amb |= (u32)reads_is_ambig(up) << j;
+    r.at |= (u32)(byte == '@') << j;
+    r.plus |= (u32)(byte == '+') << j;
+}
+
+// FASTQ: role[q] = the bytes of the chunk that lie in lines of role q = line index mod 4 (0 '@' line, 1 sequence, 2 '+'
+// line, 3 quality).  nl: the chunk's '\n' (a '\n' belongs to the line it ends); line0: the '\n' before the chunk.
+__host__ __device__ __forceinline__ void reads_roles(u32 nl, u32 line0, u32 role[4])
+{
+    u32 from = 0, q = line0 & 3;
+    role[0] = role[1] = role[2] = role[3] = 0;
+    while (nl) {
+        const u32 j = (u32)__builtin_ctz(nl);
+        role[q] |= text_bit_range(from, j + 1);
+        from = j + 1;
+        q = (q + 1) & 3;
+        nl &= nl - 1;
+    }
+    role[q] |= text_bit_range(from, 32);
+}
+// the k-th set bit of m, k from 1; m has at least k bits
+__host__ __device__ __forceinline__ u32 text_nth_bit(u32 m, u32 k)
+{
+    while (--k)
+        m &= m - 1;
+    return (u32)__builtin_ctz(m);
+}
+
+// DNAGPU_AMBIG_SPLIT: the kept bases that begin a piece.  A base begins one iff no kept base lies between it and the last
+// break at or before it; keep: the kept bases of the chunk, brk: its breaks (ambiguity letters of sequence lines and record
+// openers).  Positions are 1 + the offset inside the tile, 0 = none: at that of the chunk's byte 0, pk / pb those of the
+// last kept base / break before the chunk.  *undecided = the one bit that the tile cannot decide: a kept base with neither
+// a kept base nor a break before it in the tile (the tiles before decide: reads_finish_kernel).
+__host__ __device__ __forceinline__ u32 reads_piece_starts(u32 keep, u32 brk, u32 at, u32 pk, u32 pb, u32 *undecided)
+{
+    u32 cand = keep & (~(keep << 1) | brk), m = 0;   // the first base of every run of kept bases, and a base that is a break
+    *undecided = 0;
+    while (cand) {
+        const u32 j = (u32)__builtin_ctz(cand);
+        const u32 kb = keep & text_low_bits(j), bb = brk & text_low_bits(j + 1);
+        const u32 k = kb ? at + text_top_bit(kb) : pk, b = bb ? at + text_top_bit(bb) : pb;
+        if (!(k | b))
+            *undecided = 1u << j;
+        else if (k < b)
+            m |= 1u << j;
+        cand &= cand - 1;
+    }
+    return m;
+}
+
+// FASTQ: what the newline count decides.  lines: L '\n' in the text, one more line when the last byte is none.  The
+// newline that ends the last whole record is number fastq_cut_newline (from 1; 0: there is no whole record): one past it
+// DNAGPU_TEXT_MORE cuts, and there the truncated record begins.
+__host__ __device__ __forceinline__ u64 fastq_lines(u64 newlines, bool ends_in_newline) { return newlines + (ends_in_newline ? 0 : 1); }
+__host__ __device__ __forceinline__ u64 fastq_cut_newline(u64 newlines, bool ends_in_newline, bool more)
+{
+    return (more ? newlines : fastq_lines(newlines, ends_in_newline)) / 4 * 4;
+}
+
 }  // namespace dnagpu

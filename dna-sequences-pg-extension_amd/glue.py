@@ -192,6 +192,10 @@ def lib():
         L.copy_dna_feed.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_bool]
         L.copy_dna_next.restype = C.c_bool
         L.copy_dna_next.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
+        L.copy_reads_begin.restype = vp
+        L.copy_reads_begin.argtypes = [C.c_int, C.c_int, C.c_uint, C.c_uint64]
+        L.copy_reads_next.restype = C.c_bool
+        L.copy_reads_next.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.copy_dna_failed.restype = C.c_bool
         L.copy_dna_failed.argtypes = [vp]
         L.copy_dna_end.restype = None
@@ -766,6 +770,41 @@ def copy_dna(pieces, format=1):
         check(lib().copy_dna_feed(c, None, 0, True))
         drain()
         return rows, lines
+    finally:
+        lib().copy_dna_end(c)
+
+
+def copy_reads(pieces, format=3, ambiguous=0, fold_case=False, min_bases=0):
+    """COPY reads (record, start, sequence) FROM a FASTQ (3), FASTA (2) or one-per-line (1) file: pieces = the file's bytes in
+    order, in pieces of any size; ambiguous 0 / 1 / 2 = an ambiguity letter is an ERROR / drops its record / splits it ->
+    ([dna], [record], [offset]) in file order, record = the 0-based source record of the whole file.  An input ERROR raises
+    GlueError with the library's message and .record = the source record it belongs to (-1: none)"""
+    c = lib().copy_reads_begin(int(format), int(ambiguous), 2 if fold_case else 0, int(min_bases))
+    if not c:
+        raise _err()
+    try:
+        rows, records, offsets = [], [], []
+        p, rec, off = C.c_void_p(), C.c_int64(), C.c_int64()
+
+        def drain():
+            while lib().copy_reads_next(c, C.byref(p), C.byref(rec), C.byref(off)):
+                rows.append(dna(p=p.value))
+                records.append(rec.value)
+                offsets.append(off.value)
+
+        def check(ok):
+            if not ok:
+                e = _err()
+                lib().copy_reads_next(c, None, C.byref(rec), None)
+                e.record = rec.value
+                raise e
+        for piece in pieces:
+            b = bytes(piece)
+            check(lib().copy_dna_feed(c, b, len(b), False))
+            drain()
+        check(lib().copy_dna_feed(c, None, 0, True))
+        drain()
+        return rows, records, offsets
     finally:
         lib().copy_dna_end(c)
 

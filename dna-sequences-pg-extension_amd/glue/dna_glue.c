@@ -1998,6 +1998,14 @@ struct CopyDna {
     uint64_t cap_rows, n_rows, next;
     uint64_t first_line;                         /* rows of the whole file before rows[0] */
     int64_t bad_line;                            /* after an input ERROR: the 1-based row of the whole file it belongs to, else 0 */
+    /* copy_reads_begin: the load goes through dnagpu_reads_from_text, and every row knows where it came from */
+    bool reads;
+    int ambiguous;
+    unsigned flags;
+    uint64_t min_bases;
+    uint64_t *src_record, *src_offset;           /* per row of rows[]: the source record of the whole file, the offset in it */
+    uint64_t cap_src_record, cap_src_offset;
+    uint64_t first_record;                       /* source records of the whole file before the buffer's first byte */
 };
 
 CopyDna *copy_dna_begin(int format)
@@ -2016,6 +2024,92 @@ CopyDna *copy_dna_begin(int format)
     return c;
 }
 
+CopyDna *copy_reads_begin(int format, int ambiguous, unsigned flags, uint64_t min_bases)
+{
+    if (format != DNAGPU_TEXT_LINES && format != DNAGPU_TEXT_FASTA && format != DNAGPU_TEXT_FASTQ) {
+        ereport_error("copy_reads: the format must be 1 (one sequence per line), 2 (FASTA) or 3 (FASTQ)");
+        return NULL;
+    }
+    if (ambiguous < DNAGPU_AMBIG_ERROR || ambiguous > DNAGPU_AMBIG_SPLIT || (flags & ~DNAGPU_READS_FOLD_CASE)) {
+        ereport_error("copy_reads: the ambiguity policy must be 0, 1 or 2 and the flags 0 or DNAGPU_READS_FOLD_CASE");
+        return NULL;
+    }
+    CopyDna *c = copy_dna_begin(format == DNAGPU_TEXT_FASTQ ? DNAGPU_TEXT_LINES : format);
+    if (!c)
+        return NULL;
+    c->format = format;
+    c->reads = true;
+    c->ambiguous = ambiguous;
+    c->flags = flags;
+    c->min_bases = min_bases;
+    return c;
+}
+
+/* copy_load for copy_reads_begin: the same chunk through dnagpu_reads_from_text.  The source arrays are sized for reads of
+ * 32 bytes and more; a chunk of shorter ones is loaded a second time with the size its report names */
+static bool copy_load_reads(CopyDna *c, uint64_t n, bool more)
+{
+    const dnagpu_reads_options opt = {c->format, c->ambiguous, c->flags | (more ? DNAGPU_READS_MORE : 0u), 0u, c->min_bases};
+    dnagpu_dna *d = NULL;
+    dnagpu_reads_report rep;
+    uint64_t cap = n / 32 + 1024, *rec = NULL, *off = NULL;
+    for (;;) {
+        rec = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)cap);
+        off = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)cap);
+        if (!rec || !off) {
+            free(rec);
+            free(off);
+            ereport_error("out of memory");
+            return false;
+        }
+        const int rc = dnagpu_reads_from_text(g_ctx, c->buf, n, 0, &opt, &d, NULL, 0, rec, off, cap, &rep);
+        if (rc != DNAGPU_OK) {
+            free(rec);
+            free(off);
+            if (rep.bad_pos != UINT64_MAX) {                              /* an input error: the library's message verbatim */
+                ereport_error("%s", dnagpu_last_error());
+                c->bad_line = rep.bad_record == UINT64_MAX ? 0 : (int64_t)(c->first_record + rep.bad_record + 1);
+                return false;
+            }
+            return gpu_ok(rc);
+        }
+        if (rep.sequences <= cap)
+            break;
+        dnagpu_dna_free(g_ctx, d);
+        free(rec);
+        free(off);
+        cap = rep.sequences;
+    }
+    if (c->next == c->n_rows)                                             /* everything served: the arrays start over */
+        c->n_rows = c->next = 0;
+    bool ok = agg_grow((void **)&c->rows, &c->cap_rows, c->n_rows + rep.sequences) &&
+              agg_grow((void **)&c->src_record, &c->cap_src_record, c->n_rows + rep.sequences) &&
+              agg_grow((void **)&c->src_offset, &c->cap_src_offset, c->n_rows + rep.sequences) &&
+              (rep.sequences == 0 || table_rows(d, rep.sequences, c->rows + c->n_rows));
+    dnagpu_dna_free(g_ctx, d);
+    for (uint64_t i = 0; ok && i < rep.sequences; i++) {
+        c->src_record[c->n_rows + i] = c->first_record + rec[i];
+        c->src_offset[c->n_rows + i] = off[i];
+    }
+    free(rec);
+    free(off);
+    if (!ok)
+        return false;
+    c->n_rows += rep.sequences;
+    c->first_record += rep.records;
+    if (rep.consumed && c->len > rep.consumed)
+        memmove(c->buf, c->buf + rep.consumed, (size_t)(c->len - rep.consumed));
+    c->len -= rep.consumed;
+    if (more && rep.consumed == 0) {                                      /* a record longer than the chunk */
+        if (c->chunk >= COPY_MAX_CHUNK) {
+            ereport_error("copy_reads: a record is longer than 2^32 - 1 bytes");
+            return false;
+        }
+        c->chunk = c->chunk > COPY_MAX_CHUNK / 2 ? COPY_MAX_CHUNK : 2 * c->chunk;
+    }
+    return true;
+}
+
 /* the first n bytes of the buffer through dnagpu_table_from_text; the rows appended, the bytes accounted for dropped */
 static bool copy_load(CopyDna *c, uint64_t n, bool more)
 {
@@ -2023,6 +2117,8 @@ static bool copy_load(CopyDna *c, uint64_t n, bool more)
     dnagpu_text_report rep;
     if (!ctx())
         return false;
+    if (c->reads)
+        return copy_load_reads(c, n, more);
     const int rc = dnagpu_table_from_text(g_ctx, c->buf, n, 0, c->format, more ? DNAGPU_TEXT_MORE : 0u, &d, NULL, 0, &rep);
     if (rc != DNAGPU_OK) {
         if (rep.bad_pos != UINT64_MAX) {                                  /* an input error: the reference's message verbatim */
@@ -2109,6 +2205,23 @@ bool copy_dna_next(CopyDna *c, Dna **row, int64_t *line)
     return true;
 }
 
+bool copy_reads_next(CopyDna *c, Dna **row, int64_t *record, int64_t *offset)
+{
+    if (c->failed || !c->reads) {
+        if (record)
+            *record = c->bad_line - 1;
+        return false;
+    }
+    if (c->next >= c->n_rows)
+        return false;
+    const uint64_t i = c->next;
+    if (record)
+        *record = (int64_t)c->src_record[i];
+    if (offset)
+        *offset = (int64_t)c->src_offset[i];
+    return copy_dna_next(c, row, NULL);
+}
+
 bool copy_dna_failed(const CopyDna *c) { return c->failed; }
 
 void copy_dna_end(CopyDna *c)
@@ -2118,6 +2231,8 @@ void copy_dna_end(CopyDna *c)
     for (uint64_t i = 0; i < c->n_rows; i++)
         dna_free(c->rows[i]);
     free(c->rows);
+    free(c->src_record);
+    free(c->src_offset);
     free(c->buf);
     free(c);
 }

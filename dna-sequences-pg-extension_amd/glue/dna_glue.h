@@ -301,6 +301,18 @@ bool copy_dna_feed(CopyDna *c, const char *bytes, size_t n, bool last);
 bool copy_dna_next(CopyDna *c, Dna **row, int64_t *line);
 bool copy_dna_failed(const CopyDna *c);
 void copy_dna_end(CopyDna *c);
+/* ---- COPY reads (record, start, sequence) FROM 'x.fastq' (INTEGRATION.md 2.4n): the same feeding, through
+ * dnagpu_reads_from_text ----
+ * copy_reads_begin: format = 1, 2 or 3 (FASTQ); ambiguous = DNAGPU_AMBIG_ERROR / _DROP / _SPLIT; flags = 0 or
+ *   DNAGPU_READS_FOLD_CASE; min_bases: shorter sequences are left out.  The handle is fed with copy_dna_feed, asked with
+ *   copy_dna_failed and ended with copy_dna_end; the chunks go through the device with DNAGPU_READS_MORE as copy_dna's do.
+ * copy_reads_next = one loaded row as copy_dna_next, with record = the 0-based source record of the whole file it came from
+ *   (the numbers continue across chunks) and offset = the index of its first base in that record's sequence (0 unless the
+ *   policy is SPLIT); each may be NULL.  After an input ERROR it returns false with record = the 0-based source record the
+ *   error belongs to (-1: none).  The messages are the library's: copy_dna's, and for FASTQ "FASTQ record does not begin
+ *   with '@'", "FASTQ separator line does not begin with '+'", "truncated FASTQ record". */
+CopyDna *copy_reads_begin(int format, int ambiguous, unsigned flags, uint64_t min_bases);
+bool copy_reads_next(CopyDna *c, Dna **row, int64_t *record, int64_t *offset);
 /* bytes per chunk of copy_dna (default 2^26); tests use small values to force many chunks */
 void dna_glue_set_copy_chunk_bytes(uint64_t n);
 

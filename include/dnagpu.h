@@ -346,6 +346,82 @@ int dnagpu_table_from_text(dnagpu_ctx *ctx, const char *text, uint64_t n_bytes, 
                            uint64_t *out_record_pos, uint64_t record_cap,
                            dnagpu_text_report *report);
 int dnagpu_text_geometry(uint64_t *tile_bytes);
+/* ---- FASTQ and real FASTA as a resident table (COPY reads (record, start, sequence) FROM 'x.fastq') ----
+ * dnagpu_reads_from_text: dnagpu_table_from_text for the files that real data comes in: FASTQ records, IUPAC ambiguity
+ *   letters under a policy, lower-case (soft-masked) bases, a minimal length, and for every sequence of the result where in
+ *   the source it came from.  text, *out and the result are dnagpu_table_from_text's: an owned dnagpu_dna with a resident
+ *   sequence set, exactly what dnagpu_dna_take returns; sequences == 0 gives a valid dna of 0 bases with no set.
+ * 1. Byte classes in a sequence line.  Base: A T C G, and with DNAGPU_READS_FOLD_CASE also a t c g.  Ambiguity letter:
+ *   N R Y K M S W B D H V, and with FOLD_CASE their lower case.  Terminator: '\n', and a '\r' directly before it.  Invalid:
+ *   everything else -- U, X, '-', '*', digits, blanks, lower case without FOLD_CASE -- and DNAGPU_ERR_DNA_INVALID_CHAR under
+ *   every policy.
+ * 2. LINES and FASTA delimit records exactly as dnagpu_table_from_text does (header lines unvalidated, blank lines in FASTA
+ *   ignored, data before the first header DNAGPU_ERR_BAD_ARG).  With ambiguous == DNAGPU_AMBIG_ERROR, flags & ~MORE == 0 and
+ *   min_bases <= 1 the result is bit-identical to dnagpu_table_from_text's on the same bytes -- stream, starts, record_pos,
+ *   report -- and so is every error: code, offset, record, character and dnagpu_last_error().
+ * 3. FASTQ: strict four-line records.  Lines are numbered from 0 and end at '\n'; a last line without a terminator is a
+ *   line, text that ends in '\n' has no extra one.  Line i belongs to record i / 4 and has role i % 4.  Role 0 must begin
+ *   with '@', else DNAGPU_ERR_BAD_ARG at the line's first byte, "FASTQ record does not begin with '@'" (a blank line there
+ *   is this error); the rest of the line is ignored.  Role 1 is the sequence line, classified as in 1; an empty one is
+ *   DNAGPU_ERR_DNA_EMPTY at the line's first byte, as for LINES.  Role 2 must begin with '+', else DNAGPU_ERR_BAD_ARG at its
+ *   first byte, "FASTQ separator line does not begin with '+'"; the rest is ignored.  Role 3 is the quality line: it is
+ *   ignored whole, no byte of it is validated, and its length is NOT compared with the sequence's (that check would need the
+ *   last four newline positions across tiles; it is left out on purpose).  Multi-line FASTQ is not supported.  Without
+ *   MORE a line count that is no multiple of 4 is DNAGPU_ERR_BAD_ARG, "truncated FASTQ record", at the first byte of the
+ *   unfinished record.  With MORE consumed is one past the '\n' that ends the last complete record (0: there is none), and
+ *   nothing at or beyond it raises an error.  record_pos[r] is the offset of record r's '@'.
+ * 4. Policies, over a record's sequence text S (its sequence bytes joined, terminators removed).  DNAGPU_AMBIG_ERROR: an
+ *   ambiguity letter is DNAGPU_ERR_DNA_INVALID_CHAR with that letter.  DNAGPU_AMBIG_DROP: a record whose S holds an
+ *   ambiguity letter contributes nothing and counts in dropped; every other record is one sequence with src_offset 0.
+ *   DNAGPU_AMBIG_SPLIT: every maximal run of bases in S is one sequence, in order; src_offset is the index in S of the run's
+ *   first base (the coordinate in the original sequence, ambiguity letters counted); a non-empty S with no base contributes
+ *   nothing and is no error.  Under every policy an S with no byte at all is DNAGPU_ERR_DNA_EMPTY; a sequence shorter than
+ *   min_bases is left out and counts in short_out; src_record is the 0-based source record, the index into record_pos.
+ *   Deleting the ambiguity letters and joining the flanks is deliberately not offered: it invents k-mers.
+ * 5. Errors: every input error has a byte offset, and the lowest offset wins; at equal offsets a bad '@' or '+' comes before
+ *   empty, before invalid character, before truncated.  report gets bad_pos, bad_record and bad_char as dnagpu_text_report.
+ *   On every error *out is left as it was and nothing stays allocated; the output arrays may then hold anything.
+ * 6. out_record_pos: per SOURCE record, at most record_cap entries.  out_src_record / out_src_offset: per sequence of the
+ *   RESULT, at most seq_cap entries each.  All three are host memory, or device memory when text_on_device != 0.
+ * 7. Checks, in order, none needs a device: a NULL ctx, opt or out; a NULL text with n_bytes > 0; a NULL array with a
+ *   non-zero cap; only one of the two src arrays given with seq_cap > 0 -- all DNAGPU_ERR_BAD_ARG; then a format, ambiguous,
+ *   flags or reserved out of range, DNAGPU_ERR_BAD_ARG; then n_bytes > 2^32 - 1, DNAGPU_ERR_TOO_LARGE.  Then the input
+ *   errors, then DNAGPU_ERR_OOM.  The call waits for its work.  The success path reads back once; a second read-back (the
+ *   counts of what stays) happens only where DROP met an ambiguity letter or min_bases > 1. */
+#define DNAGPU_TEXT_FASTQ 3            /* strict four-line records: @name / sequence / +[name] / quality */
+
+#define DNAGPU_AMBIG_ERROR 0           /* an IUPAC ambiguity letter is an invalid character (dnagpu_table_from_text's rule) */
+#define DNAGPU_AMBIG_DROP  1           /* a record that holds one is left out of the result */
+#define DNAGPU_AMBIG_SPLIT 2           /* a record is cut at every run of them: each maximal run of bases is a sequence */
+
+#define DNAGPU_READS_MORE      1u      /* == DNAGPU_TEXT_MORE */
+#define DNAGPU_READS_FOLD_CASE 2u      /* a c g t are bases; lower-case ambiguity letters are ambiguity letters */
+
+typedef struct dnagpu_reads_options {
+    int      format;      /* DNAGPU_TEXT_LINES, _FASTA or _FASTQ */
+    int      ambiguous;   /* DNAGPU_AMBIG_* */
+    unsigned flags;       /* DNAGPU_READS_* */
+    unsigned reserved;    /* must be 0 */
+    uint64_t min_bases;   /* sequences of the result shorter than this are left out (0 and 1: none is) */
+} dnagpu_reads_options;
+
+typedef struct dnagpu_reads_report {
+    uint64_t records;     /* source records accounted for (finished records of text[0 .. consumed)) */
+    uint64_t sequences;   /* sequences in the result */
+    uint64_t bases;       /* bases in the result */
+    uint64_t consumed;    /* bytes of text the result accounts for (== n_bytes without MORE) */
+    uint64_t ambiguous;   /* ambiguity letters met in sequence lines */
+    uint64_t dropped;     /* DROP: records left out for an ambiguity letter */
+    uint64_t short_out;   /* sequences left out by min_bases */
+    uint64_t bad_pos, bad_record;   /* as dnagpu_text_report */
+    char     bad_char, reserved[7];
+} dnagpu_reads_report;
+
+int dnagpu_reads_from_text(dnagpu_ctx *ctx, const char *text, uint64_t n_bytes, int text_on_device,
+                           const dnagpu_reads_options *opt, dnagpu_dna **out,
+                           uint64_t *out_record_pos, uint64_t record_cap,      /* per SOURCE record: offset of its first byte */
+                           uint64_t *out_src_record, uint64_t *out_src_offset, uint64_t seq_cap,   /* per RESULT sequence */
+                           dnagpu_reads_report *report);
 /* Same over an arbitrary array of n keys of k bases already in device memory.  dev_keys is used as
  * scratch and its contents are unspecified afterwards. */
 int dnagpu_count_keys(dnagpu_ctx *ctx, uint64_t *dev_keys, uint64_t n, int k, dnagpu_hist **out);
