@@ -53,6 +53,7 @@ TEXT_LINES = 1                        # dnagpu_table_from_text: one sequence per
 TEXT_FASTA = 2                        # ... '>' header lines open records
 TEXT_MORE = 1                         # ... flags: a chunk of a longer file, the unfinished last record is held back
 TEXT_FASTQ = 3                        # dnagpu_reads_from_text only: strict four-line records
+TEXT_OUT_CRLF = 1                     # dnagpu_table_to_text: every terminator is "\r\n"
 AMBIG_ERROR, AMBIG_DROP, AMBIG_SPLIT = 0, 1, 2      # dnagpu_reads_from_text: what an IUPAC ambiguity letter does
 READS_MORE, READS_FOLD_CASE = 1, 2    # ... flags
 U64_MAX = 2 ** 64 - 1
@@ -133,6 +134,12 @@ class ReadsReport:
     record_pos: object = None         # uint64[min(records, cap)] when asked for (host), else None
     src_record: object = None         # uint64[min(sequences, cap)] each when asked for (host), else None
     src_offset: object = None
+
+
+class _TextOutOptionsC(C.Structure):
+    _fields_ = [("format", C.c_int), ("flags", C.c_uint), ("line_width", C.c_uint32), ("prefix_len", C.c_uint32),
+                ("name_prefix", C.c_char_p), ("name_base", C.c_uint64), ("numbers", C.c_void_p), ("numbers_on_device", C.c_int),
+                ("quality", C.c_char), ("reserved", C.c_char * 3)]
 
 
 class _PhaseTimes(C.Structure):
@@ -275,6 +282,15 @@ def lib():
     L.dnagpu_text_geometry.argtypes = [u64p]
     L.dnagpu_reads_from_text.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(_ReadsOptionsC), C.POINTER(vp), vp, C.c_uint64,
                                          vp, vp, C.c_uint64, C.POINTER(_ReadsReportC)]
+    L.dnagpu_table_to_text.argtypes = [vp, vp, C.POINTER(_TextOutOptionsC), C.POINTER(vp)]
+    for f in ("bytes", "sequences", "empty"):
+        getattr(L, f"dnagpu_text_image_{f}").argtypes = [vp]
+        getattr(L, f"dnagpu_text_image_{f}").restype = C.c_uint64
+    L.dnagpu_text_image_read.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_int]
+    L.dnagpu_text_image_record_pos.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_int]
+    L.dnagpu_text_image_free.argtypes = [vp, vp]
+    L.dnagpu_text_image_free.restype = None
+    L.dnagpu_text_out_geometry.argtypes = [u64p]
     L.dnagpu_dna_equals.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]
     L.dnagpu_table_classes.argtypes = [vp, vp, C.POINTER(vp)]
     for f in ("sequences", "distinct"):
@@ -394,6 +410,13 @@ def text_geometry():
     """the bytes of text one workgroup of dnagpu_table_from_text sweeps (needs no device)"""
     t = C.c_uint64()
     _chk(lib().dnagpu_text_geometry(C.byref(t)))
+    return t.value
+
+
+def text_out_geometry():
+    """the bytes of the image one workgroup of dnagpu_text_image_read forms (needs no device)"""
+    t = C.c_uint64()
+    _chk(lib().dnagpu_text_out_geometry(C.byref(t)))
     return t.value
 
 
@@ -744,6 +767,59 @@ class SeqClasses:
             if self.ctx._base_debug & DEBUG_GUARD_POOL:
                 self.ctx.synchronize()          # raises if a kernel wrote past the end of a work buffer
             lib().dnagpu_seq_classes_free(self.ctx.h, self.h)
+            self.h = None
+            self.table = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
+class TextImage:
+    """dnagpu_text_image: the text image of a resident table (Context.table_to_text), read window by window.  It borrows
+    the table: keep the Dna alive and its sequence set unchanged until free()"""
+
+    def __init__(self, ctx, handle, table):
+        self.ctx, self.h, self.table = ctx, handle, table
+
+    @property
+    def bytes(self):
+        return int(lib().dnagpu_text_image_bytes(self.h))
+
+    @property
+    def sequences(self):
+        return int(lib().dnagpu_text_image_sequences(self.h))
+
+    @property
+    def empty(self):
+        """sequences of 0 bases in the image (the loaders refuse such records)"""
+        return int(lib().dnagpu_text_image_empty(self.h))
+
+    def read(self, first=0, count=None):
+        """bytes [first, first + count) of the image (count=None: all from first on) -> bytes; at most 2^32 - 1 per call"""
+        if count is None:
+            count = self.bytes - first
+        buf = C.create_string_buffer(max(count, 1))
+        _chk(lib().dnagpu_text_image_read(self.ctx.h, self.h, first, count, buf, 0))
+        return buf.raw[:count]
+
+    def read_device(self, first, count, dev_ptr):
+        """the same into `count` bytes of device memory at any byte alignment"""
+        _chk(lib().dnagpu_text_image_read(self.ctx.h, self.h, first, count, dev_ptr, 1))
+
+    def record_pos(self, first=0, count=None):
+        """entries [first, first + count) of the sequences + 1 record offsets (the last: the image's size) -> uint64 array"""
+        if count is None:
+            count = (self.sequences + 1 if self.sequences else 0) - first
+        out = np.empty(max(count, 1), dtype=np.uint64)
+        _chk(lib().dnagpu_text_image_record_pos(self.ctx.h, self.h, first, count, out.ctypes.data, 0))
+        return out[:count]
+
+    def free(self):
+        if self.h:
+            lib().dnagpu_text_image_free(self.ctx.h, self.h)
             self.h = None
             self.table = None
 
@@ -1233,6 +1309,27 @@ class Context:
         dev_src_record / dev_src_offset: seq_cap uint64 of device memory each"""
         return self._reads_from_text(ptr, n_bytes, 1, format, ambiguous, fold_case, min_bases, more, dev_record_pos, record_cap,
                                      dev_src_record, dev_src_offset, seq_cap)
+
+    def table_to_text(self, dna, format, *, crlf=False, line_width=0, prefix=b"", name_base=0, numbers=None, quality=b"I"):
+        """the text image of the resident table dna -> TextImage (dnagpu_table_to_text): LINES, FASTA in lines of line_width
+        bases (0: one line) or FASTQ with `quality` in every quality line; names are prefix + a number, name_base + s or
+        numbers[s].  numbers: a uint64 array of one entry per sequence, or the address of one in device memory"""
+        prefix = bytes(prefix)
+        opt = _TextOutOptionsC(format=format, flags=TEXT_OUT_CRLF if crlf else 0, line_width=line_width, prefix_len=len(prefix),
+                               name_prefix=prefix if prefix else None, name_base=name_base % (1 << 64),
+                               quality=bytes(quality)[:1] if quality else b"\0")
+        keep = None
+        if numbers is not None:
+            if isinstance(numbers, int):
+                opt.numbers, opt.numbers_on_device = numbers, 1
+            else:
+                keep = np.ascontiguousarray(numbers, dtype=np.uint64)
+                if keep.size != dna.n_sequences:
+                    raise ValueError("numbers must hold one entry per sequence")
+                opt.numbers = keep.ctypes.data if keep.size else None
+        h = C.c_void_p()
+        _chk(lib().dnagpu_table_to_text(self.h, dna.h, C.byref(opt), C.byref(h)))
+        return TextImage(self, h, dna)
 
     def unpack(self, dna, first=0, count=None):
         if count is None:

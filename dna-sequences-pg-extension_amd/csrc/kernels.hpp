@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "export_math.hpp"
 #include "kmer_device.hpp"
 
 namespace dnagpu {
@@ -382,6 +383,27 @@ hipError_t launch_reads_select(const u64 *starts, const u32 *rec_amb, u64 n, u64
 // rank: the scanned flags; len32: zero before the launch
 hipError_t launch_reads_move(const u64 *starts, const u64 *src_record, const u64 *src_offset, const u32 *flags, const u32 *rank, u64 n,
                              u64 *seg_first, u32 *len32, u64 *src_record_out, u64 *src_offset_out, hipStream_t s);
+
+// ---- a resident table as text (export_kernels.hip; the record arithmetic is export_math.hpp's).
+// the plan: ex32[s] = the bytes of record s that are no bases of a sequence line (clamped to 2^32 - 1), res2[0] = their sum
+// in 64 bits, res2[1] = the sequences of 0 bases (res2 is zeroed here).  numbers may be null: the number of s is name_base + s
+hipError_t launch_export_plan(const u64 *starts, u64 n, const u64 *numbers, u64 name_base, const ExportFmt &f, u32 *ex32,
+                              unsigned long long *res2, hipStream_t s);
+// pos[0 .. n] = where every record begins, from the exclusive scan of ex32 and its total; pos[n] = the image's bytes
+hipError_t launch_export_pos(const u64 *starts, const u32 *scan, u64 n, u64 total, u64 *pos, hipStream_t s);
+// the sweep: dst[0 .. count) = bytes [first_byte, first_byte + count) of the image; dst at any byte alignment; no byte of
+// dst outside them is written or read; no word of words at or beyond n_words is read
+struct ExportRead {
+    const u64 *words;
+    u64 n_words, n_bases;
+    const u64 *starts, *pos, *numbers;       // n + 1, n + 1, n (or null) entries
+    const unsigned char *prefix;             // fmt.prefix_len bytes of device memory
+    u64 n, name_base;
+    ExportFmt fmt;
+    u64 first_byte, count;
+    unsigned char *dst;
+};
+hipError_t launch_export_read(const ExportRead &a, hipStream_t s);
 
 // ---- equal sequences (seqeq_kernels.hip; classes, items, realigned word and fingerprint are
 // seqeq_math.hpp's).  A table, or a window of one: starts = seq_starts + seq_first, n + 1 entries.

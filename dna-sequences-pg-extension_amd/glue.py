@@ -202,6 +202,16 @@ def lib():
         L.copy_dna_end.argtypes = [vp]
         L.dna_glue_set_copy_chunk_bytes.restype = None
         L.dna_glue_set_copy_chunk_bytes.argtypes = [C.c_uint64]
+        L.copy_dna_to_begin.restype = vp
+        L.copy_dna_to_begin.argtypes = [C.c_int, C.c_uint32, C.c_bool]
+        for f in (L.copy_dna_to_add, L.copy_dna_to_finish, L.copy_dna_to_next, L.copy_dna_to_failed):
+            f.restype = C.c_bool
+        L.copy_dna_to_add.argtypes = [vp, vp]
+        L.copy_dna_to_finish.argtypes = [vp]
+        L.copy_dna_to_next.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+        L.copy_dna_to_failed.argtypes = [vp]
+        L.copy_dna_to_end.restype = None
+        L.copy_dna_to_end.argtypes = [vp]
         L.kmer_index_create.restype = vp
         L.kmer_index_create.argtypes = [C.POINTER(_Kmer), C.c_uint64]
         L.kmer_index_rows.restype = C.c_uint64
@@ -772,6 +782,31 @@ def copy_dna(pieces, format=1):
         return rows, lines
     finally:
         lib().copy_dna_end(c)
+
+
+def copy_dna_to(rows, fmt, line_width=0, crlf=False):
+    """COPY ... TO a text file: the rows (dna) as one sequence per line (1), FASTA in lines of line_width bases (2) or FASTQ
+    (3) -> the file's bytes.  FASTA and FASTQ name row r of the COPY r"""
+    c = lib().copy_dna_to_begin(int(fmt), int(line_width), bool(crlf))
+    if not c:
+        raise _err()
+    try:
+        out = []
+        p, n = C.c_void_p(), C.c_size_t()
+
+        def drain():
+            while lib().copy_dna_to_next(c, C.byref(p), C.byref(n)):
+                out.append(C.string_at(p.value, n.value))
+        for row in rows:
+            if not lib().copy_dna_to_add(c, _as_dna(row).p):
+                raise _err()
+            drain()
+        if not lib().copy_dna_to_finish(c):
+            raise _err()
+        drain()
+        return b"".join(out)
+    finally:
+        lib().copy_dna_to_end(c)
 
 
 def copy_reads(pieces, format=3, ambiguous=0, fold_case=False, min_bases=0):

@@ -2237,6 +2237,147 @@ void copy_dna_end(CopyDna *c)
     free(c);
 }
 
+/* ------------------------------------------------------------------ COPY ... TO a text file: copy_dna_to */
+
+struct CopyDnaTo {
+    int format;
+    uint32_t line_width;
+    bool crlf, failed, finished;
+    RowBatch b;                                  /* the open batch */
+    uint64_t limit_bases, chunk;                 /* a batch is flushed at limit_bases; a chunk of text has at most `chunk` bytes */
+    uint64_t rows_before;                        /* rows of the flushed batches: the first name of the next one */
+    char **text;                                 /* the chunks of text formed and not yet served (NULL once served and freed) */
+    uint64_t *text_len;
+    uint64_t cap_text, cap_text_len, n_text, next;
+};
+
+CopyDnaTo *copy_dna_to_begin(int format, uint32_t line_width, bool crlf)
+{
+    if (format != DNAGPU_TEXT_LINES && format != DNAGPU_TEXT_FASTA && format != DNAGPU_TEXT_FASTQ) {
+        ereport_error("copy_dna_to: the format must be 1 (one sequence per line), 2 (FASTA) or 3 (FASTQ)");
+        return NULL;
+    }
+    if (line_width && format != DNAGPU_TEXT_FASTA) {
+        ereport_error("copy_dna_to: only FASTA (format 2) takes a line width");
+        return NULL;
+    }
+    CopyDnaTo *c = (CopyDnaTo *)calloc(1, sizeof *c);
+    if (!c) {
+        ereport_error("out of memory");
+        return NULL;
+    }
+    c->format = format;
+    c->line_width = line_width;
+    c->crlf = crlf;
+    c->chunk = g_copy_chunk_bytes < COPY_MAX_CHUNK ? g_copy_chunk_bytes : COPY_MAX_CHUNK;
+    c->limit_bases = c->chunk < ((uint64_t)1 << 30) ? 4 * c->chunk : COPY_MAX_CHUNK;      /* (packed: four bases per byte) */
+    return c;
+}
+
+/* the image of the batch's table, chunk after chunk, behind the chunks that wait */
+static bool copy_to_read(CopyDnaTo *c, const dnagpu_text_image *img)
+{
+    const uint64_t bytes = dnagpu_text_image_bytes(img);
+    for (uint64_t at = 0; at < bytes; at += c->chunk) {
+        const uint64_t n = bytes - at < c->chunk ? bytes - at : c->chunk;
+        if (!agg_grow((void **)&c->text, &c->cap_text, c->n_text + 1) ||
+            !agg_grow((void **)&c->text_len, &c->cap_text_len, c->n_text + 1))
+            return false;
+        char *t = (char *)malloc((size_t)n);
+        if (!t) {
+            ereport_error("out of memory");
+            return false;
+        }
+        c->text[c->n_text] = t;
+        c->text_len[c->n_text++] = n;
+        if (!gpu_ok(dnagpu_text_image_read(g_ctx, img, at, n, t, 0)))
+            return false;
+    }
+    return true;
+}
+
+/* the batch so far: made resident, written out, emptied */
+static bool copy_to_flush(void *self)
+{
+    CopyDnaTo *c = (CopyDnaTo *)self;
+    bool ok = true;
+    if (c->b.n_seqs > 0) {
+        const dnagpu_text_out_options opt = {c->format, c->crlf ? DNAGPU_TEXT_OUT_CRLF : 0u, c->line_width, 0, NULL, c->rows_before,
+                                             NULL, 0, 0, {0, 0, 0}};
+        dnagpu_dna *d = NULL;
+        dnagpu_text_image *img = NULL;
+        ok = batch_upload(&c->b, &d) && gpu_ok(dnagpu_table_to_text(g_ctx, d, &opt, &img)) && copy_to_read(c, img);
+        if (img)
+            dnagpu_text_image_free(g_ctx, img);
+        if (d)
+            dnagpu_dna_free(g_ctx, d);
+        c->rows_before += c->b.n_seqs;
+    }
+    rb_clear(&c->b);
+    return ok;
+}
+
+bool copy_dna_to_add(CopyDnaTo *c, const Dna *row)
+{
+    if (c->finished || c->failed) {
+        ereport_error("copy_dna_to: a row added after the last one or after the COPY failed");
+        return false;
+    }
+    if (!row) {
+        ereport_error("copy_dna_to: the row is missing");
+        return false;
+    }
+    if (rb_spills(&c->b, row->length, c->limit_bases) && !copy_to_flush(c))
+        return !(c->failed = true);
+    if (!rb_append(&c->b, row->bit_sequence, row->length)) {
+        ereport_error("out of memory");
+        return !(c->failed = true);
+    }
+    if (rb_full(&c->b, c->limit_bases) && !copy_to_flush(c))
+        return !(c->failed = true);
+    return true;
+}
+
+bool copy_dna_to_finish(CopyDnaTo *c)
+{
+    if (c->failed)
+        return false;
+    if (!c->finished && !copy_to_flush(c))
+        return !(c->failed = true);
+    c->finished = true;
+    return true;
+}
+
+bool copy_dna_to_next(CopyDnaTo *c, const char **bytes, size_t *n)
+{
+    if (c->failed || c->next >= c->n_text)
+        return false;
+    if (c->next > 0) {                                                        /* the chunk served before this one */
+        free(c->text[c->next - 1]);
+        c->text[c->next - 1] = NULL;
+    }
+    const uint64_t i = c->next++;
+    if (bytes)
+        *bytes = c->text[i];
+    if (n)
+        *n = (size_t)c->text_len[i];
+    return true;
+}
+
+bool copy_dna_to_failed(const CopyDnaTo *c) { return c->failed; }
+
+void copy_dna_to_end(CopyDnaTo *c)
+{
+    if (!c)
+        return;
+    for (uint64_t i = 0; i < c->n_text; i++)
+        free(c->text[i]);
+    free(c->text);
+    free(c->text_len);
+    rb_free(&c->b);
+    free(c);
+}
+
 /* ------------------------------------------------------------------ the index over a stored kmer column */
 
 struct KmerIndex {

@@ -315,6 +315,23 @@ CopyDna *copy_reads_begin(int format, int ambiguous, unsigned flags, uint64_t mi
 bool copy_reads_next(CopyDna *c, Dna **row, int64_t *record, int64_t *offset);
 /* bytes per chunk of copy_dna (default 2^26); tests use small values to force many chunks */
 void dna_glue_set_copy_chunk_bytes(uint64_t n);
+/* ---- COPY dna_sequences (sequence) TO a text, FASTA or FASTQ file: the mirror of copy_dna, through dnagpu_table_to_text
+ * (the reference calls dna_out -> decode_dna once per row, dna.c:135-152, 230-239) ----
+ * copy_dna_to_begin: format = 1 (one sequence per line), 2 (FASTA, lines of line_width bases, 0 = one line) or 3 (FASTQ, every
+ *   quality byte 'I'); crlf: every terminator is "\r\n".  Another format, or a line width with a format other than 2, is an
+ *   ERROR (NULL) before any device is touched.  FASTA and FASTQ name row r of the whole COPY r, in decimal.
+ * add = the next row.  The rows are collected; at dna_glue_set_copy_chunk_bytes of packed input they are made a resident table
+ *   and written out on the device, and the names count on across such flushes.  finish = no more rows.
+ * next = the next chunk of the file, at most dna_glue_set_copy_chunk_bytes of text: *bytes (not NUL-terminated, valid until the
+ *   next call of next or end) and *n.  Chunks can be fetched between adds or after finish.  false = none is waiting, or an
+ *   ERROR: copy_dna_to_failed. */
+typedef struct CopyDnaTo CopyDnaTo;
+CopyDnaTo *copy_dna_to_begin(int format, uint32_t line_width, bool crlf);
+bool copy_dna_to_add(CopyDnaTo *c, const Dna *row);
+bool copy_dna_to_finish(CopyDnaTo *c);
+bool copy_dna_to_next(CopyDnaTo *c, const char **bytes, size_t *n);
+bool copy_dna_to_failed(const CopyDnaTo *c);
+void copy_dna_to_end(CopyDnaTo *c);
 
 /* ---- CREATE INDEX ... ON kmer_data_t USING spgist (kmer_sequence spgist_kmer_ops) and the index scans of `=`, `^@` and `@>`
  * over the stored column (dna--1.0.sql:304-314; test.sql:156-270) ----

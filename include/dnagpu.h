@@ -422,6 +422,72 @@ int dnagpu_reads_from_text(dnagpu_ctx *ctx, const char *text, uint64_t n_bytes, 
                            uint64_t *out_record_pos, uint64_t record_cap,      /* per SOURCE record: offset of its first byte */
                            uint64_t *out_src_record, uint64_t *out_src_offset, uint64_t seq_cap,   /* per RESULT sequence */
                            dnagpu_reads_report *report);
+/* ---- a resident table as text, FASTA or FASTQ (COPY dna_sequences (sequence) TO '...'; dna_out -> decode_dna, dna.c:135-152,
+ * 230-239, once per row) ----
+ * The text image of a table is the file that the loaders above would read back into the same table.  dnagpu_table_to_text
+ *   plans it -- it is never materialised --, dnagpu_text_image_read forms any byte window of it on the device, and
+ *   dnagpu_text_image_free releases the plan (dnagpu_ranking's shape).
+ * The image is record after record, in table order.  T is the terminator ("\n", or "\r\n" with DNAGPU_TEXT_OUT_CRLF), len
+ *   the sequence's bases, name = name_prefix followed by the record's number in decimal without padding (1 .. 20 digits); the
+ *   number of sequence s is numbers[s], or name_base + s (mod 2^64) when numbers is NULL.  Codes 0 .. 3 are A T C G.
+ *   LINES: the bases, T (prefix, base and numbers are ignored).
+ *   FASTA: '>' name T, then the bases in lines of line_width bases, each followed by T; the last line may be shorter, there is
+ *     never an empty line, and line_width == 0 or >= len gives one line.
+ *   FASTQ: '@' name T, the bases, T, '+' T, the quality byte len times, T.
+ * A sequence of 0 bases (dnagpu_dna_take can return such tables) is written as what it is -- LINES a bare T, FASTA a header
+ *   with no sequence line, FASTQ four lines of which two are empty -- and counted in dnagpu_text_image_empty: the loaders
+ *   refuse such records, the caller is told, nothing is invented.
+ * Round trip: for a table without empty sequences the whole image, given to dnagpu_table_from_text (LINES, FASTA) or
+ *   dnagpu_reads_from_text (FASTQ), yields bit-identical words and starts, and the loader's record_pos equals
+ *   dnagpu_text_image_record_pos.
+ * Lifetime: the image holds copies of the options, the prefix and the numbers, and one offset per sequence in pool memory;
+ *   it BORROWS the table, whose stream and sequence set are read by every dnagpu_text_image_read -- the caller keeps the
+ *   table alive and its set unchanged until dnagpu_text_image_free (dnagpu_table_classes' rule).  The table is only read: no
+ *   word at or beyond its n_words, and no byte of the image depends on bits behind the last base (dnagpu_dna_wrap's rule).
+ *   A table of 0 sequences gives an image of 0 bytes that holds no device memory.
+ * Checks of dnagpu_table_to_text, in order (the first three need no device): a NULL ctx, table, opt or out is
+ *   DNAGPU_ERR_BAD_ARG; a format outside 1 .. 3, flags other than 0 or 1, non-zero reserved bytes, prefix_len > 64, a NULL
+ *   prefix with prefix_len > 0, a '\n' or '\r' in the prefix, a quality byte outside 33 .. 126 (0 means 'I'), or line_width
+ *   != 0 with LINES or FASTQ, is DNAGPU_ERR_BAD_ARG; a non-empty stream without a sequence set is DNAGPU_ERR_BAD_ARG
+ *   (dnagpu_count_kmers_table's rule); more than 2^32 - 1 bytes of the image that are no bases of a sequence line (headers,
+ *   terminators, '+' and quality lines; summed in 64 bits on the device before anything is scanned) is DNAGPU_ERR_TOO_LARGE
+ *   -- callers split such tables with dnagpu_dna_take; an allocation failure is DNAGPU_ERR_OOM with nothing leaked.  On every
+ *   error *out is left as it was.  The call waits for its work and reads back once.
+ * dnagpu_text_image_read: bytes [first_byte, first_byte + count) of the image to out_text -- host memory, or device memory
+ *   at any byte alignment when out_on_device != 0.  Exactly count bytes are written, no NUL, and no byte of the destination
+ *   outside them is written or read.  dnagpu_ranking_read's window rule: first_byte > bytes or count > bytes - first_byte is
+ *   DNAGPU_ERR_BAD_ARG; count == 0 is DNAGPU_OK; count > 2^32 - 1 is DNAGPU_ERR_TOO_LARGE (callers page).  Windows tile: the
+ *   concatenation of any partition of [0, bytes) is the image.  Offsets are 64-bit throughout.  Waits for its work.
+ * dnagpu_text_image_record_pos: entry s = the offset of record s's first byte; sequences + 1 entries, the last = bytes (an
+ *   image of 0 sequences has 0 entries); dnagpu_dna_sequence_starts' window rule.
+ * dnagpu_text_out_geometry: *tile_bytes = the bytes one workgroup forms (the edge shapes of the tests); needs no device. */
+typedef struct dnagpu_text_image dnagpu_text_image;
+
+#define DNAGPU_TEXT_OUT_CRLF 1u            /* every terminator is "\r\n" instead of "\n" */
+
+typedef struct dnagpu_text_out_options {
+    int         format;        /* DNAGPU_TEXT_LINES, DNAGPU_TEXT_FASTA or DNAGPU_TEXT_FASTQ (the loaders' constants) */
+    unsigned    flags;         /* DNAGPU_TEXT_OUT_* */
+    uint32_t    line_width;    /* FASTA: bases per sequence line; 0 = the whole sequence on one line.  Must be 0 for LINES / FASTQ */
+    uint32_t    prefix_len;    /* bytes of name_prefix, <= 64 */
+    const char *name_prefix;   /* host memory; copied; no '\n' or '\r' in it; may be NULL when prefix_len == 0 */
+    uint64_t    name_base;     /* the number in sequence s's header is name_base + s (mod 2^64) ... */
+    const uint64_t *numbers;   /* ... or numbers[s] when this is not NULL: n_seqs entries, copied by the call */
+    int         numbers_on_device;
+    char        quality;       /* FASTQ: the byte that fills every quality line, 33..126; 0 means 'I' */
+    char        reserved[3];   /* must be 0 */
+} dnagpu_text_out_options;
+
+int      dnagpu_table_to_text(dnagpu_ctx *ctx, const dnagpu_dna *table, const dnagpu_text_out_options *opt, dnagpu_text_image **out);
+uint64_t dnagpu_text_image_bytes(const dnagpu_text_image *img);       /* size of the whole image; 0 for NULL */
+uint64_t dnagpu_text_image_sequences(const dnagpu_text_image *img);
+uint64_t dnagpu_text_image_empty(const dnagpu_text_image *img);       /* sequences of 0 bases in it */
+int      dnagpu_text_image_read(dnagpu_ctx *ctx, const dnagpu_text_image *img, uint64_t first_byte, uint64_t count,
+                                char *out_text, int out_on_device);
+int      dnagpu_text_image_record_pos(dnagpu_ctx *ctx, const dnagpu_text_image *img, uint64_t first_seq, uint64_t count,
+                                      uint64_t *out_pos, int out_on_device);
+void     dnagpu_text_image_free(dnagpu_ctx *ctx, dnagpu_text_image *img);
+int      dnagpu_text_out_geometry(uint64_t *tile_bytes);              /* bytes one workgroup forms; needs no device */
 /* Same over an arbitrary array of n keys of k bases already in device memory.  dev_keys is used as
  * scratch and its contents are unspecified afterwards. */
 int dnagpu_count_keys(dnagpu_ctx *ctx, uint64_t *dev_keys, uint64_t n, int k, dnagpu_hist **out);
