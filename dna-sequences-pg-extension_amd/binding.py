@@ -136,6 +136,55 @@ class ReadsReport:
     src_offset: object = None
 
 
+class _QualsReportC(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("bad_pos", C.c_uint64), ("bad_record", C.c_uint64), ("bad_char", C.c_char),
+                ("reserved", C.c_char * 7)]
+
+
+@dataclasses.dataclass
+class QualsReport:
+    """dnagpu_quals_report.  bad_pos / bad_record are None where the C struct holds ~0, bad_char is b"" where it holds 0"""
+    records: int = 0
+    bad_pos: object = None
+    bad_record: object = None
+    bad_char: bytes = b""
+
+
+class _QualsTrimOptionsC(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("cut_front", "cut_tail", "min_mean_q", "low_q", "low_num", "low_den")] + \
+               [("min_bases", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+_TRIM_REPORT_FIELDS = ("sequences", "passed", "bases_in", "bases_kept", "cut_front", "cut_tail", "failed_short", "failed_mean",
+                       "failed_low")
+
+
+class _QualsTrimReportC(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in _TRIM_REPORT_FIELDS]
+
+
+@dataclasses.dataclass
+class TrimResult:
+    """what Context.quals_trim returns: the dnagpu_quals_trim_report's counters; first / length / qsum / low: uint64 per
+    sequence; seg_seq / seg_first / seg_len: the passing sequences in table order, at most cap of them"""
+    sequences: int = 0
+    passed: int = 0
+    bases_in: int = 0
+    bases_kept: int = 0
+    cut_front: int = 0
+    cut_tail: int = 0
+    failed_short: int = 0
+    failed_mean: int = 0
+    failed_low: int = 0
+    first: object = None
+    length: object = None
+    qsum: object = None
+    low: object = None
+    seg_seq: object = None
+    seg_first: object = None
+    seg_len: object = None
+
+
 class _TextOutOptionsC(C.Structure):
     _fields_ = [("format", C.c_int), ("flags", C.c_uint), ("line_width", C.c_uint32), ("prefix_len", C.c_uint32),
                 ("name_prefix", C.c_char_p), ("name_base", C.c_uint64), ("numbers", C.c_void_p), ("numbers_on_device", C.c_int),
@@ -291,6 +340,20 @@ def lib():
     L.dnagpu_text_image_free.argtypes = [vp, vp]
     L.dnagpu_text_image_free.restype = None
     L.dnagpu_text_out_geometry.argtypes = [u64p]
+    L.dnagpu_quals_upload.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(_QualsReportC)]
+    L.dnagpu_quals_bases.argtypes = [vp]
+    L.dnagpu_quals_bases.restype = C.c_uint64
+    L.dnagpu_quals_read.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_int]
+    L.dnagpu_quals_free.argtypes = [vp, vp]
+    L.dnagpu_quals_free.restype = None
+    L.dnagpu_quals_from_fastq.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, vp, vp, C.POINTER(vp), C.POINTER(_QualsReportC)]
+    L.dnagpu_quals_gather.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
+    L.dnagpu_quals_take.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
+    L.dnagpu_text_image_read_quals.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, vp, C.c_int]
+    L.dnagpu_quals_copy_geometry.argtypes = [u64p, u64p, u64p]
+    L.dnagpu_quals_trim.argtypes = [vp, vp, vp, C.POINTER(_QualsTrimOptionsC), vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_int,
+                                    C.POINTER(_QualsTrimReportC)]
+    L.dnagpu_quals_geometry.argtypes = [u64p, u64p, u64p]
     L.dnagpu_dna_equals.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]
     L.dnagpu_table_classes.argtypes = [vp, vp, C.POINTER(vp)]
     for f in ("sequences", "distinct"):
@@ -418,6 +481,21 @@ def text_out_geometry():
     t = C.c_uint64()
     _chk(lib().dnagpu_text_out_geometry(C.byref(t)))
     return t.value
+
+
+def quals_copy_geometry():
+    """(chunk_bytes, tile_bytes, lds_segments): the bytes one lane and one workgroup of the quality column's copy form, and
+    the most segments of a tile it stages in LDS (needs no device)"""
+    c, t, s = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _chk(lib().dnagpu_quals_copy_geometry(C.byref(c), C.byref(t), C.byref(s)))
+    return c.value, t.value, s.value
+
+
+def quals_geometry():
+    """(group_bases, wave_bases, tile_bases): the length limits of dnagpu_quals_trim's paths (needs no device)"""
+    g, w, t = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _chk(lib().dnagpu_quals_geometry(C.byref(g), C.byref(w), C.byref(t)))
+    return g.value, w.value, t.value
 
 
 def profile_geometry():
@@ -809,6 +887,18 @@ class TextImage:
         """the same into `count` bytes of device memory at any byte alignment"""
         _chk(lib().dnagpu_text_image_read(self.ctx.h, self.h, first, count, dev_ptr, 1))
 
+    def read_quals(self, quals, first=0, count=None):
+        """read() of a FASTQ image with every quality line taken from the column quals (dnagpu_text_image_read_quals)"""
+        if count is None:
+            count = self.bytes - first
+        buf = C.create_string_buffer(max(count, 1))
+        _chk(lib().dnagpu_text_image_read_quals(self.ctx.h, self.h, quals.h, first, count, buf, 0))
+        return buf.raw[:count]
+
+    def read_quals_device(self, quals, first, count, dev_ptr):
+        """the same into `count` bytes of device memory at any byte alignment"""
+        _chk(lib().dnagpu_text_image_read_quals(self.ctx.h, self.h, quals.h, first, count, dev_ptr, 1))
+
     def record_pos(self, first=0, count=None):
         """entries [first, first + count) of the sequences + 1 record offsets (the last: the image's size) -> uint64 array"""
         if count is None:
@@ -822,6 +912,40 @@ class TextImage:
             lib().dnagpu_text_image_free(self.ctx.h, self.h)
             self.h = None
             self.table = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
+class Quals:
+    """dnagpu_quals: the quality column of a resident table, one Phred+33 byte per base of its stream.  It holds no
+    boundaries: the calls that need them take the table too"""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+
+    @property
+    def n_bases(self):
+        return int(lib().dnagpu_quals_bases(self.h))
+
+    def read(self, first=0, count=None):
+        """bytes [first, first + count) of the column (count=None: all from first on) -> bytes"""
+        if count is None:
+            count = self.n_bases - first
+        buf = C.create_string_buffer(max(count, 1))
+        _chk(lib().dnagpu_quals_read(self.ctx.h, self.h, first, count, buf, 0))
+        return buf.raw[:count]
+
+    def read_device(self, first, count, dev_ptr):
+        _chk(lib().dnagpu_quals_read(self.ctx.h, self.h, first, count, dev_ptr, 1))
+
+    def free(self):
+        if self.h:
+            lib().dnagpu_quals_free(self.ctx.h, self.h)
+            self.h = None
 
     def __enter__(self):
         return self
@@ -1330,6 +1454,114 @@ class Context:
         h = C.c_void_p()
         _chk(lib().dnagpu_table_to_text(self.h, dna.h, C.byref(opt), C.byref(h)))
         return TextImage(self, h, dna)
+
+    @staticmethod
+    def _quals_result(rc, h, rep):
+        none = lambda v: None if v == U64_MAX else int(v)
+        report = QualsReport(int(rep.records), none(rep.bad_pos), none(rep.bad_record), rep.bad_char if rep.bad_char != b"\0" else b"")
+        if rc != OK:
+            e = DnaGpuError(rc)
+            e.report = report
+            raise e
+        return report
+
+    def quals_upload(self, data):
+        """a quality column from Phred+33 bytes -> Quals; a byte outside 33 .. 126 raises DnaGpuError with the QualsReport
+        as .report (dnagpu_quals_upload)"""
+        b = bytes(data)
+        h, rep = C.c_void_p(), _QualsReportC()
+        rc = lib().dnagpu_quals_upload(self.h, b if b else None, len(b), 0, C.byref(h), C.byref(rep))
+        self._quals_result(rc, h, rep)
+        return Quals(self, h)
+
+    def quals_upload_device(self, ptr, n):
+        h, rep = C.c_void_p(), _QualsReportC()
+        rc = lib().dnagpu_quals_upload(self.h, ptr, n, 1, C.byref(h), C.byref(rep))
+        self._quals_result(rc, h, rep)
+        return Quals(self, h)
+
+    def quals_from_fastq(self, data, table, src_record=None, src_offset=None):
+        """the quality column of the table that reads_from_text made from the FASTQ bytes `data` -> (Quals, QualsReport);
+        src_record / src_offset: what the loader reported for every sequence (None: sequence s is record s, offset 0).  An
+        input error raises DnaGpuError with the report as .report (dnagpu_quals_from_fastq)"""
+        b = bytes(data)
+        rec = None if src_record is None else np.ascontiguousarray(src_record, dtype=np.uint64)
+        off = None if src_offset is None else np.ascontiguousarray(src_offset, dtype=np.uint64)
+        if rec is not None and off is not None and (rec.size != table.n_sequences or off.size != table.n_sequences):
+            raise ValueError("src_record and src_offset must hold one entry per sequence")
+        ptr = lambda a: None if a is None else (a.ctypes.data if a.size else self._one.ctypes.data)
+        return self.quals_from_fastq_device(b if b else None, len(b), table, ptr(rec), ptr(off), on_device=0)
+
+    _one = np.zeros(1, dtype=np.uint64)
+
+    def quals_from_fastq_device(self, ptr, n_bytes, table, dev_src_record=None, dev_src_offset=None, on_device=1):
+        """the same from n_bytes of device memory at any byte alignment; the src arrays in device memory"""
+        h, rep = C.c_void_p(), _QualsReportC()
+        rc = lib().dnagpu_quals_from_fastq(self.h, ptr, n_bytes, on_device, table.h, dev_src_record, dev_src_offset, C.byref(h),
+                                           C.byref(rep))
+        report = self._quals_result(rc, h, rep)
+        return Quals(self, h), report
+
+    def quals_take(self, table, quals, ids, flip=None, on_device=False):
+        """the column of dna_take(table, ids, flip): the qualities of the sequences ids, reversed where flipped -> Quals"""
+        h = C.c_void_p()
+        if on_device:
+            _chk(lib().dnagpu_quals_take(self.h, table.h, quals.h, ids[0], flip, ids[1], 1, C.byref(h)))
+            return Quals(self, h)
+        a = np.ascontiguousarray(ids, dtype=np.uint64)
+        f = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, dtype=np.uint8)
+        if f is not None and f.size != a.size:
+            raise ValueError("flip must hold one flag per id")
+        _chk(lib().dnagpu_quals_take(self.h, table.h, quals.h, a.ctypes.data if a.size else None,
+                                     f.ctypes.data if f is not None and f.size else None, a.size, 0, C.byref(h)))
+        return Quals(self, h)
+
+    def quals_gather(self, quals, first, length, flip=None, on_device=False):
+        """the column of dna_gather(dna, first, length, flip) -> Quals; on_device: first = (dev_first, n), length and flip
+        device pointers"""
+        h = C.c_void_p()
+        if on_device:
+            _chk(lib().dnagpu_quals_gather(self.h, quals.h, first[0], length, flip, first[1], 1, C.byref(h)))
+            return Quals(self, h)
+        a = np.ascontiguousarray(first, dtype=np.uint64)
+        b = np.ascontiguousarray(length, dtype=np.uint64)
+        f = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, dtype=np.uint8)
+        if b.size != a.size or (f is not None and f.size != a.size):
+            raise ValueError("first, length and flip must be of one size")
+        _chk(lib().dnagpu_quals_gather(self.h, quals.h, a.ctypes.data if a.size else None, b.ctypes.data if b.size else None,
+                                       f.ctypes.data if f is not None and f.size else None, a.size, 0, C.byref(h)))
+        return Quals(self, h)
+
+    def quals_trim(self, table, quals, cut_front=0, cut_tail=0, min_bases=0, min_mean_q=0, low_q=0, low_frac=(0, 0), cap=None,
+                   want=True):
+        """quality trimming and filtering of every sequence of table, whose column quals is -> TrimResult
+        (dnagpu_quals_trim).  low_frac = (low_num, low_den): passes iff low * low_den <= low_num * len, (x, 0) = no such
+        test; cap: at most so many passing sequences are written (None: all); want=False: the report only"""
+        n = table.n_sequences
+        cap = n if cap is None else int(cap)
+        opt = _QualsTrimOptionsC(cut_front, cut_tail, min_mean_q, low_q, low_frac[0], low_frac[1], min_bases, 0)
+        rep = _QualsTrimReportC()
+        per = [np.empty(max(n, 1), dtype=np.uint64) for _ in range(4)] if want else [None] * 4
+        seg = [np.empty(max(cap, 1), dtype=np.uint64) for _ in range(3)] if want else [None] * 3
+        ptr = lambda a: None if a is None else a.ctypes.data
+        _chk(lib().dnagpu_quals_trim(self.h, table.h, quals.h, C.byref(opt), *[ptr(a) for a in per], *[ptr(a) for a in seg],
+                                     cap if want else 0, 0, C.byref(rep)))
+        r = TrimResult(**{f: int(getattr(rep, f)) for f in _TRIM_REPORT_FIELDS})
+        if want:
+            r.first, r.length, r.qsum, r.low = (a[:n] for a in per)
+            m = min(r.passed, cap)
+            r.seg_seq, r.seg_first, r.seg_len = (a[:m] for a in seg)
+        return r
+
+    def quals_trim_device(self, table, quals, opt, dev_per=(None,) * 4, dev_seg=(None,) * 3, cap=0):
+        """the same with every output in device memory: dev_per = (first, len, qsum, low), dev_seg = (seq, first, len)
+        pointers or None; opt: the keyword arguments of quals_trim as a dict -> TrimResult with the counters only"""
+        lf = opt.get("low_frac", (0, 0))
+        o = _QualsTrimOptionsC(opt.get("cut_front", 0), opt.get("cut_tail", 0), opt.get("min_mean_q", 0), opt.get("low_q", 0), lf[0], lf[1],
+                               opt.get("min_bases", 0), 0)
+        rep = _QualsTrimReportC()
+        _chk(lib().dnagpu_quals_trim(self.h, table.h, quals.h, C.byref(o), *dev_per, *dev_seg, cap, 1, C.byref(rep)))
+        return TrimResult(**{f: int(getattr(rep, f)) for f in _TRIM_REPORT_FIELDS})
 
     def unpack(self, dna, first=0, count=None):
         if count is None:

@@ -128,12 +128,12 @@ extern "C" uint64_t dnagpu_text_image_bytes(const dnagpu_text_image *img) { retu
 extern "C" uint64_t dnagpu_text_image_sequences(const dnagpu_text_image *img) { return img ? img->n : 0; }
 extern "C" uint64_t dnagpu_text_image_empty(const dnagpu_text_image *img) { return img ? img->empty : 0; }
 
-extern "C" int dnagpu_text_image_read(dnagpu_ctx *ctx, const dnagpu_text_image *img, uint64_t first_byte, uint64_t count,
-                                      char *out_text, int out_on_device)
+namespace {
+
+// dnagpu_text_image_read, and with quals != null dnagpu_text_image_read_quals: the same window, then the overlay
+int read_window(dnagpu_ctx *ctx, const dnagpu_text_image *img, const dnagpu_quals *quals, u64 first_byte, u64 count, char *out_text,
+                int out_on_device)
 {
-    return guarded([&]() -> int {
-    if (!ctx || !img || (count && !out_text))
-        return DNAGPU_ERR_BAD_ARG;
     if (first_byte > img->bytes || count > img->bytes - first_byte)
         return DNAGPU_ERR_BAD_ARG;
     if (count == 0)
@@ -150,10 +150,35 @@ extern "C" int dnagpu_text_image_read(dnagpu_ctx *ctx, const dnagpu_text_image *
                           reinterpret_cast<const unsigned char *>(img->pos + img->n + 1), img->n, img->name_base, img->fmt,
                           first_byte, count, dt};
     HIP_TRY(launch_export_read(a, ctx->stream));
+    if (quals)
+        HIP_TRY(launch_quals_overlay(quals->bytes, t->seq_starts, img->pos, img->n, img->fmt.term, first_byte, count, dt, ctx->stream));
     if (!out_on_device)
         HIP_TRY(hipMemcpyAsync(out_text, dt, count, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return DNAGPU_OK;
+}
+
+}  // namespace
+
+extern "C" int dnagpu_text_image_read(dnagpu_ctx *ctx, const dnagpu_text_image *img, uint64_t first_byte, uint64_t count,
+                                      char *out_text, int out_on_device)
+{
+    return guarded([&]() -> int {
+    if (!ctx || !img || (count && !out_text))
+        return DNAGPU_ERR_BAD_ARG;
+    return read_window(ctx, img, nullptr, first_byte, count, out_text, out_on_device);
+    });
+}
+
+extern "C" int dnagpu_text_image_read_quals(dnagpu_ctx *ctx, const dnagpu_text_image *img, const dnagpu_quals *quals,
+                                            uint64_t first_byte, uint64_t count, char *out_text, int out_on_device)
+{
+    return guarded([&]() -> int {
+    if (!ctx || !img || !quals || (count && !out_text))
+        return DNAGPU_ERR_BAD_ARG;
+    if (img->fmt.format != EXPORT_FASTQ || quals->n != img->table->n_bases)
+        return DNAGPU_ERR_BAD_ARG;
+    return read_window(ctx, img, quals, first_byte, count, out_text, out_on_device);
     });
 }
 

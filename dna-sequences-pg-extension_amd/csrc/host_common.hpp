@@ -1,5 +1,5 @@
 // host_common.hpp -- what the host files of the C-ABI (dnagpu_api.hip, count_host.hip, sk_host.hip, multi_host.hip, query_host.hip,
-// filter_host.hip, index_host.hip, join_host.hip, hits_host.hip, take_host.hip, profile_host.hip, seqeq_host.hip, text_host.hip, export_host.hip, host_steps.hip) share
+// filter_host.hip, index_host.hip, join_host.hip, hits_host.hip, take_host.hip, profile_host.hip, seqeq_host.hip, text_host.hip, export_host.hip, quals_host.hip, host_steps.hip) share
 // (internal, like kernels.hpp): the error macros, the context / dna / histogram objects, the buffer pool, and the few
 // functions one of the files calls in another.  Declarations only, plus the templates and macros that must be visible;
 // the definitions are in dnagpu_api.hip unless a section says otherwise.
@@ -401,6 +401,12 @@ struct dnagpu_seq_classes {
     u32 *copies = nullptr;
     u64 *sfp = nullptr;         // the (fingerprint, id) pairs sorted by fingerprint, ids ascending inside a run
     u32 *sid = nullptr;
+};
+
+// the quality column of a table (quals_host.hip): one Phred+33 byte per base of the table's stream.  It holds no boundaries.
+struct dnagpu_quals {
+    unsigned char *bytes = nullptr;     // pool memory: whole 16-byte chunks, at least one
+    u64 n = 0;
 };
 
 struct dnagpu_records {

@@ -405,6 +405,40 @@ struct ExportRead {
 };
 hipError_t launch_export_read(const ExportRead &a, hipStream_t s);
 
+// ---- the quality column of a table (quals_kernels.hip; the byte arithmetic is quals_math.hpp's).
+// col: a caller's n bytes in a column's allocation (whole 16-byte chunks); res[0] takes the minimum of the error words
+hipError_t launch_quals_validate(unsigned char *col, u64 n, unsigned long long *res, hipStream_t s);
+// FASTQ: rec[4 r ..] = start and end of the sequence line and of the quality line of every whole record (nl_base: the
+// scanned launch_reads_newlines counts, *total their sum); res[0] takes the error words of the quality lines' bytes, and
+// launch_quals_lengths adds those of the lengths, one thread per record of the records_cap that rec has room for
+hipError_t launch_quals_lines(const unsigned char *text, u64 n, u32 n_tiles, const u32 *nl_base, const u32 *total, u32 *rec,
+                              unsigned long long *res, hipStream_t s);
+hipError_t launch_quals_lengths(const unsigned char *text, u64 n, const u32 *total, const u32 *rec, u64 records_cap,
+                                unsigned long long *res, hipStream_t s);
+// src_at[s] = the text's byte where the qualities of sequence s begin; res[1] = the records, res[2] |= 1 on a bad source
+hipError_t launch_quals_sources(const unsigned char *text, u64 n, const u32 *total, const u32 *rec, const u64 *starts, u64 n_seqs,
+                                const u64 *src_record, const u64 *src_offset, u64 *src_at, unsigned long long *res, hipStream_t s);
+// out[0 .. total) = segment i's bytes src[src_at[i] ..) (backwards where seg_flip[i]) at out_starts[i]; out holds whole
+// 16-byte chunks; no byte of src outside [0, src_n) is read
+hipError_t launch_quals_copy(const unsigned char *src, u64 src_n, const u64 *src_at, const uint8_t *seg_flip, const u64 *out_starts,
+                             u64 n, u64 total, unsigned char *out, hipStream_t s);
+// dst[0 .. count) = bytes [first, first + count) of a FASTQ image as launch_export_read left them: the bytes of quality
+// lines become the column's; dst at any byte alignment; no byte of dst outside them is written or read
+hipError_t launch_quals_overlay(const unsigned char *quals, const u64 *starts, const u64 *pos, u64 n, u32 term, u64 first,
+                                u64 count, unsigned char *dst, hipStream_t s);
+// the trim: first / len / qsum / low[s] (none null) = the kept range of every sequence as a stream coordinate and a length,
+// the sum of its Phred values and its bases below low_q.  lists: 2 n_seqs words, counts2: 2 words (scratch: the longer
+// sequences by class).  Three launches: groups of lanes, waves, workgroups.
+struct QualsTrimOpt;
+hipError_t launch_quals_trim(const unsigned char *col, const u64 *starts, u64 n_seqs, const QualsTrimOpt &o, u64 *first, u64 *len,
+                             u64 *qsum, u64 *low, u32 *lists, u32 *counts2, hipStream_t s);
+// flags[s] = sequence s passes; res7 = {passed, bases kept, cut in front, cut at the tail, failed short, mean, low} (zeroed here)
+hipError_t launch_quals_verdict(const u64 *starts, u64 n_seqs, const QualsTrimOpt &o, const u64 *first, const u64 *len, const u64 *qsum,
+                                const u64 *low, u32 *flags, unsigned long long *res7, hipStream_t s);
+// rank: the scanned flags; the passing sequences in table order, at most cap of them; any list may be null
+hipError_t launch_quals_segments(const u32 *flags, const u32 *rank, const u64 *first, const u64 *len, u64 n_seqs, u64 cap, u64 *seg_seq,
+                                 u64 *seg_first, u64 *seg_len, hipStream_t s);
+
 // ---- equal sequences (seqeq_kernels.hip; classes, items, realigned word and fingerprint are
 // seqeq_math.hpp's).  A table, or a window of one: starts = seq_starts + seq_first, n + 1 entries.
 struct SeqTable {

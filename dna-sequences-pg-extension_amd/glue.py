@@ -212,6 +212,20 @@ def lib():
         L.copy_dna_to_failed.argtypes = [vp]
         L.copy_dna_to_end.restype = None
         L.copy_dna_to_end.argtypes = [vp]
+        L.trim_reads_begin.restype = vp
+        L.trim_reads_begin.argtypes = [C.c_int, C.c_uint, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.trim_reads_next.restype = C.c_bool
+        L.trim_reads_next.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(vp)]
+        L.copy_reads_to_begin.restype = vp
+        L.copy_reads_to_begin.argtypes = [C.c_bool]
+        for f in (L.copy_reads_to_add, L.copy_reads_to_finish, L.copy_reads_to_next, L.copy_reads_to_failed):
+            f.restype = C.c_bool
+        L.copy_reads_to_add.argtypes = [vp, vp, C.c_char_p, C.c_size_t]
+        L.copy_reads_to_finish.argtypes = [vp]
+        L.copy_reads_to_next.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+        L.copy_reads_to_failed.argtypes = [vp]
+        L.copy_reads_to_end.restype = None
+        L.copy_reads_to_end.argtypes = [vp]
         L.kmer_index_create.restype = vp
         L.kmer_index_create.argtypes = [C.POINTER(_Kmer), C.c_uint64]
         L.kmer_index_rows.restype = C.c_uint64
@@ -842,6 +856,69 @@ def copy_reads(pieces, format=3, ambiguous=0, fold_case=False, min_bases=0):
         return rows, records, offsets
     finally:
         lib().copy_dna_end(c)
+
+
+def trim_reads(pieces, ambiguous=0, fold_case=False, cut_front=0, cut_tail=0, min_bases=0, min_mean_q=0, low_q=0, low_frac=(0, 0)):
+    """FASTQ with its qualities, quality-trimmed and filtered on the device: pieces = the file's bytes in order, in pieces of
+    any size -> ([dna], [record], [offset], [quality bytes]) of the passing reads in file order; offset = the index of the
+    read's first kept base in its source record's sequence.  With all thresholds 0 it is the plain load with qualities.  An
+    input ERROR raises GlueError with the library's message and .record = the source record it belongs to (-1: none)"""
+    c = lib().trim_reads_begin(int(ambiguous), 2 if fold_case else 0, int(cut_front), int(cut_tail), int(min_bases), int(min_mean_q),
+                               int(low_q), int(low_frac[0]), int(low_frac[1]))
+    if not c:
+        raise _err()
+    try:
+        rows, records, offsets, quals = [], [], [], []
+        p, rec, off, q = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_void_p()
+
+        def drain():
+            while lib().trim_reads_next(c, C.byref(p), C.byref(rec), C.byref(off), C.byref(q)):
+                rows.append(dna(p=p.value))
+                records.append(rec.value)
+                offsets.append(off.value)
+                quals.append(C.string_at(q.value))
+                _libc.free(q.value)
+
+        def check(ok):
+            if not ok:
+                e = _err()
+                lib().trim_reads_next(c, None, C.byref(rec), None, None)
+                e.record = rec.value
+                raise e
+        for piece in pieces:
+            b = bytes(piece)
+            check(lib().copy_dna_feed(c, b, len(b), False))
+            drain()
+        check(lib().copy_dna_feed(c, None, 0, True))
+        drain()
+        return rows, records, offsets, quals
+    finally:
+        lib().copy_dna_end(c)
+
+
+def copy_reads_to(rows, quals, crlf=False):
+    """rows (dna) with their quality texts (bytes, one per base) -> the FASTQ file's bytes; row r of the COPY is named r"""
+    c = lib().copy_reads_to_begin(bool(crlf))
+    if not c:
+        raise _err()
+    try:
+        out = []
+        p, n = C.c_void_p(), C.c_size_t()
+
+        def drain():
+            while lib().copy_reads_to_next(c, C.byref(p), C.byref(n)):
+                out.append(C.string_at(p.value, n.value))
+        for row, q in zip(rows, quals):
+            q = bytes(q)
+            if not lib().copy_reads_to_add(c, _as_dna(row).p, q, len(q)):
+                raise _err()
+            drain()
+        if not lib().copy_reads_to_finish(c):
+            raise _err()
+        drain()
+        return b"".join(out)
+    finally:
+        lib().copy_reads_to_end(c)
 
 
 class kmer_index:

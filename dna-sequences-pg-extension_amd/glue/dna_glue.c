@@ -2006,6 +2006,11 @@ struct CopyDna {
     uint64_t *src_record, *src_offset;           /* per row of rows[]: the source record of the whole file, the offset in it */
     uint64_t cap_src_record, cap_src_offset;
     uint64_t first_record;                       /* source records of the whole file before the buffer's first byte */
+    /* trim_reads_begin: FASTQ with its qualities, trimmed and filtered on the device; every row has its quality text */
+    bool trim;
+    dnagpu_quals_trim_options trim_opt;
+    char **qual;                                 /* per row of rows[]: malloc'd, NUL-terminated (NULL once handed out) */
+    uint64_t cap_qual;
 };
 
 CopyDna *copy_dna_begin(int format)
@@ -2045,6 +2050,113 @@ CopyDna *copy_reads_begin(int format, int ambiguous, unsigned flags, uint64_t mi
     return c;
 }
 
+CopyDna *trim_reads_begin(int ambiguous, unsigned flags, uint32_t cut_front, uint32_t cut_tail, uint64_t min_bases, uint32_t min_mean_q,
+                          uint32_t low_q, uint32_t low_num, uint32_t low_den)
+{
+    if (cut_front > 255 || cut_tail > 255 || min_mean_q > 255 || low_q > 255) {
+        ereport_error("trim_reads: cut_front, cut_tail, min_mean_q and low_q must be at most 255");
+        return NULL;
+    }
+    CopyDna *c = copy_reads_begin(DNAGPU_TEXT_FASTQ, ambiguous, flags, 0);
+    if (!c)
+        return NULL;
+    c->trim = true;
+    const dnagpu_quals_trim_options o = {cut_front, cut_tail, min_mean_q, low_q, low_num, low_den, min_bases, 0};
+    c->trim_opt = o;
+    return c;
+}
+
+/* trim_reads: the table d that the loader made of the first text_bytes bytes of the buffer (rec / off: its source map, n_seqs
+ * entries) with its qualities, trimmed and filtered on the device: the passing reads appended as rows with their source
+ * record, the offset of their first kept base in it, and their quality text.  *appended = how many. */
+static bool trim_load(CopyDna *c, const dnagpu_dna *d, uint64_t text_bytes, const uint64_t *rec, const uint64_t *off, uint64_t n_seqs,
+                      uint64_t *appended)
+{
+    dnagpu_quals *q = NULL, *tq = NULL;
+    dnagpu_dna *td = NULL;
+    dnagpu_quals_report qrep;
+    dnagpu_quals_trim_report trep;
+    uint64_t *seg = NULL, *starts = NULL;
+    char *text = NULL;
+    bool ok = false;
+    *appended = 0;
+    const int rc = dnagpu_quals_from_fastq(g_ctx, c->buf, text_bytes, 0, d, n_seqs ? rec : NULL, n_seqs ? off : NULL, &q, &qrep);
+    if (rc != DNAGPU_OK) {
+        if (qrep.bad_pos != UINT64_MAX) {                                 /* an input error: the library's message verbatim */
+            ereport_error("%s", dnagpu_last_error());
+            c->bad_line = qrep.bad_record == UINT64_MAX ? 0 : (int64_t)(c->first_record + qrep.bad_record + 1);
+            return false;
+        }
+        return gpu_ok(rc);
+    }
+    if (n_seqs == 0) {
+        dnagpu_quals_free(g_ctx, q);
+        return true;
+    }
+    seg = (uint64_t *)malloc(sizeof(uint64_t) * 3 * (size_t)n_seqs);
+    starts = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(n_seqs + 1));
+    if (!seg || !starts) {
+        ereport_error("out of memory");
+        goto done;
+    }
+    uint64_t *seg_seq = seg, *seg_first = seg + n_seqs, *seg_len = seg + 2 * n_seqs;
+    if (!gpu_ok(dnagpu_quals_trim(g_ctx, d, q, &c->trim_opt, NULL, NULL, NULL, NULL, seg_seq, seg_first, seg_len, n_seqs, 0, &trep)) ||
+        !gpu_ok(dnagpu_dna_sequence_starts(g_ctx, d, 0, n_seqs + 1, starts, 0)))
+        goto done;
+    const uint64_t m = trep.passed;
+    if (m == 0) {
+        ok = true;
+        goto done;
+    }
+    if (!gpu_ok(dnagpu_dna_gather(g_ctx, d, seg_first, seg_len, NULL, m, 0, &td)) ||
+        !gpu_ok(dnagpu_quals_gather(g_ctx, q, seg_first, seg_len, NULL, m, 0, &tq)))
+        goto done;
+    const uint64_t kept = dnagpu_quals_bases(tq);
+    text = (char *)malloc((size_t)kept + 1);
+    if (!text) {
+        ereport_error("out of memory");
+        goto done;
+    }
+    if (!gpu_ok(dnagpu_quals_read(g_ctx, tq, 0, kept, text, 0)) ||
+        !agg_grow((void **)&c->rows, &c->cap_rows, c->n_rows + m) || !agg_grow((void **)&c->qual, &c->cap_qual, c->n_rows + m) ||
+        !agg_grow((void **)&c->src_record, &c->cap_src_record, c->n_rows + m) ||
+        !agg_grow((void **)&c->src_offset, &c->cap_src_offset, c->n_rows + m) || !table_rows(td, m, c->rows + c->n_rows))
+        goto done;
+    uint64_t at = 0;
+    for (uint64_t i = 0; i < m; i++)
+        c->qual[c->n_rows + i] = NULL;
+    for (uint64_t i = 0; i < m; i++) {
+        const uint64_t s = seg_seq[i], len = seg_len[i];
+        char *t = (char *)malloc((size_t)len + 1);
+        if (!t) {
+            ereport_error("out of memory");
+            for (uint64_t j = 0; j < m; j++) {                            /* the rows of this load are not kept */
+                dna_free(c->rows[c->n_rows + j]);
+                free(c->qual[c->n_rows + j]);
+            }
+            goto done;
+        }
+        memcpy(t, text + at, (size_t)len);
+        t[len] = 0;
+        at += len;
+        c->qual[c->n_rows + i] = t;
+        c->src_record[c->n_rows + i] = c->first_record + rec[s];
+        c->src_offset[c->n_rows + i] = off[s] + (seg_first[i] - starts[s]);
+    }
+    *appended = m;
+    ok = true;
+done:
+    free(text);
+    free(seg);
+    free(starts);
+    if (td)
+        dnagpu_dna_free(g_ctx, td);
+    if (tq)
+        dnagpu_quals_free(g_ctx, tq);
+    dnagpu_quals_free(g_ctx, q);
+    return ok;
+}
+
 /* copy_load for copy_reads_begin: the same chunk through dnagpu_reads_from_text.  The source arrays are sized for reads of
  * 32 bytes and more; a chunk of shorter ones is loaded a second time with the size its report names */
 static bool copy_load_reads(CopyDna *c, uint64_t n, bool more)
@@ -2082,20 +2194,26 @@ static bool copy_load_reads(CopyDna *c, uint64_t n, bool more)
     }
     if (c->next == c->n_rows)                                             /* everything served: the arrays start over */
         c->n_rows = c->next = 0;
-    bool ok = agg_grow((void **)&c->rows, &c->cap_rows, c->n_rows + rep.sequences) &&
-              agg_grow((void **)&c->src_record, &c->cap_src_record, c->n_rows + rep.sequences) &&
-              agg_grow((void **)&c->src_offset, &c->cap_src_offset, c->n_rows + rep.sequences) &&
-              (rep.sequences == 0 || table_rows(d, rep.sequences, c->rows + c->n_rows));
-    dnagpu_dna_free(g_ctx, d);
-    for (uint64_t i = 0; ok && i < rep.sequences; i++) {
-        c->src_record[c->n_rows + i] = c->first_record + rec[i];
-        c->src_offset[c->n_rows + i] = off[i];
+    uint64_t added = rep.sequences;
+    bool ok;
+    if (c->trim) {                                                        /* the qualities of the same bytes, then the trim */
+        ok = trim_load(c, d, more ? rep.consumed : n, rec, off, rep.sequences, &added);
+    } else {
+        ok = agg_grow((void **)&c->rows, &c->cap_rows, c->n_rows + rep.sequences) &&
+             agg_grow((void **)&c->src_record, &c->cap_src_record, c->n_rows + rep.sequences) &&
+             agg_grow((void **)&c->src_offset, &c->cap_src_offset, c->n_rows + rep.sequences) &&
+             (rep.sequences == 0 || table_rows(d, rep.sequences, c->rows + c->n_rows));
+        for (uint64_t i = 0; ok && i < rep.sequences; i++) {
+            c->src_record[c->n_rows + i] = c->first_record + rec[i];
+            c->src_offset[c->n_rows + i] = off[i];
+        }
     }
+    dnagpu_dna_free(g_ctx, d);
     free(rec);
     free(off);
     if (!ok)
         return false;
-    c->n_rows += rep.sequences;
+    c->n_rows += added;
     c->first_record += rep.records;
     if (rep.consumed && c->len > rep.consumed)
         memmove(c->buf, c->buf + rep.consumed, (size_t)(c->len - rep.consumed));
@@ -2222,12 +2340,33 @@ bool copy_reads_next(CopyDna *c, Dna **row, int64_t *record, int64_t *offset)
     return copy_dna_next(c, row, NULL);
 }
 
+bool trim_reads_next(CopyDna *c, Dna **row, int64_t *record, int64_t *offset, char **quality)
+{
+    if (c->failed || !c->trim) {
+        if (record)
+            *record = c->bad_line - 1;
+        return false;
+    }
+    if (c->next >= c->n_rows)
+        return false;
+    const uint64_t i = c->next;
+    if (quality)
+        *quality = c->qual[i];                                            /* the caller's from here on (free) */
+    else
+        free(c->qual[i]);
+    c->qual[i] = NULL;
+    return copy_reads_next(c, row, record, offset);
+}
+
 bool copy_dna_failed(const CopyDna *c) { return c->failed; }
 
 void copy_dna_end(CopyDna *c)
 {
     if (!c)
         return;
+    for (uint64_t i = 0; c->qual && i < c->n_rows; i++)
+        free(c->qual[i]);
+    free(c->qual);
     for (uint64_t i = 0; i < c->n_rows; i++)
         dna_free(c->rows[i]);
     free(c->rows);
@@ -2249,6 +2388,10 @@ struct CopyDnaTo {
     char **text;                                 /* the chunks of text formed and not yet served (NULL once served and freed) */
     uint64_t *text_len;
     uint64_t cap_text, cap_text_len, n_text, next;
+    /* copy_reads_to_begin: FASTQ whose quality lines are the rows' own */
+    bool reads;
+    char *qual;                                  /* the quality bytes of the open batch, one per base */
+    uint64_t cap_qual;
 };
 
 CopyDnaTo *copy_dna_to_begin(int format, uint32_t line_width, bool crlf)
@@ -2275,7 +2418,7 @@ CopyDnaTo *copy_dna_to_begin(int format, uint32_t line_width, bool crlf)
 }
 
 /* the image of the batch's table, chunk after chunk, behind the chunks that wait */
-static bool copy_to_read(CopyDnaTo *c, const dnagpu_text_image *img)
+static bool copy_to_read(CopyDnaTo *c, const dnagpu_text_image *img, const dnagpu_quals *quals)
 {
     const uint64_t bytes = dnagpu_text_image_bytes(img);
     for (uint64_t at = 0; at < bytes; at += c->chunk) {
@@ -2290,7 +2433,7 @@ static bool copy_to_read(CopyDnaTo *c, const dnagpu_text_image *img)
         }
         c->text[c->n_text] = t;
         c->text_len[c->n_text++] = n;
-        if (!gpu_ok(dnagpu_text_image_read(g_ctx, img, at, n, t, 0)))
+        if (!gpu_ok(quals ? dnagpu_text_image_read_quals(g_ctx, img, quals, at, n, t, 0) : dnagpu_text_image_read(g_ctx, img, at, n, t, 0)))
             return false;
     }
     return true;
@@ -2306,9 +2449,23 @@ static bool copy_to_flush(void *self)
                                              NULL, 0, 0, {0, 0, 0}};
         dnagpu_dna *d = NULL;
         dnagpu_text_image *img = NULL;
-        ok = batch_upload(&c->b, &d) && gpu_ok(dnagpu_table_to_text(g_ctx, d, &opt, &img)) && copy_to_read(c, img);
+        dnagpu_quals *q = NULL;
+        ok = batch_upload(&c->b, &d);
+        if (ok && c->reads) {
+            dnagpu_quals_report qrep;
+            const int rc = dnagpu_quals_upload(g_ctx, c->qual, c->b.n_bases, 0, &q, &qrep);
+            if (rc != DNAGPU_OK && qrep.bad_pos != UINT64_MAX) {          /* the library's message verbatim */
+                ereport_error("%s", dnagpu_last_error());
+                ok = false;
+            } else {
+                ok = gpu_ok(rc);
+            }
+        }
+        ok = ok && gpu_ok(dnagpu_table_to_text(g_ctx, d, &opt, &img)) && copy_to_read(c, img, q);
         if (img)
             dnagpu_text_image_free(g_ctx, img);
+        if (q)
+            dnagpu_quals_free(g_ctx, q);
         if (d)
             dnagpu_dna_free(g_ctx, d);
         c->rows_before += c->b.n_seqs;
@@ -2337,6 +2494,46 @@ bool copy_dna_to_add(CopyDnaTo *c, const Dna *row)
         return !(c->failed = true);
     return true;
 }
+
+CopyDnaTo *copy_reads_to_begin(bool crlf)
+{
+    CopyDnaTo *c = copy_dna_to_begin(DNAGPU_TEXT_FASTQ, 0, crlf);
+    if (c)
+        c->reads = true;
+    return c;
+}
+
+bool copy_reads_to_add(CopyDnaTo *c, const Dna *row, const char *quality, size_t quality_len)
+{
+    if (c->finished || c->failed || !c->reads) {
+        ereport_error("copy_reads_to: a row added after the last one or after the COPY failed");
+        return false;
+    }
+    if (!row || (quality_len && !quality)) {
+        ereport_error("copy_reads_to: the row or its quality text is missing");
+        return false;
+    }
+    if ((uint64_t)quality_len != row->length) {
+        ereport_error("FASTQ quality line length differs from the sequence's");
+        return !(c->failed = true);
+    }
+    if (rb_spills(&c->b, row->length, c->limit_bases) && !copy_to_flush(c))
+        return !(c->failed = true);
+    if (!rb_grow((void **)&c->qual, &c->cap_qual, c->b.n_bases + row->length + 1) || !rb_append(&c->b, row->bit_sequence, row->length)) {
+        ereport_error("out of memory");
+        return !(c->failed = true);
+    }
+    if (quality_len)
+        memcpy(c->qual + c->b.n_bases - row->length, quality, quality_len);
+    if (rb_full(&c->b, c->limit_bases) && !copy_to_flush(c))
+        return !(c->failed = true);
+    return true;
+}
+
+bool copy_reads_to_finish(CopyDnaTo *c) { return copy_dna_to_finish(c); }
+bool copy_reads_to_next(CopyDnaTo *c, const char **bytes, size_t *n) { return copy_dna_to_next(c, bytes, n); }
+bool copy_reads_to_failed(const CopyDnaTo *c) { return copy_dna_to_failed(c); }
+void copy_reads_to_end(CopyDnaTo *c) { copy_dna_to_end(c); }
 
 bool copy_dna_to_finish(CopyDnaTo *c)
 {
@@ -2374,6 +2571,7 @@ void copy_dna_to_end(CopyDnaTo *c)
         free(c->text[i]);
     free(c->text);
     free(c->text_len);
+    free(c->qual);
     rb_free(&c->b);
     free(c);
 }

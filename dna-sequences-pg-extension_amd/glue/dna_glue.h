@@ -332,6 +332,30 @@ bool copy_dna_to_finish(CopyDnaTo *c);
 bool copy_dna_to_next(CopyDnaTo *c, const char **bytes, size_t *n);
 bool copy_dna_to_failed(const CopyDnaTo *c);
 void copy_dna_to_end(CopyDnaTo *c);
+/* ---- FASTQ reads WITH their qualities: in through the quality column, trimmed and filtered on the
+ * device; out with every quality line the row's own ----
+ * trim_reads_begin: a copy_reads handle for FASTQ (ambiguous and flags as copy_reads_begin) whose chunks also go through
+ *   dnagpu_quals_from_fastq and dnagpu_quals_trim: cut_front / cut_tail are cutadapt's thresholds (0: no cut), a read passes
+ *   iff its kept length is > 0 and >= min_bases, its Phred sum >= min_mean_q * length, and its bases below low_q number at most
+ *   low_num / low_den of it (low_den 0: no such test).  With all of them 0 it is the plain load with qualities.  A threshold
+ *   above 255 is an ERROR (NULL).  Fed with copy_dna_feed, asked with copy_dna_failed, ended with copy_dna_end.
+ * trim_reads_next = one passing read: its kept bases, record = its 0-based source record of the whole file, offset = the index
+ *   of its first kept base in that record's sequence, *quality = its quality text (malloc'd, NUL-terminated, the caller's;
+ *   NULL: not wanted).  After an input ERROR false with record as copy_reads_next.  Besides copy_reads' messages: "FASTQ
+ *   quality line length differs from the sequence's", "invalid FASTQ quality character".
+ * copy_reads_to_begin / _add: copy_dna_to for FASTQ where every row comes with its quality text, quality_len bytes (not
+ *   NUL-terminated).  A text of another length than the row is the ERROR "FASTQ quality line length differs from the
+ *   sequence's"; a byte outside 33 .. 126 is "invalid FASTQ quality character", raised when the batch is written.
+ *   finish, next, failed and end are copy_dna_to's. */
+CopyDna *trim_reads_begin(int ambiguous, unsigned flags, uint32_t cut_front, uint32_t cut_tail, uint64_t min_bases, uint32_t min_mean_q,
+                          uint32_t low_q, uint32_t low_num, uint32_t low_den);
+bool trim_reads_next(CopyDna *c, Dna **row, int64_t *record, int64_t *offset, char **quality);
+CopyDnaTo *copy_reads_to_begin(bool crlf);
+bool copy_reads_to_add(CopyDnaTo *c, const Dna *row, const char *quality, size_t quality_len);
+bool copy_reads_to_finish(CopyDnaTo *c);
+bool copy_reads_to_next(CopyDnaTo *c, const char **bytes, size_t *n);
+bool copy_reads_to_failed(const CopyDnaTo *c);
+void copy_reads_to_end(CopyDnaTo *c);
 
 /* ---- CREATE INDEX ... ON kmer_data_t USING spgist (kmer_sequence spgist_kmer_ops) and the index scans of `=`, `^@` and `@>`
  * over the stored column (dna--1.0.sql:304-314; test.sql:156-270) ----

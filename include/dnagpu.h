@@ -488,6 +488,121 @@ int      dnagpu_text_image_record_pos(dnagpu_ctx *ctx, const dnagpu_text_image *
                                       uint64_t *out_pos, int out_on_device);
 void     dnagpu_text_image_free(dnagpu_ctx *ctx, dnagpu_text_image *img);
 int      dnagpu_text_out_geometry(uint64_t *tile_bytes);              /* bytes one workgroup forms; needs no device */
+
+/* ---- The quality column of a table of reads: dnagpu_quals.
+ *
+ * A column is an owned object (dnagpu_quals_free) of n bytes in device memory: byte b is the raw Phred+33 character of
+ *   base b of a table's stream.  It holds no boundaries of its own: every call that needs them takes the table too, and
+ *   answers DNAGPU_ERR_BAD_ARG when dnagpu_dna_length(table) != dnagpu_quals_bases(q).  Every byte of a column is in 33 ..
+ *   126; that is checked wherever a column is made, so no later call has an error path for it.
+ * dnagpu_quals_upload: a column from the caller's n bytes (host memory, or device memory when on_device != 0).  A byte
+ *   outside 33 .. 126 is DNAGPU_ERR_BAD_ARG, "invalid FASTQ quality character"; the lowest offset is found on the device
+ *   and reported with the character in report->bad_pos / bad_char (report may be NULL).  A NULL ctx or out, or NULL bytes
+ *   with n > 0, is DNAGPU_ERR_BAD_ARG; n > 2^32 - 1 is DNAGPU_ERR_TOO_LARGE (a resident table's limit).  n == 0 gives a
+ *   valid column of 0 bytes.
+ * dnagpu_quals_bases: n (0 for NULL).  dnagpu_quals_read: bytes [first, first + count) to out (host memory, or device
+ *   memory when out_on_device != 0) by dnagpu_ranking_read's window rule: first > n or count > n - first is
+ *   DNAGPU_ERR_BAD_ARG; count == 0 is DNAGPU_OK; a NULL ctx or q, or a NULL out with count > 0, is DNAGPU_ERR_BAD_ARG.
+ *
+ * dnagpu_quals_from_fastq: the column of the table that dnagpu_reads_from_text made from the same bytes.
+ *   text[0 .. n_bytes) is whole FASTQ records (with DNAGPU_READS_MORE the caller passes the loader's `consumed`);
+ *   src_record / src_offset are the arrays the loader wrote, one entry per sequence of the table (device memory iff
+ *   text_on_device; both NULL: sequence s is record s at offset 0).  The qualities of sequence s, of len_s bases, are bytes
+ *   [src_offset[s], src_offset[s] + len_s) of the quality line of record src_record[s]; they are placed at the sequence's
+ *   place in the stream.  DROP, SPLIT and min_bases are covered by this with no policy here.
+ *   Input errors carry a byte offset (report->bad_pos, and the record in bad_record); the lowest offset wins, and at one
+ *   offset a length error comes before a character error.  A line count that is no multiple of 4 is DNAGPU_ERR_BAD_ARG,
+ *   "truncated FASTQ record", at the first byte of the unfinished record.  A quality line whose length differs from its
+ *   sequence line's is DNAGPU_ERR_BAD_ARG, "FASTQ quality line length differs from the sequence's", at the quality line's
+ *   first byte; lengths are taken without the terminator, and a '\r' directly before '\n' belongs to the terminator (the
+ *   check dnagpu_reads_from_text leaves out).  A byte outside 33 .. 126 in a quality line is the error of
+ *   dnagpu_quals_upload at that byte.  '@' and '+' are not looked at again: the loader owns that check.
+ *   Checks, in order: a NULL ctx, table or out, or NULL text with n_bytes > 0, is DNAGPU_ERR_BAD_ARG; only one of the two
+ *   src arrays is DNAGPU_ERR_BAD_ARG; a non-empty stream without a sequence set is DNAGPU_ERR_BAD_ARG; n_bytes > 2^32 - 1 is
+ *   DNAGPU_ERR_TOO_LARGE.  These need no device.  Then the input errors; then the sources: src_record[s] >= the text's
+ *   records, or src_offset[s] + len_s beyond that record's quality line, is DNAGPU_ERR_BAD_ARG with no offset.  On every
+ *   error *out is left as it was and nothing stays allocated.  The call waits for its work.
+ *
+ * dnagpu_quals_gather / dnagpu_quals_take: the arguments, the checks in their order and the limits of dnagpu_dna_gather /
+ *   dnagpu_dna_take, over the column (gather: segments of src's bytes; take: sequences of `table`, whose column `quals`
+ *   is -- a column of another length is DNAGPU_ERR_BAD_ARG, checked after the missing sequence set).  Given the same lists,
+ *   the result is the column of the table those two return.  A flipped segment is reversed: qualities have no complement.
+ *
+ * dnagpu_text_image_read_quals: dnagpu_text_image_read with every quality line of the image taken from the column -- the
+ *   quality line of sequence s is the column's bytes [starts[s], starts[s + 1]) -- and dnagpu_text_out_options.quality
+ *   ignored.  The image must be FASTQ and dnagpu_quals_bases(quals) the bases of the image's table, else
+ *   DNAGPU_ERR_BAD_ARG (after the NULL checks, before the window's).  The window rule, the any-alignment rule and the "no
+ *   byte outside the window is touched" rule are dnagpu_text_image_read's; windows tile; every byte outside a quality line
+ *   is what dnagpu_text_image_read writes.
+ *
+ * dnagpu_quals_trim: quality trimming and quality filtering of every sequence of a table, on the device.  The Phred value
+ *   of a byte is byte - 33.  For a sequence with values q[0 .. n) the cut points are cutadapt's / BWA's, each computed over
+ *   the whole sequence:
+ *     front (cut_front = F; F == 0: start = 0):  s = 0, best = 0, start = 0
+ *         for i = 0 .. n-1:  s += F - q[i];  if s < 0: break;  if s > best: best = s, start = i + 1
+ *     tail  (cut_tail = T; T == 0: stop = n):    s = 0, best = 0, stop = n
+ *         for i = n-1 .. 0:  s += T - q[i];  if s < 0: break;  if s > best: best = s, stop = i
+ *     if start >= stop: start = stop = 0
+ *   Per sequence s, over [start, stop), all uint64: out_first[s] = starts[s] + start (a stream coordinate), out_len[s] the
+ *   kept length, out_qsum[s] the sum of the values, out_low[s] the bases with a value < low_q.  With len the kept length a
+ *   sequence passes iff len > 0, len >= min_bases, qsum >= min_mean_q * len and low * low_den <= low_num * len (64-bit
+ *   integer comparisons; low_den == 0 switches the last test off); a failing sequence is counted under the first criterion
+ *   it fails, in the order short, mean, low.  The passing sequences are written in table order as seg_seq / seg_first /
+ *   seg_len, at most seg_cap of them (the report carries the full count): lists that go straight into dnagpu_dna_gather
+ *   and dnagpu_quals_gather.  Every output is host memory, or device memory when out_on_device != 0; any may be NULL.
+ *   The report: sequences, passed, bases_in, bases_kept, the bases cut in front (start) and at the tail (n - stop), summed
+ *   over all sequences after the start >= stop rule -- a sequence cut away whole counts at the tail -- so that bases_in =
+ *   bases_kept + cut_front + cut_tail, and the three failure counts.  It is the call's only read-back.
+ *   Checks, in order: a NULL ctx, table, quals or opt is DNAGPU_ERR_BAD_ARG; cut_front, cut_tail, min_mean_q or low_q above
+ *   255, or a non-zero reserved, is DNAGPU_ERR_BAD_ARG; a non-empty stream without a sequence set is DNAGPU_ERR_BAD_ARG; a
+ *   column of another length than the table is DNAGPU_ERR_BAD_ARG.  These need no device.  The call waits for its work.
+ *   dnagpu_quals_geometry names the paths by length (needs no device): a sequence of at most group_bases bases is handled
+ *   by a group of 16 lanes of one wave, one of at most wave_bases by a wave, one of at most tile_bases by a workgroup in
+ *   one tile, a longer one by a workgroup tile after tile. */
+typedef struct dnagpu_quals dnagpu_quals;
+typedef struct dnagpu_quals_trim_options {
+    uint32_t cut_front;   /* F; 0: no cut in front */
+    uint32_t cut_tail;    /* T; 0: no cut at the tail */
+    uint32_t min_mean_q;  /* passes iff qsum >= min_mean_q * len */
+    uint32_t low_q;       /* a base is low iff its value < low_q */
+    uint32_t low_num;     /* passes iff low * low_den <= low_num * len; low_den == 0: no such test */
+    uint32_t low_den;
+    uint64_t min_bases;   /* passes iff len >= min_bases (and len > 0) */
+    uint64_t reserved;    /* 0 */
+} dnagpu_quals_trim_options;
+typedef struct dnagpu_quals_trim_report {
+    uint64_t sequences, passed, bases_in, bases_kept, cut_front, cut_tail, failed_short, failed_mean, failed_low;
+} dnagpu_quals_trim_report;
+int      dnagpu_quals_trim(dnagpu_ctx *ctx, const dnagpu_dna *table, const dnagpu_quals *quals, const dnagpu_quals_trim_options *opt,
+                           uint64_t *out_first, uint64_t *out_len, uint64_t *out_qsum, uint64_t *out_low, uint64_t *seg_seq,
+                           uint64_t *seg_first, uint64_t *seg_len, uint64_t seg_cap, int out_on_device,
+                           dnagpu_quals_trim_report *report);
+int      dnagpu_quals_geometry(uint64_t *group_bases, uint64_t *wave_bases, uint64_t *tile_bases);
+typedef struct dnagpu_quals_report {
+    uint64_t records;     /* dnagpu_quals_from_fastq: whole records of the text (0 when the call failed before counting) */
+    uint64_t bad_pos;     /* an input error: the byte offset; ~0 otherwise */
+    uint64_t bad_record;  /* dnagpu_quals_from_fastq: the record bad_pos lies in; ~0 otherwise */
+    char     bad_char;    /* "invalid FASTQ quality character": the character, else 0 */
+    char     reserved[7];
+} dnagpu_quals_report;
+int      dnagpu_quals_upload(dnagpu_ctx *ctx, const char *bytes, uint64_t n, int on_device, dnagpu_quals **out,
+                             dnagpu_quals_report *report);
+uint64_t dnagpu_quals_bases(const dnagpu_quals *q);
+int      dnagpu_quals_read(dnagpu_ctx *ctx, const dnagpu_quals *q, uint64_t first, uint64_t count, char *out, int out_on_device);
+void     dnagpu_quals_free(dnagpu_ctx *ctx, dnagpu_quals *q);
+int      dnagpu_quals_from_fastq(dnagpu_ctx *ctx, const char *text, uint64_t n_bytes, int text_on_device, const dnagpu_dna *table,
+                                 const uint64_t *src_record, const uint64_t *src_offset, dnagpu_quals **out,
+                                 dnagpu_quals_report *report);
+int      dnagpu_quals_gather(dnagpu_ctx *ctx, const dnagpu_quals *src, const uint64_t *seg_first, const uint64_t *seg_len,
+                             const uint8_t *seg_flip, uint64_t n_segs, int on_device, dnagpu_quals **out);
+int      dnagpu_quals_take(dnagpu_ctx *ctx, const dnagpu_dna *table, const dnagpu_quals *quals, const uint64_t *seq_ids,
+                           const uint8_t *seq_flip, uint64_t n_ids, int on_device, dnagpu_quals **out);
+int      dnagpu_text_image_read_quals(dnagpu_ctx *ctx, const dnagpu_text_image *img, const dnagpu_quals *quals,
+                                      uint64_t first_byte, uint64_t count, char *out_text, int out_on_device);
+/* bytes one lane and one workgroup of the column copy form, and the most segments of a tile it stages in LDS; needs no device.
+ * It is here for the reason dnagpu_text_geometry, dnagpu_text_out_geometry and dnagpu_quals_geometry are: the copy takes another
+ * path past each of these sizes, and a caller's tests can only place their cases on the edges if the library names them. */
+int      dnagpu_quals_copy_geometry(uint64_t *chunk_bytes, uint64_t *tile_bytes, uint64_t *lds_segments);
 /* Same over an arbitrary array of n keys of k bases already in device memory.  dev_keys is used as
  * scratch and its contents are unspecified afterwards. */
 int dnagpu_count_keys(dnagpu_ctx *ctx, uint64_t *dev_keys, uint64_t n, int k, dnagpu_hist **out);
