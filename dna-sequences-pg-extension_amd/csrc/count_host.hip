@@ -416,16 +416,10 @@ extern "C" int dnagpu_count_kmers_batch(dnagpu_ctx *ctx, const dnagpu_dna *dna, 
     if (n_seqs == 1)                               // one sequence: the plain count
         return count_core(ctx, dna, 0, rows, k, nullptr, out, 0, 0, 0, 1, true);
     PoolScope ps(ctx);
-    hipStream_t st = ctx->stream;
     // ---- the marks: one bit per base, set where a sequence starts
-    const u64 n_mark_words = dna->n_bases / 32 + 3;
+    u64 n_mark_words = 0, *d_starts = nullptr;
     u32 *marks = nullptr;
-    u64 *d_starts = nullptr;
-    RC_TRY(ps.alloc((size_t)n_mark_words, &marks));
-    RC_TRY(ps.alloc((size_t)n_seqs + 1, &d_starts));
-    HIP_TRY(hipMemcpyAsync(d_starts, seq_starts, (size_t)(n_seqs + 1) * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(launch_batch_marks(d_starts, n_seqs, marks, n_mark_words, st));
-    HIP_TRY(hipStreamSynchronize(st));             // (seq_starts is the caller's: not kept behind the call)
+    RC_TRY(starts_and_marks(ctx, ps, seq_starts, n_seqs, dna->n_bases, &d_starts, &marks, &n_mark_words));
     return count_table(ctx, dna, marks, n_mark_words, rows, k, out);
     }), out, k);
 }
@@ -451,16 +445,10 @@ extern "C" int dnagpu_dna_set_sequences(dnagpu_ctx *ctx, dnagpu_dna *dna, const 
     dna->n_seqs = dna->n_mark_words = 0;
     if (n_seqs == 0)
         return DNAGPU_OK;                          // (an empty table over an empty stream: nothing to keep)
-    hipStream_t st = ctx->stream;
     PoolScope ps(ctx);
-    const u64 n_mark_words = dna->n_bases / 32 + 3;
-    u64 *ds = nullptr;
+    u64 n_mark_words = 0, *ds = nullptr;
     u32 *dm = nullptr;
-    RC_TRY(ps.alloc((size_t)n_seqs + 1, &ds));
-    RC_TRY(ps.alloc((size_t)n_mark_words, &dm));
-    HIP_TRY(hipMemcpyAsync(ds, seq_starts, (size_t)(n_seqs + 1) * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(launch_batch_marks(ds, n_seqs, dm, n_mark_words, st));
-    HIP_TRY(hipStreamSynchronize(st));             // (seq_starts is the caller's: not kept behind the call)
+    RC_TRY(starts_and_marks(ctx, ps, seq_starts, n_seqs, dna->n_bases, &ds, &dm, &n_mark_words));
     ps.release(ds);
     ps.release(dm);
     dna->seq_starts = ds;
@@ -481,8 +469,8 @@ extern "C" int dnagpu_count_kmers_table(dnagpu_ctx *ctx, const dnagpu_dna *dna, 
     if (k < 1 || k > 32)
         return DNAGPU_ERR_INVALID_K;
     *out = nullptr;
-    if (dna->n_seqs == 0 && dna->n_bases != 0)
-        return DNAGPU_ERR_BAD_ARG;                 // (no dnagpu_dna_set_sequences before)
+    if (table_without_set(dna))
+        return DNAGPU_ERR_BAD_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     u64 rows = 0;
     if (dna->n_seqs) {

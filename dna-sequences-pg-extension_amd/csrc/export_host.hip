@@ -111,8 +111,8 @@ extern "C" int dnagpu_table_to_text(dnagpu_ctx *ctx, const dnagpu_dna *table, co
     if (!ctx || !table || !opt || !out)
         return DNAGPU_ERR_BAD_ARG;
     RC_TRY(check_options(opt));
-    if (table->n_seqs == 0 && table->n_bases != 0)
-        return DNAGPU_ERR_BAD_ARG;                   // (no dnagpu_dna_set_sequences before)
+    if (table_without_set(table))
+        return DNAGPU_ERR_BAD_ARG;
     std::unique_ptr<dnagpu_text_image> img(new dnagpu_text_image);
     const int rc = plan_image(ctx, table, opt, img.get());
     if (rc != DNAGPU_OK) {                           // (what the scope of the plan had not yet handed over is already back)

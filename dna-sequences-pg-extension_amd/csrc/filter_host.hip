@@ -268,8 +268,8 @@ extern "C" int dnagpu_generate_kmers_table(dnagpu_ctx *ctx, const dnagpu_dna *dn
     if (!ctx || !dna || !n_out)
         return DNAGPU_ERR_BAD_ARG;
     RC_TRY(check_range(dna, k, first, count));
-    if (dna->n_seqs == 0 && dna->n_bases != 0)
-        return DNAGPU_ERR_BAD_ARG;                 // (no dnagpu_dna_set_sequences before)
+    if (table_without_set(dna))
+        return DNAGPU_ERR_BAD_ARG;
     FilterBits fb = all_rows(k);
     bool none = false;
     int op_error = DNAGPU_OK;                      // raised only if a table row evaluates the operator

@@ -70,8 +70,8 @@ extern "C" int dnagpu_table_hits(dnagpu_ctx *ctx, const dnagpu_dna *dna, const d
     if (!ctx || !dna || !set || !out)
         return DNAGPU_ERR_BAD_ARG;
     *out = nullptr;
-    if (dna->n_seqs == 0 && dna->n_bases != 0)
-        return DNAGPU_ERR_BAD_ARG;                   // (no dnagpu_dna_set_sequences before)
+    if (table_without_set(dna))
+        return DNAGPU_ERR_BAD_ARG;
     if (seq_first > dna->n_seqs || seq_count > dna->n_seqs - seq_first)
         return DNAGPU_ERR_BAD_ARG;
     std::unique_ptr<dnagpu_seq_hits> h(new dnagpu_seq_hits());

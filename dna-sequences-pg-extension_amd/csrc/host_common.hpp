@@ -1,5 +1,5 @@
 // host_common.hpp -- what the host files of the C-ABI (dnagpu_api.hip, count_host.hip, sk_host.hip, multi_host.hip, query_host.hip,
-// filter_host.hip, index_host.hip, join_host.hip, hits_host.hip, take_host.hip, profile_host.hip, seqeq_host.hip, text_host.hip, export_host.hip, quals_host.hip, host_steps.hip) share
+// filter_host.hip, index_host.hip, join_host.hip, hits_host.hip, take_host.hip, profile_host.hip, seqeq_host.hip, text_host.hip, reads_host.hip, export_host.hip, quals_host.hip, host_steps.hip, table_steps.hip) share
 // (internal, like kernels.hpp): the error macros, the context / dna / histogram objects, the buffer pool, and the few
 // functions one of the files calls in another.  Declarations only, plus the templates and macros that must be visible;
 // the definitions are in dnagpu_api.hip unless a section says otherwise.
@@ -201,6 +201,10 @@ void prof_end(dnagpu_ctx *ctx);      // names[i] labels the interval [mark i, ma
 
 // ---------------------------------------------------------------- dna
 inline u64 words_for(u64 n_bases) { return (n_bases + 31) / 32; }
+// the words of seq_marks over a stream of n_bases bases: what every reader of the marks is handed as n_mark_words
+inline u64 table_mark_words(u64 n_bases) { return n_bases / 32 + 3; }
+// bases but no set: no dnagpu_dna_set_sequences before.  (An empty stream without a set is a table of no sequence.)
+inline bool table_without_set(const dnagpu_dna *dna) { return dna->n_seqs == 0 && dna->n_bases != 0; }
 // validates [first, first+count) against the row count of generate_kmers(dna, k)
 int check_range(const dnagpu_dna *dna, int k, u64 first, u64 count);
 
@@ -296,6 +300,114 @@ struct OutCols {
 
 // n entries of a u32 device array widened to u64 at `out` (host memory, or device memory; null: nothing).  Queued only.
 int widen_out(dnagpu_ctx *ctx, PoolScope &ps, const u32 *src, u64 n, u64 *out, int out_on_device);
+#pragma GCC visibility pop
+
+// ---------------------------------------------------------------- table_steps.hip
+// The host-side steps that the calls which make a resident table, or a column beside one, drive the same way: the hand-over
+// of a new table, the starts and marks of a caller's boundaries, the segment plan of take / gather, and the front end of the
+// text loaders.  (Hidden, like the steps above.)
+#pragma GCC visibility push(hidden)
+// A table being made.  It owns the scope of the call that makes it: everything allocated from ps goes back to the pool when
+// the call returns, except what hand_over (or empty) has passed to the caller.
+struct NewTable {
+    PoolScope ps;
+    std::unique_ptr<dnagpu_dna> h;
+    explicit NewTable(dnagpu_ctx *ctx) : ps(ctx) {}
+    // *out = a valid table of 0 bases with no set (one word): what dnagpu_dna_upload makes of 0 bases
+    int empty(dnagpu_dna **out);
+    // n_seqs + 1 starts, the marks and max(words, 1) stream words of n_bases bases, allocated in that order; a block that the
+    // caller already has in ps (starts, words) is adopted instead.  Nothing of it is assumed zero.
+    int alloc(u64 n_seqs, u64 n_bases, u64 *starts = nullptr, u64 *words = nullptr);
+    int queue_marks(hipStream_t st);                 // launch_batch_marks over h->seq_starts; queued only
+    void hand_over(dnagpu_dna **out);                // the three blocks leave ps; the caller has waited for the stream
+};
+
+// n_seqs + 1 starts from the host into ps memory and the marks of a stream of n_bases bases beside them.  Waits (the
+// caller's array is not kept behind the call).
+int starts_and_marks(dnagpu_ctx *ctx, PoolScope &ps, const u64 *host_starts, u64 n_seqs, u64 n_bases, u64 **starts, u32 **marks,
+                     u64 *n_mark_words);
+
+// The two faces of take / gather.  ids != nullptr: take (segment i = sequence ids[i] of the source's set); else gather
+// (first / len).  All the lists are host memory, or device memory when on_device.
+struct TakeLists {
+    const u64 *ids;
+    const u64 *first, *len;
+    const uint8_t *flip;              // may be null
+    u64 n;
+    int on_device;
+};
+// What the copy kernel of a take reads, in memory of ps: where every segment begins in the source, the flips (null: none),
+// the n + 1 starts of the result, and its bases.
+struct TakePlan {
+    const u64 *seg_first;
+    const uint8_t *flip;
+    u64 *starts;                      // written by queue_starts
+    u64 total;
+    u32 *len32, *scan_tmp;            // the lengths of the n segments, and the scratch of their scan
+    u64 n;
+    int queue_starts(dnagpu_ctx *ctx) const;         // phase "take_starts": the scan and the starts; queued only
+};
+// The plan of in.n >= 1 segments over a source of n_seqs sequences (seq_starts; take only) and stream_bases bases: the lists
+// on the device, validated and summed in one pass (one read-back: it waits, the caller's host lists have been read).
+// BAD_ARG with its text for an id >= n_seqs or a segment that leaves the stream, TOO_LARGE for more than 2^32 - 1 bases.
+// Phases: lists_mark, "take_segments" (the caller has called prof_begin).  The caller allocates its result, then queues the
+// starts.
+int take_plan(dnagpu_ctx *ctx, PoolScope &ps, const TakeLists &in, const u64 *seq_starts, u64 n_seqs, u64 stream_bases,
+              const char *lists_mark, TakePlan *plan);
+
+// A report of a text loader as it is before anything is known
+template <typename R>
+void report_clear(R *r)
+{
+    if (!r)
+        return;
+    memset(r, 0, sizeof *r);
+    r->bad_pos = ~(u64)0;
+    r->bad_record = ~(u64)0;
+}
+
+// FASTA: the state every tile begins in, and the per-tile words that launch_text_finish reads.  The caller sets sw.text,
+// sw.lim, sw.n_tiles and sw.res.  before_sweep (phase "text_heads"): the eight per-tile arrays, launch_text_heads and its two
+// maximum scans; the caller's sweep then writes sw.last_seq, sw.first_header and sw.seq_before.  after_sweep: the maximum
+// scan of last_seq and launch_text_finish.
+struct FastaTiles {
+    TextSweep sw = {};
+    u32 *last_header = nullptr, *seq_before_t = nullptr;
+    int before_sweep(dnagpu_ctx *ctx, PoolScope &ps);
+    int after_sweep(hipStream_t st) const;
+};
+
+// Where an error word points, for the launch that ranks its byte: rec_t = the scanned records per tile (LINES, FASTA),
+// nl_base = the '\n' before every tile (FASTQ)
+struct TextErrorIn {
+    const unsigned char *text;
+    u64 n;
+    const u64 *lim;
+    int format;                       // TEXT_FORMAT_*
+    const u32 *rec_t, *nl_base;
+};
+// who = {the record of the byte at pos, the byte, FASTQ: the role of its line}.  One launch, one read-back.
+int text_error_rank(dnagpu_ctx *ctx, PoolScope &ps, const TextErrorIn &in, u64 pos, u64 who[3]);
+struct TextBad {
+    u64 pos, record;
+    char byte;                        // 0 unless the error is an invalid character
+    int code;
+};
+// after the error word `word` of a sweep: where it is, dnagpu_last_error() and the code (the reference's three messages;
+// FASTQ: the truncated record, the missing '@' and '+')
+int text_error_find(dnagpu_ctx *ctx, PoolScope &ps, const TextErrorIn &in, u64 word, TextBad *bad);
+template <typename R>
+int text_input_error(dnagpu_ctx *ctx, PoolScope &ps, const TextErrorIn &in, u64 word, R *report)
+{
+    TextBad bad = {};
+    RC_TRY(text_error_find(ctx, ps, in, word, &bad));
+    if (report) {
+        report->bad_pos = bad.pos;
+        report->bad_record = bad.record;
+        report->bad_char = bad.byte;
+    }
+    return bad.code;
+}
 #pragma GCC visibility pop
 
 // ---------------------------------------------------------------- filter_host.hip

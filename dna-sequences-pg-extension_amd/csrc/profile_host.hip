@@ -74,8 +74,8 @@ extern "C" int dnagpu_table_profile(dnagpu_ctx *ctx, const dnagpu_dna *dna, int 
         return DNAGPU_ERR_BAD_ARG;
     if (seq_count > U32_MAX64)
         return DNAGPU_ERR_TOO_LARGE;                       // (more sequences than bases allows: all but 2^32 - 1 are empty)
-    if (dna->n_seqs == 0 && dna->n_bases != 0)
-        return DNAGPU_ERR_BAD_ARG;                         // (no dnagpu_dna_set_sequences before)
+    if (table_without_set(dna))
+        return DNAGPU_ERR_BAD_ARG;
     if (seq_count == 0)
         return DNAGPU_OK;
     if (!out_counts)

@@ -10,15 +10,6 @@ using namespace dnagpu;
 
 namespace {
 
-void report_clear(dnagpu_quals_report *r)
-{
-    if (!r)
-        return;
-    memset(r, 0, sizeof *r);
-    r->bad_pos = ~(u64)0;
-    r->bad_record = ~(u64)0;
-}
-
 // a column of n bytes that nothing has written yet, owned by ps until the caller releases its bytes
 int column_new(PoolScope &ps, u64 n, std::unique_ptr<dnagpu_quals> *out)
 {
@@ -93,13 +84,8 @@ int from_fastq(dnagpu_ctx *ctx, const char *text, u64 n, int text_on_device, con
     }
     prof_begin(ctx);
     prof_mark(ctx, "quals_stage");
-    const unsigned char *dtext = reinterpret_cast<const unsigned char *>(text);
-    if (!text_on_device) {
-        unsigned char *stage = nullptr;
-        RC_TRY(ps.alloc((size_t)n, &stage));
-        HIP_TRY(hipMemcpyAsync(stage, text, (size_t)n, hipMemcpyHostToDevice, st));
-        dtext = stage;
-    }
+    const unsigned char *dtext = nullptr;
+    RC_TRY(device_list(ctx, ps, reinterpret_cast<const unsigned char *>(text), n, text_on_device, &dtext));
     const u64 *drec = nullptr, *doff = nullptr;
     if (n_seqs) {
         RC_TRY(device_list(ctx, ps, src_record, n_seqs, text_on_device, &drec));
@@ -140,10 +126,8 @@ int from_fastq(dnagpu_ctx *ctx, const char *text, u64 n, int text_on_device, con
     if (got[Q_ERROR] != QUALS_NO_ERROR) {
         const u64 pos = quals_error_pos(got[Q_ERROR]);
         const u32 kind = quals_error_kind(got[Q_ERROR]);
-        u64 *who = nullptr, hwho[3] = {0, 0, 0};
-        RC_TRY(ps.alloc(3, &who));
-        HIP_TRY(launch_reads_fastq_rank(dtext, n, nl_base, pos, who, st));
-        RC_TRY(read_back(ctx, hwho, who, sizeof hwho));
+        u64 hwho[3] = {0, 0, 0};
+        RC_TRY(text_error_rank(ctx, ps, TextErrorIn{dtext, n, nullptr, TEXT_FORMAT_FASTQ, nullptr, nl_base}, pos, hwho));
         if (kind == QUALS_ERR_CHAR)
             return bad_character(pos, (char)hwho[1], hwho[0], report);
         if (report) {
@@ -174,66 +158,25 @@ int from_fastq(dnagpu_ctx *ctx, const char *text, u64 n, int text_on_device, con
 // dnagpu_dna_gather's core (take_host.hip) over bytes: ids != nullptr: segment i = sequence ids[i] of the table; else
 // (first, len).  Only the column is made: the starts of the result are scratch here, the table they belong to is what
 // dnagpu_dna_take / dnagpu_dna_gather return for the same lists.
-struct QualsLists {
-    const u64 *ids;
-    const u64 *first, *len;
-    const uint8_t *flip;
-    u64 n;
-    int on_device;
-};
-
-int gather_core(dnagpu_ctx *ctx, const dnagpu_dna *table, const dnagpu_quals *src, const QualsLists &in, dnagpu_quals **out)
+int gather_core(dnagpu_ctx *ctx, const dnagpu_dna *table, const dnagpu_quals *src, const TakeLists &in, dnagpu_quals **out)
 {
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     PoolScope ps(ctx);
-    const u64 n = in.n;
     std::unique_ptr<dnagpu_quals> q;
-    if (n == 0) {
+    if (in.n == 0) {
         RC_TRY(column_new(ps, 0, &q));
         ps.release(q->bytes);
         *out = q.release();
         return DNAGPU_OK;
     }
     prof_begin(ctx);
-    prof_mark(ctx, "quals_lists");
-    const u64 *ids = nullptr, *first = nullptr, *len = nullptr;
-    const uint8_t *flip = nullptr;
-    RC_TRY(device_list(ctx, ps, in.ids, n, in.on_device, &ids));
-    RC_TRY(device_list(ctx, ps, in.first, n, in.on_device, &first));
-    RC_TRY(device_list(ctx, ps, in.len, n, in.on_device, &len));
-    RC_TRY(device_list(ctx, ps, in.flip, n, in.on_device, &flip));
-    u64 *seg_first = nullptr;
-    u32 *len32 = nullptr;
-    unsigned long long *res = nullptr;
-    if (ids)
-        RC_TRY(ps.alloc((size_t)n, &seg_first));
-    RC_TRY(ps.alloc((size_t)n, &len32));
-    RC_TRY(ps.alloc(2, &res));
-    prof_mark(ctx, "take_segments");
-    HIP_TRY(launch_take_segments(ids, ids ? table->seq_starts : nullptr, ids ? table->n_seqs : 0, first, len, src->n, n, seg_first,
-                                 len32, res, st));
-    u64 got[2] = {0, 0};
-    RC_TRY(read_back(ctx, got, res, sizeof got));    // (waits for the stream: the caller's host lists have been read)
-    if (got[1]) {
-        set_err(ids ? "take: a sequence id is not below the table's %llu sequences"
-                    : "gather: a segment leaves the stream of %llu bases",
-                (unsigned long long)(ids ? table->n_seqs : src->n));
-        return DNAGPU_ERR_BAD_ARG;
-    }
-    const u64 total = got[0];
-    if (total > U32_MAX64)
-        return DNAGPU_ERR_TOO_LARGE;
-    u32 *scan_tmp = nullptr;
-    u64 *starts = nullptr;
-    RC_TRY(ps.alloc((size_t)scan_tmp_words(n), &scan_tmp));
-    RC_TRY(ps.alloc((size_t)n + 1, &starts));
-    RC_TRY(column_new(ps, total, &q));
-    prof_mark(ctx, "take_starts");
-    HIP_TRY(launch_scan_u32(len32, len32, n, scan_tmp, nullptr, st));
-    HIP_TRY(launch_take_starts(len32, n, total, starts, st));
+    TakePlan plan = {};
+    RC_TRY(take_plan(ctx, ps, in, table ? table->seq_starts : nullptr, table ? table->n_seqs : 0, src->n, "quals_lists", &plan));
+    RC_TRY(column_new(ps, plan.total, &q));
+    RC_TRY(plan.queue_starts(ctx));
     prof_mark(ctx, "quals_copy");
-    HIP_TRY(launch_quals_copy(src->bytes, src->n, ids ? seg_first : first, flip, starts, n, total, q->bytes, st));
+    HIP_TRY(launch_quals_copy(src->bytes, src->n, plan.seg_first, plan.flip, plan.starts, in.n, plan.total, q->bytes, st));
     prof_mark(ctx, "end");
     HIP_TRY(hipStreamSynchronize(st));
     prof_end(ctx);
@@ -298,8 +241,8 @@ extern "C" int dnagpu_quals_from_fastq(dnagpu_ctx *ctx, const char *text, uint64
         return DNAGPU_ERR_BAD_ARG;
     if ((src_record == nullptr) != (src_offset == nullptr))
         return DNAGPU_ERR_BAD_ARG;
-    if (table->n_seqs == 0 && table->n_bases != 0)
-        return DNAGPU_ERR_BAD_ARG;                   // (no dnagpu_dna_set_sequences before)
+    if (table_without_set(table))
+        return DNAGPU_ERR_BAD_ARG;
     if (n_bytes > U32_MAX64)
         return DNAGPU_ERR_TOO_LARGE;
     dnagpu_quals *made = nullptr;
@@ -317,7 +260,7 @@ extern "C" int dnagpu_quals_gather(dnagpu_ctx *ctx, const dnagpu_quals *src, con
         return DNAGPU_ERR_BAD_ARG;
     if (n_segs > U32_MAX64)
         return DNAGPU_ERR_TOO_LARGE;
-    const QualsLists in = {nullptr, seg_first, seg_len, seg_flip, n_segs, on_device};
+    const TakeLists in = {nullptr, seg_first, seg_len, seg_flip, n_segs, on_device};
     return gather_core(ctx, nullptr, src, in, out);
     });
 }
@@ -328,8 +271,8 @@ extern "C" int dnagpu_quals_take(dnagpu_ctx *ctx, const dnagpu_dna *table, const
     return guarded([&]() -> int {
     if (!ctx || !table || !quals || !out || (n_ids && !seq_ids))
         return DNAGPU_ERR_BAD_ARG;
-    if (table->n_seqs == 0 && table->n_bases != 0)
-        return DNAGPU_ERR_BAD_ARG;                   // (no dnagpu_dna_set_sequences before)
+    if (table_without_set(table))
+        return DNAGPU_ERR_BAD_ARG;
     if (table->n_bases != quals->n)
         return DNAGPU_ERR_BAD_ARG;                   // (not this table's column)
     if (n_ids > U32_MAX64)
@@ -338,7 +281,7 @@ extern "C" int dnagpu_quals_take(dnagpu_ctx *ctx, const dnagpu_dna *table, const
         set_err("take: a sequence id is not below the table's 0 sequences");
         return DNAGPU_ERR_BAD_ARG;
     }
-    const QualsLists in = {seq_ids, nullptr, nullptr, seq_flip, n_ids, on_device};
+    const TakeLists in = {seq_ids, nullptr, nullptr, seq_flip, n_ids, on_device};
     return gather_core(ctx, table, quals, in, out);
     });
 }
@@ -431,8 +374,8 @@ extern "C" int dnagpu_quals_trim(dnagpu_ctx *ctx, const dnagpu_dna *table, const
     if (opt->cut_front > QUALS_MAX_THRESHOLD || opt->cut_tail > QUALS_MAX_THRESHOLD || opt->min_mean_q > QUALS_MAX_THRESHOLD ||
         opt->low_q > QUALS_MAX_THRESHOLD || opt->reserved)
         return DNAGPU_ERR_BAD_ARG;
-    if (table->n_seqs == 0 && table->n_bases != 0)
-        return DNAGPU_ERR_BAD_ARG;                   // (no dnagpu_dna_set_sequences before)
+    if (table_without_set(table))
+        return DNAGPU_ERR_BAD_ARG;
     if (table->n_bases != quals->n)
         return DNAGPU_ERR_BAD_ARG;                   // (not this table's column)
     if (table->n_seqs > U32_MAX64)

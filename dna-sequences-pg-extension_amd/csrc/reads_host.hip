@@ -8,25 +8,6 @@ using namespace dnagpu;
 
 namespace {
 
-void report_clear(dnagpu_reads_report *r)
-{
-    if (!r)
-        return;
-    memset(r, 0, sizeof *r);
-    r->bad_pos = ~(u64)0;
-    r->bad_record = ~(u64)0;
-}
-
-// a valid dna of 0 bases with no set: what dnagpu_dna_take makes of no segment
-int empty_table(PoolScope &ps, dnagpu_dna **out)
-{
-    std::unique_ptr<dnagpu_dna> h(new dnagpu_dna{nullptr, 0, 0, true});
-    RC_TRY(ps.alloc(1, &h->words));
-    ps.release(h->words);
-    *out = h.release();
-    return DNAGPU_OK;
-}
-
 // the words of res, the block that the read-backs bring home
 enum { R_ERROR, R_RECORDS, R_BASES, R_LIM, R_AMBIG, R_PIECES, R_DROPPED, R_SHORT, R_KEPT, R_KEPT_BASES, R_NEWLINES, R_WORDS };
 
@@ -36,62 +17,22 @@ struct Caller {
     int on_device;
 };
 
-// after an error word: the report, dnagpu_last_error() and the code
-int input_error(dnagpu_ctx *ctx, PoolScope &ps, const ReadsSweep &a, u64 n, const u32 *nl_base, u64 word, dnagpu_reads_report *report)
-{
-    const u64 pos = text_error_pos(word);
-    const u32 kind = text_error_kind(word);
-    u64 *who = nullptr, hwho[3] = {0, 0, 0};
-    RC_TRY(ps.alloc(3, &who));
-    if (a.format == TEXT_FORMAT_FASTQ)
-        HIP_TRY(launch_reads_fastq_rank(a.text, n, nl_base, pos, who, ctx->stream));
-    else
-        HIP_TRY(launch_text_rank(a.text, a.lim, a.format, a.rec_t, pos, who, ctx->stream));
-    RC_TRY(read_back(ctx, hwho, who, sizeof hwho));
-    if (report) {
-        report->bad_pos = pos;
-        report->bad_record = hwho[0];
-        report->bad_char = kind == TEXT_ERR_CHAR ? (char)hwho[1] : 0;
-    }
-    if (kind == TEXT_ERR_CHAR) {
-        set_err("Invalid character in DNA sequence: %c", (char)hwho[1]);
-        return DNAGPU_ERR_DNA_INVALID_CHAR;
-    }
-    if (kind == TEXT_ERR_EMPTY) {
-        set_err("DNA sequence cannot be empty");
-        return DNAGPU_ERR_DNA_EMPTY;
-    }
-    if (kind == TEXT_ERR_TRUNC)
-        set_err("truncated FASTQ record");
-    else if (a.format != TEXT_FORMAT_FASTQ)
-        set_err("sequence data before the first header");
-    else if (hwho[2] == 0)
-        set_err("FASTQ record does not begin with '@'");
-    else
-        set_err("FASTQ separator line does not begin with '+'");
-    return DNAGPU_ERR_BAD_ARG;
-}
-
 int from_text(dnagpu_ctx *ctx, const char *text, u64 n, int text_on_device, const dnagpu_reads_options &opt, dnagpu_dna **out,
               const Caller &c, dnagpu_reads_report *report)
 {
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    PoolScope ps(ctx);
+    NewTable t(ctx);
+    PoolScope &ps = t.ps;
     if (n == 0)
-        return empty_table(ps, out);
+        return t.empty(out);
     const int format = opt.format;
     const bool more = (opt.flags & DNAGPU_READS_MORE) != 0, split = opt.ambiguous == READS_AMBIG_SPLIT;
     const bool fasta = format == TEXT_FORMAT_FASTA, fastq = format == TEXT_FORMAT_FASTQ;
     prof_begin(ctx);
     prof_mark(ctx, "reads_stage");
-    const unsigned char *dtext = reinterpret_cast<const unsigned char *>(text);
-    if (!text_on_device) {
-        unsigned char *stage = nullptr;
-        RC_TRY(ps.alloc((size_t)n, &stage));
-        HIP_TRY(hipMemcpyAsync(stage, text, (size_t)n, hipMemcpyHostToDevice, st));
-        dtext = stage;
-    }
+    const unsigned char *dtext = nullptr;
+    RC_TRY(device_list(ctx, ps, reinterpret_cast<const unsigned char *>(text), n, text_on_device, &dtext));
     const u32 nt = (u32)text_tiles(n);
     u64 *res = nullptr;
     RC_TRY(ps.alloc(R_WORDS, &res));
@@ -106,7 +47,7 @@ int from_text(dnagpu_ctx *ctx, const char *text, u64 n, int text_on_device, cons
     a.fold = (opt.flags & DNAGPU_READS_FOLD_CASE) != 0;
     a.n_tiles = nt;
     a.res = res;
-    u32 *scan_tmp = nullptr, *last_header = nullptr, *seq_before_t = nullptr, *nl_base = nullptr;
+    u32 *scan_tmp = nullptr, *nl_base = nullptr;
     RC_TRY(ps.alloc((size_t)nt, &a.keep_t));
     RC_TRY(ps.alloc((size_t)nt, &a.rec_t));
     RC_TRY(ps.alloc((size_t)scan_tmp_words(nt), &scan_tmp));
@@ -126,29 +67,18 @@ int from_text(dnagpu_ctx *ctx, const char *text, u64 n, int text_on_device, cons
         prof_mark(ctx, "text_cut");
         HIP_TRY(launch_text_cut(dtext, n, format, res + R_LIM, st));
     }
-    TextSweep fa = {};                               // FASTA: the words launch_text_finish reads
+    FastaTiles tiles;                                // FASTA: the words launch_text_finish reads
     if (fasta) {
-        u32 *last_start = nullptr, *in_state = nullptr, *header_before = nullptr;
-        RC_TRY(ps.alloc((size_t)nt, &last_start));
-        RC_TRY(ps.alloc((size_t)nt, &last_header));
-        RC_TRY(ps.alloc((size_t)nt, &in_state));
-        RC_TRY(ps.alloc((size_t)nt, &header_before));
-        RC_TRY(ps.alloc((size_t)nt, &a.last_seq));
-        RC_TRY(ps.alloc((size_t)nt, &a.first_header));
-        RC_TRY(ps.alloc((size_t)nt, &a.seq_before));
-        RC_TRY(ps.alloc((size_t)nt, &seq_before_t));
-        prof_mark(ctx, "text_heads");
-        HIP_TRY(launch_text_heads(dtext, a.lim, nt, last_start, last_header, st));
-        HIP_TRY(launch_text_max_scan(last_start, in_state, nt, st));
-        HIP_TRY(launch_text_max_scan(last_header, header_before, nt, st));
-        a.in_state = in_state;
-        a.header_before = header_before;
-        fa.header_before = header_before;
-        fa.last_seq = a.last_seq;
-        fa.first_header = a.first_header;
-        fa.seq_before = a.seq_before;
-        fa.n_tiles = nt;
-        fa.res = res;
+        tiles.sw.text = dtext;
+        tiles.sw.lim = a.lim;
+        tiles.sw.n_tiles = nt;
+        tiles.sw.res = res;
+        RC_TRY(tiles.before_sweep(ctx, ps));
+        a.in_state = tiles.sw.in_state;
+        a.header_before = tiles.sw.header_before;
+        a.last_seq = tiles.sw.last_seq;
+        a.first_header = tiles.sw.first_header;
+        a.seq_before = tiles.sw.seq_before;
     }
     if (split) {
         u32 *kb = nullptr, *bb = nullptr;
@@ -167,10 +97,8 @@ int from_text(dnagpu_ctx *ctx, const char *text, u64 n, int text_on_device, cons
     prof_mark(ctx, "reads_sweep");
     HIP_TRY(launch_reads_sweep(a, st));
     prof_mark(ctx, "reads_scan");
-    if (fasta) {
-        HIP_TRY(launch_text_max_scan(a.last_seq, seq_before_t, nt, st));
-        HIP_TRY(launch_text_finish(fa, last_header, seq_before_t, st));
-    }
+    if (fasta)
+        RC_TRY(tiles.after_sweep(st));
     if (split) {
         HIP_TRY(launch_text_max_scan(a.last_keep, const_cast<u32 *>(a.keep_before_t), nt, st));
         HIP_TRY(launch_text_max_scan(a.last_brk, const_cast<u32 *>(a.brk_before_t), nt, st));
@@ -184,7 +112,7 @@ int from_text(dnagpu_ctx *ctx, const char *text, u64 n, int text_on_device, cons
     u64 got[R_PIECES + 1] = {};
     RC_TRY(read_back(ctx, got, res, sizeof got));    // (waits for the stream: a host text has been read)
     if (got[R_ERROR] != TEXT_NO_ERROR)
-        return input_error(ctx, ps, a, n, nl_base, got[R_ERROR], report);
+        return text_input_error(ctx, ps, TextErrorIn{dtext, n, a.lim, format, a.rec_t, nl_base}, got[R_ERROR], report);
     const u64 records = got[R_RECORDS], all_bases = got[R_BASES], all_seqs = split ? got[R_PIECES] : records;
     if (report) {
         report->records = records;
@@ -192,14 +120,13 @@ int from_text(dnagpu_ctx *ctx, const char *text, u64 n, int text_on_device, cons
         report->ambiguous = got[R_AMBIG];
     }
     if (records == 0)                                // (then there is no base either: every base belongs to a record)
-        return empty_table(ps, out);
+        return t.empty(out);
 
     // ---- the second sweep: every sequence, before any is left out
     const bool filter = all_seqs && ((opt.ambiguous == READS_AMBIG_DROP && got[R_AMBIG]) || opt.min_bases > 1);
     const bool want_src = c.seq_cap != 0;
-    std::unique_ptr<dnagpu_dna> h(new dnagpu_dna{nullptr, 0, 0, true});
     const u64 n_pos = c.record_pos ? std::min(records, c.record_cap) : 0;
-    u64 *pos_dev = text_on_device ? c.record_pos : nullptr;
+    OutCols<1> pos;
     u64 *src_record = nullptr, *src_offset = nullptr;
     ReadsPack p = {};
     p.n_bases = all_bases;
@@ -207,8 +134,7 @@ int from_text(dnagpu_ctx *ctx, const char *text, u64 n, int text_on_device, cons
     p.n_records = records;
     RC_TRY(ps.alloc((size_t)all_seqs + 1, &p.starts));
     RC_TRY(ps.alloc((size_t)std::max<u64>(text_words(all_bases), 1), &p.words));
-    if (n_pos && !text_on_device)
-        RC_TRY(ps.alloc((size_t)n_pos, &pos_dev));
+    RC_TRY(pos.init(ctx, ps, {c.record_pos}, n_pos, text_on_device));
     if (split || want_src || filter) {
         RC_TRY(ps.alloc((size_t)std::max<u64>(all_seqs, 1), &src_record));
         RC_TRY(ps.alloc((size_t)std::max<u64>(all_seqs, 1), &src_offset));
@@ -219,7 +145,7 @@ int from_text(dnagpu_ctx *ctx, const char *text, u64 n, int text_on_device, cons
         RC_TRY(ps.alloc((size_t)records, &p.rec_amb));
         HIP_TRY(hipMemsetAsync(p.rec_amb, 0, (size_t)records * sizeof(u32), st));
     }
-    p.record_pos = n_pos ? pos_dev : nullptr;
+    p.record_pos = n_pos ? pos.dev(0) : nullptr;
     p.record_cap = n_pos;
     p.src_record = src_record;
     p.src_offset = src_offset;
@@ -270,9 +196,8 @@ int from_text(dnagpu_ctx *ctx, const char *text, u64 n, int text_on_device, cons
         }
     }
 
-    // ---- the caller's arrays, the marks, the hand-over
-    if (n_pos && !text_on_device)
-        HIP_TRY(hipMemcpyAsync(c.record_pos, pos_dev, (size_t)n_pos * 8, hipMemcpyDeviceToHost, st));
+    // ---- the caller's arrays, the marks, the hand-over.  (src_record / src_offset keep their own copies: their count is not
+    // record_pos's, and copy_cols would wait for the stream a second time.)
     const u64 n_src = std::min(n_seqs, c.seq_cap);
     const hipMemcpyKind kind = text_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (n_src && c.src_record)
@@ -284,28 +209,18 @@ int from_text(dnagpu_ctx *ctx, const char *text, u64 n, int text_on_device, cons
         report->bases = bases;
     }
     if (n_seqs == 0) {
-        HIP_TRY(hipStreamSynchronize(st));
+        RC_TRY(pos.finish());
         prof_mark(ctx, "end");
         prof_end(ctx);
-        return empty_table(ps, out);
+        return t.empty(out);
     }
-    const u64 n_mark_words = text_mark_words(bases);
-    RC_TRY(ps.alloc((size_t)n_mark_words, &h->seq_marks));
+    RC_TRY(t.alloc(n_seqs, bases, starts, words));   // (the packed or the gathered blocks are the result's)
     prof_mark(ctx, "reads_marks");
-    HIP_TRY(launch_batch_marks(starts, n_seqs, h->seq_marks, n_mark_words, st));
+    RC_TRY(t.queue_marks(st));
     prof_mark(ctx, "end");
-    HIP_TRY(hipStreamSynchronize(st));
+    RC_TRY(pos.finish());                            // (the call's one wait at the end)
     prof_end(ctx);
-    h->seq_starts = starts;
-    h->words = words;
-    ps.release(h->seq_starts);
-    ps.release(h->seq_marks);
-    ps.release(h->words);
-    h->n_words = text_words(bases);
-    h->n_bases = bases;
-    h->n_seqs = n_seqs;
-    h->n_mark_words = n_mark_words;
-    *out = h.release();
+    t.hand_over(out);
     return DNAGPU_OK;
 }
 

@@ -250,8 +250,8 @@ extern "C" int dnagpu_table_classes(dnagpu_ctx *ctx, const dnagpu_dna *table, dn
     return guarded([&]() -> int {
     if (!ctx || !table || !out)
         return DNAGPU_ERR_BAD_ARG;
-    if (table->n_seqs == 0 && table->n_bases != 0)
-        return DNAGPU_ERR_BAD_ARG;                         // (no dnagpu_dna_set_sequences before)
+    if (table_without_set(table))
+        return DNAGPU_ERR_BAD_ARG;
     if (table->n_seqs > U32_MAX64)
         return DNAGPU_ERR_TOO_LARGE;                       // (32-bit ids, and all-ones is "no match")
     std::unique_ptr<dnagpu_seq_classes> c(new dnagpu_seq_classes());
@@ -325,8 +325,8 @@ extern "C" int dnagpu_table_match(dnagpu_ctx *ctx, const dnagpu_seq_classes *bui
         return DNAGPU_ERR_BAD_ARG;
     if (seq_count > U32_MAX64)
         return DNAGPU_ERR_TOO_LARGE;                       // (part of the window rule, as in dnagpu_table_profile)
-    if (probe->n_seqs == 0 && probe->n_bases != 0)
-        return DNAGPU_ERR_BAD_ARG;                         // (no dnagpu_dna_set_sequences before)
+    if (table_without_set(probe))
+        return DNAGPU_ERR_BAD_ARG;
     if (seq_count == 0) {
         if (n_matched)
             *n_matched = 0;

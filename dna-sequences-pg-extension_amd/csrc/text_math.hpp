@@ -17,7 +17,6 @@ constexpr u32 TEXT_TILE_BYTES = TEXT_THREADS * TEXT_CHUNK;
 
 __host__ __device__ __forceinline__ u64 text_tiles(u64 n_bytes) { return (n_bytes + TEXT_TILE_BYTES - 1) / TEXT_TILE_BYTES; }
 __host__ __device__ __forceinline__ u64 text_words(u64 n_bases) { return (n_bases + 31) / 32; }
-__host__ __device__ __forceinline__ u64 text_mark_words(u64 n_bases) { return n_bases / 32 + 3; }     // (dnagpu_dna_take's)
 
 // 'A','T','C','G' -> 0,1,2,3 (dna.c:120-123); anything else -> 4
 __host__ __device__ __forceinline__ u32 base_code(u32 c)

@@ -188,6 +188,30 @@ def check_gather(ctx, d, text, first, length, flip, what):
     out.free()
 
 
+def phase_names_of(c, call):
+    """the phase names dnagpu_last_phase_times reports after one call with profiling on (the call's result is freed)"""
+    c.set_profiling(True)
+    try:
+        call().free()
+        return [name for name, _ in c.last_phase_times()]
+    finally:
+        c.set_profiling(False)
+
+
+TAKE_IDS, TAKE_FLIP = [7, 0, 11, 3, 7], [0, 0, 1, 0, 0]           # (test_read_quals.py takes the column by the same lists)
+TAKE_PHASE_NAMES = ["take_lists", "take_segments", "take_starts", "take_marks", "take_copy"]   # (profiles and tools key on these names)
+
+
+@pytest.mark.gpu
+def test_phase_names_of_a_take(ctx):
+    """dnagpu_dna_take of five of twelve sequences by host ids, one flipped"""
+    d = resident(ctx, [text_of(SEED + 130 + i, 20 + 9 * i) for i in range(12)])
+    try:
+        assert phase_names_of(ctx, lambda: ctx.dna_take(d, TAKE_IDS, TAKE_FLIP)) == TAKE_PHASE_NAMES
+    finally:
+        d.free()
+
+
 @pytest.mark.gpu
 def test_take_identity_and_order(ctx, dbg):
     """70 sequences, sequence i of i bases (so an empty one is among them): all ids in order reproduce the table -- words,

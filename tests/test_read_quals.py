@@ -18,7 +18,7 @@ import quals_model as Q
 import reads_model
 from __graft_entry__ import ROOT, load_package
 from test_device_io import Arena
-from test_dna_take import check_table, encode_table
+from test_dna_take import TAKE_FLIP, TAKE_IDS, check_table, encode_table, phase_names_of
 
 BAD_ARG, TOO_LARGE = 5, 6
 FASTQ = 3
@@ -595,10 +595,44 @@ def test_gather_and_take(ctx, dbg, pkg):
                 ctx.quals_take(d, other, [0])
             assert ei.value.code == BAD_ARG
         assert ctx.device_bytes() == before
+        refused = []             # the segment plan's two errors: one code and one text for the table and for its column
+        for call in (lambda: ctx.dna_take(d, [0, n]), lambda: ctx.quals_take(d, q, [0, n]),
+                     lambda: ctx.dna_gather(d, [3, total - 4], [2, 5]), lambda: ctx.quals_gather(q, [3, total - 4], [2, 5])):
+            with pytest.raises(pkg.DnaGpuError) as ei:
+                call()
+            refused.append((ei.value.code, pkg.strerror(ei.value.code), pkg.lib().dnagpu_last_error().decode()))
+        assert refused[0] == refused[1] == (BAD_ARG, pkg.strerror(BAD_ARG), f"take: a sequence id is not below the table's {n} sequences")
+        assert refused[2] == refused[3] == (BAD_ARG, pkg.strerror(BAD_ARG), f"gather: a segment leaves the stream of {total} bases")
     finally:
         ar.free()
         q.free()
         d.free()
+
+
+# (profiles and tools key on these names)
+QUALS_PHASE_NAMES = {
+    "take": ["quals_lists", "take_segments", "take_starts", "quals_copy"],
+    "from_fastq": ["quals_stage", "quals_newlines", "quals_lines", "quals_copy"],
+}
+
+
+@pytest.mark.gpu
+def test_phase_names_of_the_column(ctx, pkg):
+    """dnagpu_quals_take by the lists of test_dna_take's phase test, over twelve reads; dnagpu_quals_from_fastq over a FASTQ
+    text of three tiles and its table"""
+    rng = np.random.default_rng(SEED + 30)
+    T = pkg.text_geometry()
+    d, q, _, _ = load(ctx, pkg, fastq(*random_reads(rng, [20 + 9 * i for i in range(12)])))
+    text = fastq(*random_reads(rng, [150] * (3 * T // 312)))
+    assert 2 * T < len(text) <= 3 * T
+    big, rep = ctx.reads_from_text(text, pkg.TEXT_FASTQ, source=True)
+    try:
+        assert phase_names_of(ctx, lambda: ctx.quals_take(d, q, TAKE_IDS, TAKE_FLIP)) == QUALS_PHASE_NAMES["take"]
+        names = phase_names_of(ctx, lambda: ctx.quals_from_fastq(text, big, rep.src_record, rep.src_offset)[0])
+        assert names == QUALS_PHASE_NAMES["from_fastq"]
+    finally:
+        for o in (d, q, big):
+            o.free()
 
 
 def trim_table(ctx, values):

@@ -20,8 +20,8 @@ import reads_model as R
 import text_model as M
 from __graft_entry__ import ROOT, load_package
 from test_device_io import Arena
-from test_dna_take import check_table
-from test_table_from_text import error_cases, fasta_text, lines_text, random_bases
+from test_dna_take import check_table, phase_names_of
+from test_table_from_text import check_load, error_cases, fasta_text, lines_text, random_bases
 
 BAD_ARG, TOO_LARGE, DNA_EMPTY, DNA_INVALID_CHAR = 5, 6, 11, 12
 LINES, FASTA, FASTQ = R.LINES, R.FASTA, R.FASTQ
@@ -632,3 +632,73 @@ def test_the_split_result_is_a_table(ctx, dbg, pkg, T):
     check_table(t, [want.sequences[last], want.sequences[0], want.sequences[last // 2]])
     t.free()
     d.free()
+
+
+# (profiles and tools key on these names)
+READS_PHASE_NAMES = {
+    "fastq": ["reads_stage", "reads_newlines", "reads_sweep", "reads_scan", "reads_pack", "reads_marks"],
+    "fasta, drop": ["reads_stage", "text_heads", "reads_sweep", "reads_scan", "reads_pack", "reads_select", "reads_take", "reads_marks"],
+}
+
+
+@pytest.mark.gpu
+def test_phase_names_of_the_reads_loader(ctx, pkg, T):
+    """FASTQ of three tiles under ERROR; FASTA of three tiles with a few N under DROP and a min_bases that leaves out some
+    sequences but not all"""
+    rng = np.random.default_rng(SEED + 60)
+    fq = fastq_exact(rng, 3 * T - 7)
+    fa = masked_fasta(rng, [int(n) for n in rng.integers(20, 400, 3 * T // 235)], run=(1, 3), share=0.004, lower=0)
+    want = R.parse(fa, Opt(FASTA, DROP, min_bases=100))
+    assert 2 * T < len(fa) <= 3 * T and want.dropped and want.short_out and want.sequences
+    assert phase_names_of(ctx, lambda: ctx.reads_from_text(fq, FASTQ)[0]) == READS_PHASE_NAMES["fastq"]
+    assert phase_names_of(ctx, lambda: ctx.reads_from_text(fa, FASTA, DROP, min_bases=100)[0]) == READS_PHASE_NAMES["fasta, drop"]
+
+
+@pytest.mark.gpu
+def test_the_empty_table_of_every_source(ctx, dbg, pkg):
+    """a take of no id, a text of 0 bytes, a header and nothing else with MORE, and reads of which DROP and min_bases leave none: one and the
+    same table of 0 bases and no set"""
+    rng = np.random.default_rng(SEED + 61)
+    src, _ = ctx.table_from_text(lines_text(rng, [30, 40]))
+    dropped, rep = ctx.reads_from_text(b">a\nATNG\n>b\nAT\n>c\nANA\n", FASTA, DROP, min_bases=3)
+    assert (rep.records, rep.sequences, rep.dropped, rep.short_out) == (3, 0, 2, 1)
+    made = {"take of no id": ctx.dna_take(src, []), "text of 0 bytes": ctx.table_from_text(b"")[0],
+            "reads of 0 bytes": ctx.reads_from_text(b"", FASTA)[0],
+            "a header only, more": ctx.table_from_text(b">a header\n", FASTA, more=True)[0],
+            "a header only, more, reads": ctx.reads_from_text(b">a header\n", FASTA, more=True)[0], "nothing stays": dropped}
+    try:
+        for what, d in made.items():
+            assert (d.n_bases, d.n_sequences, len(d.sequence_starts()), d.download().tobytes()) == \
+                (0, 0, 0, made["take of no id"].download().tobytes()), what
+    finally:
+        for d in list(made.values()) + [src]:
+            d.free()
+
+
+@pytest.mark.gpu
+def test_record_pos_stops_at_the_cap(ctx, dbg, pkg, T, arena):
+    """record_pos with a cap below and above the record count, from both loaders, in host memory (a longer array of a
+    sentinel: nothing behind min(cap, records) is written) and in device memory (the arena's check)"""
+    L = pkg.lib()
+    rng = np.random.default_rng(SEED + 62)
+    data = fasta_text(rng, [int(n) for n in rng.integers(100, 900, 40)], 70)
+    want = M.parse(data, FASTA)
+    records, sentinel = len(want.records), 0xA1B2C3D4E5F60718
+    assert want.error is None and records == 40 and len(data) > 2 * T
+    buf = C.create_string_buffer(data, len(data))
+    opt = pkg.binding._ReadsOptionsC(FASTA, ERROR, 0, 0, 0)
+    for cap in (records - 3, records + 3):
+        for loader in ("table", "reads"):
+            pos, out = np.full(records + 8, sentinel, dtype=np.uint64), C.c_void_p()
+            if loader == "table":
+                rc = L.dnagpu_table_from_text(ctx.h, buf, len(data), 0, FASTA, 0, C.byref(out), pos.ctypes.data, cap, None)
+            else:
+                rc = L.dnagpu_reads_from_text(ctx.h, buf, len(data), 0, C.byref(opt), C.byref(out), pos.ctypes.data, cap, None, None, 0,
+                                              None)
+            assert rc == 0, (loader, cap)
+            pkg.binding.Dna(ctx, out).free()
+            n = min(cap, records)
+            assert pos[:n].tolist() == want.pos[:n] and (pos[n:] == sentinel).all(), (loader, cap)
+        check_load(ctx, pkg, data, FASTA, cap=cap, dev=(arena, 3), what=f"cap={cap}")
+        check_reads(ctx, pkg, data, Opt(FASTA), dev=(arena, 3), what=f"cap={cap}", caps=(cap, 0))
+        check_reads(ctx, pkg, data, Opt(FASTA), dev=(arena, 3), what=f"cap={cap}", caps=(cap, cap))

@@ -17,7 +17,7 @@ import oracle as orc
 import text_model as M
 from __graft_entry__ import ROOT, load_package
 from test_device_io import Arena
-from test_dna_take import check_table
+from test_dna_take import check_table, phase_names_of
 
 BAD_ARG, TOO_LARGE, DNA_EMPTY, DNA_INVALID_CHAR = 5, 6, 11, 12
 LINES, FASTA = M.LINES, M.FASTA
@@ -362,6 +362,10 @@ def error_cases(T):
     cases.append(("an empty record across tiles", far, FASTA, (DNA_EMPTY, 6, 1, b"")))
     cases.append(("an empty record before an invalid byte", b">x\n>y\nANA\n", FASTA, (DNA_EMPTY, 0, 0, b"")))
     cases.append(("'>' inside a sequence line", b">x\nAT>G\n", FASTA, (DNA_INVALID_CHAR, 5, 0, b">")))
+    body = b">x\nAT\n>y\n" + b"\n".join(b(70) for _ in range(2 * T // 71 + 2)) + b"\n>z\nA\n"
+    at = T + 300 - (body[T + 300:T + 301] == b"\n")
+    cases.append((f"an invalid byte in the second tile of a record, at {at}", body[:at] + b"N" + body[at + 1:], FASTA,
+                  (DNA_INVALID_CHAR, at, 1, b"N")))
     return cases
 
 
@@ -466,3 +470,23 @@ def test_the_table_is_usable(ctx, dbg, pkg):
         assert row.n_bases == len(text) and [int(x) for x in row.download()] == [word], text
         row.free()
     d.free()
+
+
+# (profiles and tools key on these names)
+TEXT_PHASE_NAMES = {
+    "lines": ["text_stage", "text_sweep", "text_scan", "text_pack", "text_marks"],
+    "fasta, more": ["text_stage", "text_cut", "text_heads", "text_sweep", "text_scan", "text_pack", "text_marks"],
+}
+
+
+@pytest.mark.gpu
+def test_phase_names_of_the_text_loader(ctx, T):
+    """a host text of three tiles as LINES; FASTA with MORE over records whose header and sequence lie in different tiles"""
+    rng = np.random.default_rng(SEED + 60)
+    lines = lines_text(rng, [150] * (3 * T // 151))
+    assert 2 * T < len(lines) <= 3 * T
+    fasta = b"".join(b">" + b"h" * T + b"\n" + random_bases(rng, 2 * T + r) + b"\n" for r in range(3))
+    want = M.parse(fasta, FASTA, True)
+    assert want.error is None and len(want.records) == 2 and all(p // T != (p + T + 2) // T for p in want.pos)
+    assert phase_names_of(ctx, lambda: ctx.table_from_text(lines, LINES)[0]) == TEXT_PHASE_NAMES["lines"]
+    assert phase_names_of(ctx, lambda: ctx.table_from_text(fasta, FASTA, more=True)[0]) == TEXT_PHASE_NAMES["fasta, more"]
