@@ -1,5 +1,5 @@
 /*
- * row_batch.h -- the batch every streaming object of dna_glue.c collects its rows in: the rows back to back as ONE packed
+ * row_batch.h -- the batch every streaming object of the glue (glue_*.c) collects its rows in: the rows back to back as ONE packed
  * stream (2 bits per base, base 0 at bit 0 of word 0) with the base at which every row starts.  Plain C11 without the GPU
  * library: a row is (bits, length), and tests/host/row_batch_check.c runs all of this on the host.
  */
