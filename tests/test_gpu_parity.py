@@ -229,6 +229,8 @@ def test_filters_survey_positions(ctx, pkg, survey_vectors):
         d.free()
 
 
+# PATTERNS_21[2] holds a 'U', which matches no base: the host answers zero rows and no kernel runs -- a host-side zero-row
+# case, not a test of the letters on the device (those: tests/test_operator_semantics.py)
 PATTERNS_21 = ["NNNNNNNNNNWSNNNNNNNNN", "RYNNNNNNNNNNNNNNNNNNN", "ATCGUWSMKRYBDHVNNNNNN"[:21],
                "BDHVBDHVBDHVBDHVBDHVB", "NNNNNNNNNNNNNNNNNNNNN", "ANNNNNNNNNNNNNNNNNNNT"]
 

@@ -15,14 +15,13 @@ import pytest
 
 import oracle as orc
 from __graft_entry__ import ROOT, load_package
+from operator_model import IUPAC                  # letter -> 4-bit set of codes: the suite's one copy
 
 T = 2048                                          # INDEX_SORT_TILE of csrc/kernels.hpp: keys per workgroup of the sort
 MAX_RANGES = 1024                                 # DNAGPU_INDEX_MAX_RANGES
 INVALID_K, LEN_MISMATCH, PREFIX_TOO_LONG, QKMER_INVALID, BAD_ARG, TOO_LARGE = 1, 2, 3, 4, 5, 6
 SENTINEL = np.uint64(0xC3C3C3C3C3C3C3C3)
 N_SCAN = 200_003
-IUPAC = {"A": 1, "T": 2, "C": 4, "G": 8, "U": 0, "W": 3, "S": 12, "M": 5, "K": 10, "R": 9, "Y": 6, "B": 14, "D": 11, "H": 7,
-         "V": 13, "N": 15}
 
 
 @pytest.fixture(scope="module")
