@@ -150,6 +150,21 @@ class QualsReport:
     bad_char: bytes = b""
 
 
+class _NamesReportC(C.Structure):
+    _fields_ = [("bad_pos", C.c_uint64), ("bad_record", C.c_uint64), ("bad_char", C.c_char), ("reserved", C.c_char * 7)]
+
+
+@dataclasses.dataclass
+class NamesReport:
+    """dnagpu_names_report.  bad_pos / bad_record are None where the C struct holds ~0, bad_char is b"" where it holds 0"""
+    bad_pos: object = None
+    bad_record: object = None
+    bad_char: bytes = b""
+
+
+NAMES_FIRST_WORD = 1                  # dnagpu_names_from_text: a name ends before its first blank or tab
+
+
 class _QualsTrimOptionsC(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("cut_front", "cut_tail", "min_mean_q", "low_q", "low_num", "low_den")] + \
                [("min_bases", C.c_uint64), ("reserved", C.c_uint64)]
@@ -354,6 +369,20 @@ def lib():
     L.dnagpu_quals_trim.argtypes = [vp, vp, vp, C.POINTER(_QualsTrimOptionsC), vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_int,
                                     C.POINTER(_QualsTrimReportC)]
     L.dnagpu_quals_geometry.argtypes = [u64p, u64p, u64p]
+    L.dnagpu_names_upload.argtypes = [vp, vp, vp, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(_NamesReportC)]
+    L.dnagpu_names_sequences.argtypes = [vp]
+    L.dnagpu_names_sequences.restype = C.c_uint64
+    L.dnagpu_names_bytes.argtypes = [vp]
+    L.dnagpu_names_bytes.restype = C.c_uint64
+    L.dnagpu_names_offsets.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_int]
+    L.dnagpu_names_read.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_int]
+    L.dnagpu_names_free.argtypes = [vp, vp]
+    L.dnagpu_names_free.restype = None
+    L.dnagpu_names_from_text.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_uint, vp, C.c_uint64, vp, C.c_uint64,
+                                         C.POINTER(vp), C.POINTER(_NamesReportC)]
+    L.dnagpu_names_take.argtypes = [vp, vp, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
+    L.dnagpu_table_to_text_named.argtypes = [vp, vp, vp, C.POINTER(_TextOutOptionsC), C.POINTER(vp)]
+    L.dnagpu_names_geometry.argtypes = [u64p, u64p, u64p]
     L.dnagpu_dna_equals.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]
     L.dnagpu_table_classes.argtypes = [vp, vp, C.POINTER(vp)]
     for f in ("sequences", "distinct"):
@@ -489,6 +518,14 @@ def quals_copy_geometry():
     c, t, s = C.c_uint64(), C.c_uint64(), C.c_uint64()
     _chk(lib().dnagpu_quals_copy_geometry(C.byref(c), C.byref(t), C.byref(s)))
     return c.value, t.value, s.value
+
+
+def names_geometry():
+    """(chunk_bytes, tile_bytes, group_tiles): the bytes of text one lane and one workgroup of dnagpu_names_from_text's sweep
+    mark, and the tiles whose suffix minimum one workgroup forms (needs no device)"""
+    c, t, g = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _chk(lib().dnagpu_names_geometry(C.byref(c), C.byref(t), C.byref(g)))
+    return c.value, t.value, g.value
 
 
 def quals_geometry():
@@ -861,6 +898,7 @@ class TextImage:
 
     def __init__(self, ctx, handle, table):
         self.ctx, self.h, self.table = ctx, handle, table
+        self.names = None                   # table_to_text_named: the borrowed Names column
 
     @property
     def bytes(self):
@@ -912,6 +950,60 @@ class TextImage:
             lib().dnagpu_text_image_free(self.ctx.h, self.h)
             self.h = None
             self.table = None
+            self.names = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
+class Names:
+    """dnagpu_names: the names column of a resident table, one byte string per sequence; no byte is a line terminator"""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+
+    @property
+    def n_sequences(self):
+        return int(lib().dnagpu_names_sequences(self.h))
+
+    @property
+    def n_bytes(self):
+        return int(lib().dnagpu_names_bytes(self.h))
+
+    def offsets(self, first=0, count=None):
+        """entries [first, first + count) of the n_sequences + 1 offsets -> uint64 array"""
+        if count is None:
+            count = self.n_sequences + 1 - first
+        out = np.empty(max(count, 1), dtype=np.uint64)
+        _chk(lib().dnagpu_names_offsets(self.ctx.h, self.h, first, count, out.ctypes.data, 0))
+        return out[:count]
+
+    def offsets_device(self, first, count, dev_ptr):
+        _chk(lib().dnagpu_names_offsets(self.ctx.h, self.h, first, count, dev_ptr, 1))
+
+    def read(self, first=0, count=None):
+        """bytes [first, first + count) of the column (count=None: all from first on) -> bytes"""
+        if count is None:
+            count = self.n_bytes - first
+        buf = C.create_string_buffer(max(count, 1))
+        _chk(lib().dnagpu_names_read(self.ctx.h, self.h, first, count, buf, 0))
+        return buf.raw[:count]
+
+    def read_device(self, first, count, dev_ptr):
+        _chk(lib().dnagpu_names_read(self.ctx.h, self.h, first, count, dev_ptr, 1))
+
+    def download(self):
+        """the column as a list of bytes, one per sequence"""
+        off, b = self.offsets(), self.read()
+        return [b[int(off[i]):int(off[i + 1])] for i in range(self.n_sequences)]
+
+    def free(self):
+        if self.h:
+            lib().dnagpu_names_free(self.ctx.h, self.h)
+            self.h = None
 
     def __enter__(self):
         return self
@@ -1454,6 +1546,82 @@ class Context:
         h = C.c_void_p()
         _chk(lib().dnagpu_table_to_text(self.h, dna.h, C.byref(opt), C.byref(h)))
         return TextImage(self, h, dna)
+
+    def table_to_text_named(self, dna, names, format, *, crlf=False, line_width=0, quality=b"I"):
+        """table_to_text where the name of sequence s is string s of the Names column (dnagpu_table_to_text_named): FASTA or
+        FASTQ.  The image borrows the column as it borrows the table"""
+        opt = _TextOutOptionsC(format=format, flags=TEXT_OUT_CRLF if crlf else 0, line_width=line_width, prefix_len=0,
+                               name_prefix=None, name_base=0, quality=bytes(quality)[:1] if quality else b"\0")
+        h = C.c_void_p()
+        _chk(lib().dnagpu_table_to_text_named(self.h, dna.h, names.h, C.byref(opt), C.byref(h)))
+        img = TextImage(self, h, dna)
+        img.names = names
+        return img
+
+    @staticmethod
+    def _names_result(rc, rep):
+        none = lambda v: None if v == U64_MAX else int(v)
+        report = NamesReport(none(rep.bad_pos), none(rep.bad_record), rep.bad_char if rep.bad_char != b"\0" else b"")
+        if rc != OK:
+            e = DnaGpuError(rc)
+            e.report = report
+            raise e
+        return report
+
+    def names_upload(self, names):
+        """a names column from a list of byte strings -> Names; a CR or LF raises DnaGpuError with the NamesReport as .report
+        (dnagpu_names_upload)"""
+        names = [bytes(x) for x in names]
+        off = np.zeros(len(names) + 1, dtype=np.uint64)
+        if names:
+            off[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64)
+        return self.names_upload_raw(b"".join(names), off, len(names))
+
+    def names_upload_raw(self, data, offsets, n):
+        """the same from the bytes and the n + 1 uint64 offsets as they are (the offsets are checked by the library)"""
+        b = bytes(data)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        h, rep = C.c_void_p(), _NamesReportC()
+        rc = lib().dnagpu_names_upload(self.h, b if b else None, off.ctypes.data if off.size else None, n, 0, C.byref(h), C.byref(rep))
+        self._names_result(rc, rep)
+        return Names(self, h)
+
+    def names_upload_device(self, dev_bytes, dev_offsets, n):
+        h, rep = C.c_void_p(), _NamesReportC()
+        rc = lib().dnagpu_names_upload(self.h, dev_bytes, dev_offsets, n, 1, C.byref(h), C.byref(rep))
+        self._names_result(rc, rep)
+        return Names(self, h)
+
+    def names_from_text(self, data, format, record_pos, src_record=None, first_word=False):
+        """the names of the table that reads_from_text made from the bytes `data` -> Names; record_pos / src_record: what the
+        loader reported (src_record None: sequence s is record s).  A CR inside a name raises DnaGpuError with the
+        NamesReport as .report (dnagpu_names_from_text)"""
+        b = bytes(data)
+        pos = np.ascontiguousarray(record_pos, dtype=np.uint64)
+        rec = None if src_record is None else np.ascontiguousarray(src_record, dtype=np.uint64)
+        ptr = lambda a: None if a is None or not a.size else a.ctypes.data
+        return self.names_from_text_device(b if b else None, len(b), format, ptr(pos), pos.size, ptr(rec),
+                                           pos.size if rec is None else rec.size, first_word=first_word, on_device=0)
+
+    def names_from_text_device(self, ptr, n_bytes, format, dev_record_pos, n_records, dev_src_record, n_seqs, first_word=False,
+                               on_device=1):
+        """the same from n_bytes of device memory at any byte alignment; the two arrays in device memory"""
+        h, rep = C.c_void_p(), _NamesReportC()
+        rc = lib().dnagpu_names_from_text(self.h, ptr, n_bytes, on_device, format, NAMES_FIRST_WORD if first_word else 0,
+                                          dev_record_pos, n_records, dev_src_record, n_seqs, C.byref(h), C.byref(rep))
+        self._names_result(rc, rep)
+        return Names(self, h)
+
+    def names_take(self, names, ids, on_device=False):
+        """the names of dna_take(table, ids): string i of the result is string ids[i] of names -> Names; on_device: ids =
+        (dev_ids, n)"""
+        h = C.c_void_p()
+        if on_device:
+            _chk(lib().dnagpu_names_take(self.h, names.h, ids[0], ids[1], 1, C.byref(h)))
+            return Names(self, h)
+        a = np.ascontiguousarray(ids, dtype=np.uint64)
+        _chk(lib().dnagpu_names_take(self.h, names.h, a.ctypes.data if a.size else None, a.size, 0, C.byref(h)))
+        return Names(self, h)
 
     @staticmethod
     def _quals_result(rc, h, rep):

@@ -14,6 +14,7 @@ struct dnagpu_text_image {
     u64 n = 0, bytes = 0, empty = 0, name_base = 0;
     u64 *pos = nullptr;                 // pool memory: n + 1 record offsets, then EXPORT_PREFIX_MAX bytes of prefix
     u64 *numbers = nullptr;             // pool memory, n entries, or null
+    const dnagpu_names *names = nullptr;    // dnagpu_table_to_text_named: BORROWED like the table; the headers are its strings
     unsigned char prefix[EXPORT_PREFIX_MAX] = {};
 };
 
@@ -40,15 +41,17 @@ int check_options(const dnagpu_text_out_options *opt)
     return DNAGPU_OK;
 }
 
-int plan_image(dnagpu_ctx *ctx, const dnagpu_dna *table, const dnagpu_text_out_options *opt, dnagpu_text_image *img)
+int plan_image(dnagpu_ctx *ctx, const dnagpu_dna *table, const dnagpu_names *names, const dnagpu_text_out_options *opt,
+               dnagpu_text_image *img)
 {
     const u64 n = table->n_seqs;
     img->table = table;
+    img->names = names;
     img->n = n;
     img->fmt.format = opt->format;
     img->fmt.term = opt->flags & DNAGPU_TEXT_OUT_CRLF ? 2 : 1;
     img->fmt.width = opt->line_width;
-    const bool named = opt->format != DNAGPU_TEXT_LINES;             // LINES ignores prefix, base and numbers
+    const bool named = opt->format != DNAGPU_TEXT_LINES && !names;   // LINES and a names column ignore prefix, base and numbers
     img->fmt.prefix_len = named ? opt->prefix_len : 0;
     img->fmt.quality = opt->quality ? (unsigned char)opt->quality : (unsigned char)'I';
     img->name_base = named ? opt->name_base : 0;
@@ -75,7 +78,10 @@ int plan_image(dnagpu_ctx *ctx, const dnagpu_dna *table, const dnagpu_text_out_o
     RC_TRY(ps.alloc((size_t)n + 1, &ex32));
     RC_TRY(ps.alloc(2, &res));
     prof_mark(ctx, "export_plan");
-    HIP_TRY(launch_export_plan(table->seq_starts, n, numbers, img->name_base, img->fmt, ex32, res, st));
+    if (names)
+        HIP_TRY(launch_export_plan_named(table->seq_starts, n, names->off, img->fmt, ex32, res, st));
+    else
+        HIP_TRY(launch_export_plan(table->seq_starts, n, numbers, img->name_base, img->fmt, ex32, res, st));
     u64 got[2] = {0, 0};
     RC_TRY(read_back(ctx, got, res, sizeof got));    // (waits for the stream: the caller's numbers have been read)
     if (got[0] > U32_MAX64) {
@@ -114,8 +120,32 @@ extern "C" int dnagpu_table_to_text(dnagpu_ctx *ctx, const dnagpu_dna *table, co
     if (table_without_set(table))
         return DNAGPU_ERR_BAD_ARG;
     std::unique_ptr<dnagpu_text_image> img(new dnagpu_text_image);
-    const int rc = plan_image(ctx, table, opt, img.get());
+    const int rc = plan_image(ctx, table, nullptr, opt, img.get());
     if (rc != DNAGPU_OK) {                           // (what the scope of the plan had not yet handed over is already back)
+        img->pos = img->numbers = nullptr;
+        return rc;
+    }
+    *out = img.release();
+    return DNAGPU_OK;
+    });
+}
+
+extern "C" int dnagpu_table_to_text_named(dnagpu_ctx *ctx, const dnagpu_dna *table, const dnagpu_names *names,
+                                          const dnagpu_text_out_options *opt, dnagpu_text_image **out)
+{
+    return guarded([&]() -> int {
+    if (!ctx || !table || !names || !opt || !out)
+        return DNAGPU_ERR_BAD_ARG;
+    RC_TRY(check_options(opt));
+    if (opt->format == DNAGPU_TEXT_LINES)
+        return DNAGPU_ERR_BAD_ARG;                   // (LINES has no names)
+    if (table_without_set(table))
+        return DNAGPU_ERR_BAD_ARG;
+    if (names->n != table->n_seqs)
+        return DNAGPU_ERR_BAD_ARG;                   // (not this table's column)
+    std::unique_ptr<dnagpu_text_image> img(new dnagpu_text_image);
+    const int rc = plan_image(ctx, table, names, opt, img.get());
+    if (rc != DNAGPU_OK) {
         img->pos = img->numbers = nullptr;
         return rc;
     }
@@ -149,7 +179,10 @@ int read_window(dnagpu_ctx *ctx, const dnagpu_text_image *img, const dnagpu_qual
     const ExportRead a = {t->words, t->n_words, t->n_bases, t->seq_starts, img->pos, img->numbers,
                           reinterpret_cast<const unsigned char *>(img->pos + img->n + 1), img->n, img->name_base, img->fmt,
                           first_byte, count, dt};
-    HIP_TRY(launch_export_read(a, ctx->stream));
+    if (img->names)
+        HIP_TRY(launch_export_read_named(a, ExportNames{img->names->bytes, img->names->off}, ctx->stream));
+    else
+        HIP_TRY(launch_export_read(a, ctx->stream));
     if (quals)
         HIP_TRY(launch_quals_overlay(quals->bytes, t->seq_starts, img->pos, img->n, img->fmt.term, first_byte, count, dt, ctx->stream));
     if (!out_on_device)

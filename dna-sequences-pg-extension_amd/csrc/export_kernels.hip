@@ -1,25 +1,33 @@
 // export_kernels.hip -- the text image of a resident table (dnagpu_table_to_text, dnagpu_text_image_read): the
 // pass that sizes every record, the widening of the scanned sizes into record offsets, and the output-centric sweep that
-// forms any byte window of the image.  The record arithmetic is export_math.hpp's.
+// forms any byte window of the image.  The record arithmetic is export_math.hpp's.  Every kernel has a NAMED sibling
+// (dnagpu_table_to_text_named) made from the same body: the headers are the strings of a names column.
 #include <hip/hip_runtime.h>
 
 #include "export_math.hpp"
 #include "kernels.hpp"
+#include "quals_math.hpp"
 
 namespace dnagpu {
 
 // ---- the plan.  One thread per sequence (grid-stride): ex32[s] = the bytes of record s that are no bases of a sequence
 // line (clamped: the scan is only run once the total is known to fit 32 bits); res[0] += those, res[1] += the sequences of
 // 0 bases: a block reduce, then one atomic per workgroup and word (take_segments_kernel's shape).
-__global__ __launch_bounds__(EXPORT_THREADS) void export_plan_kernel(const u64 *__restrict__ starts, u64 n,
-                                                                     const u64 *__restrict__ numbers, u64 name_base, ExportFmt f,
-                                                                     u32 *__restrict__ ex32, unsigned long long *__restrict__ res)
+// NAMED (dnagpu_table_to_text_named): `numbers` is the n + 1 offsets of a names column, and the header of record s is its
+// marker and the column's string s.
+template <bool NAMED>
+__device__ __forceinline__ void export_plan_body(const u64 *__restrict__ starts, u64 n, const u64 *__restrict__ numbers, u64 name_base,
+                                                 const ExportFmt &f, u32 *__restrict__ ex32, unsigned long long *__restrict__ res)
 {
     __shared__ u64 wsum[EXPORT_THREADS / 64], wemp[EXPORT_THREADS / 64];
     u64 sum = 0, emp = 0;
     for (u64 s = (u64)blockIdx.x * EXPORT_THREADS + threadIdx.x; s < n; s += (u64)gridDim.x * EXPORT_THREADS) {
         const u64 len = starts[s + 1] - starts[s];
-        const u32 hl = export_header_len(f, numbers ? numbers[s] : name_base + s);
+        u32 hl;
+        if constexpr (NAMED)
+            hl = 1u + (u32)(numbers[s + 1] - numbers[s]);
+        else
+            hl = export_header_len(f, numbers ? numbers[s] : name_base + s);
         const u64 ex = export_extras(f, len, hl);
         ex32[s] = ex > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)ex;
         sum += ex;                                   // (at most 2^32 - 1 bases in all: no overflow)
@@ -46,6 +54,18 @@ __global__ __launch_bounds__(EXPORT_THREADS) void export_plan_kernel(const u64 *
         if (empties)
             atomicAdd(&res[1], (unsigned long long)empties);
     }
+}
+__global__ __launch_bounds__(EXPORT_THREADS) void export_plan_kernel(const u64 *__restrict__ starts, u64 n,
+                                                                     const u64 *__restrict__ numbers, u64 name_base, ExportFmt f,
+                                                                     u32 *__restrict__ ex32, unsigned long long *__restrict__ res)
+{
+    export_plan_body<false>(starts, n, numbers, name_base, f, ex32, res);
+}
+__global__ __launch_bounds__(EXPORT_THREADS) void export_plan_named_kernel(const u64 *__restrict__ starts, u64 n,
+                                                                           const u64 *__restrict__ name_off, ExportFmt f,
+                                                                           u32 *__restrict__ ex32, unsigned long long *__restrict__ res)
+{
+    export_plan_body<true>(starts, n, name_off, 0, f, ex32, res);
 }
 
 // pos[s] = starts[s] + scan[s] (the exclusive scan of the extras) for s < n, pos[n] = starts[n] + total
@@ -132,10 +152,35 @@ struct ExportHint {
     u64 rec, bo0, q0, col0;
 };
 
+// the number of record s's name; NAMED: where its name begins in the column's bytes (what ExportRec.number then holds)
+template <bool NAMED>
+__device__ __forceinline__ u64 export_name_of(const ExportRead &A, const ExportNames &N, u64 s)
+{
+    if constexpr (NAMED)
+        return N.off[s];
+    else
+        return A.numbers ? A.numbers[s] : A.name_base + s;
+}
+
+// sixteen bytes of a names column from byte a on, as aligned words; the column's allocation has NAMES_SLACK bytes behind
+// its last byte, so the fifth word is inside it
+__device__ __forceinline__ QualsBytes export_name16(const ExportNames &N, u64 a)
+{
+    const u32 mis = (u32)(reinterpret_cast<uintptr_t>(N.bytes + a) & 3);
+    const u32 *q = reinterpret_cast<const u32 *>(N.bytes + a - mis);
+    u32 d[5];
+#pragma unroll
+    for (u32 i = 0; i < 4; i++)
+        d[i] = q[i];
+    d[4] = mis ? q[4] : 0u;
+    return quals_from_words(d, mis);
+}
+
 // One chunk: bytes [j0, j1) of the 16 bytes at out (16-byte aligned), the first of them byte p of the image, which lies
 // in record s.  Record i's offset and first base are posA[i - bias] and startA[i - bias].
-__device__ __forceinline__ void export_chunk(const ExportRead &A, const u64 *posA, const u64 *startA, u64 bias, u64 s, u64 p,
-                                             const ExportHint &h, u32 j0, u32 j1, unsigned char *out)
+template <bool NAMED>
+__device__ __forceinline__ void export_chunk(const ExportRead &A, const ExportNames &N, const u64 *posA, const u64 *startA, u64 bias,
+                                             u64 s, u64 p, const ExportHint &h, u32 j0, u32 j1, unsigned char *out)
 {
     const ExportFmt &f = A.fmt;
     u64 rp = posA[s - bias], st = startA[s - bias];
@@ -157,8 +202,19 @@ __device__ __forceinline__ void export_chunk(const ExportRead &A, const u64 *pos
         }
     });
     if (c.phase == 0)
-        r.number = A.numbers ? A.numbers[s] : A.name_base + s;
+        r.number = export_name_of<NAMED>(A, N, s);
     const bool whole = j0 == 0 && j1 == EXPORT_CHUNK;
+    if constexpr (NAMED) {
+        if (whole && c.phase == 0 && c.rem >= EXPORT_CHUNK) {       // inside one header: the name's bytes as words
+            QualsBytes v = export_name16(N, r.number + (c.idx ? c.idx - 1 : 0));
+            if (c.idx == 0) {                                        // the marker, then the name's first fifteen bytes
+                v.hi = (v.hi << 8) | (v.lo >> 56);
+                v.lo = (v.lo << 8) | (u64)(f.format == EXPORT_FASTA ? '>' : '@');
+            }
+            *reinterpret_cast<uint4 *>(out) = make_uint4((u32)v.lo, (u32)(v.lo >> 32), (u32)v.hi, (u32)(v.hi >> 32));
+            return;
+        }
+    }
     if (whole && c.phase == 6 && c.rem >= EXPORT_CHUNK) {
         const u32 v = f.quality * 0x01010101u;
         *reinterpret_cast<uint4 *>(out) = make_uint4(v, v, v, v);
@@ -210,14 +266,21 @@ __device__ __forceinline__ void export_chunk(const ExportRead &A, const u64 *pos
                 r.header_len = export_header_from_size(f, r.len, posA[s + 1 - bias] - rp);
                 c = export_begin(f, r);
                 if (c.phase == 0)
-                    r.number = A.numbers ? A.numbers[s] : A.name_base + s;
+                    r.number = export_name_of<NAMED>(A, N, s);
             }
         }
-        const u64 b = export_emit(f, r, c, A.prefix, [&]() {
-            const u32 code = bits & 3;
-            bits >>= 2;
-            return code;
-        });
+        u64 b;
+        if (NAMED && c.phase == 0) {
+            b = c.idx == 0 ? (u64)(f.format == EXPORT_FASTA ? '>' : '@') : (u64)N.bytes[r.number + c.idx - 1];
+            c.idx++;
+            c.rem--;
+        } else {
+            b = export_emit(f, r, c, A.prefix, [&]() {
+                const u32 code = bits & 3;
+                bits >>= 2;
+                return code;
+            });
+        }
         if (j < 8)
             lo |= b << (8 * j);
         else
@@ -231,8 +294,9 @@ __device__ __forceinline__ void export_chunk(const ExportRead &A, const u64 *pos
     }
 }
 
-__device__ __forceinline__ void export_tile_chunks(const ExportRead &A, const u64 *posA, const u64 *startA, u64 bias, u64 lo,
-                                                   u64 hi, const ExportHint &h, u64 v_tile, u32 a, u64 v_end)
+template <bool NAMED>
+__device__ __forceinline__ void export_tile_chunks(const ExportRead &A, const ExportNames &N, const u64 *posA, const u64 *startA,
+                                                   u64 bias, u64 lo, u64 hi, const ExportHint &h, u64 v_tile, u32 a, u64 v_end)
 {
     const u32 tid = threadIdx.x;
     unsigned char *dst_al = A.dst - a;
@@ -250,7 +314,7 @@ __device__ __forceinline__ void export_tile_chunks(const ExportRead &A, const u6
             continue;
         const u32 j0 = v < a ? a - (u32)v : 0;
         const u32 j1 = v_end - v < EXPORT_CHUNK ? (u32)(v_end - v) : EXPORT_CHUNK;
-        export_chunk(A, posA, startA, bias, rec[k], A.first_byte + v + j0 - a, h, j0, j1, dst_al + v);
+        export_chunk<NAMED>(A, N, posA, startA, bias, rec[k], A.first_byte + v + j0 - a, h, j0, j1, dst_al + v);
     }
 }
 
@@ -260,7 +324,8 @@ __device__ __forceinline__ void export_tile_chunks(const ExportRead &A, const u6
 // that hold the window's first and last byte are stored byte by byte.  The workgroup finds the records of its first and last
 // byte once (take_copy_kernel's way), brings the offsets and first bases of the records between them into LDS when they are
 // at most EXPORT_LDS_RECS, and every lane searches for the record of its chunk's first byte there.  count > 0.
-__global__ __launch_bounds__(EXPORT_THREADS) void export_read_kernel(const ExportRead A)
+template <bool NAMED>
+__device__ __forceinline__ void export_read_body(const ExportRead &A, const ExportNames &N)
 {
     __shared__ u32 wc[EXPORT_THREADS / 64], wle[EXPORT_THREADS / 64];
     __shared__ u64 s_pos[EXPORT_LDS_RECS + 1], s_start[EXPORT_LDS_RECS + 1];
@@ -308,10 +373,19 @@ __global__ __launch_bounds__(EXPORT_THREADS) void export_read_kernel(const Expor
             s_start[i] = A.starts[rec_lo + i];
         }
         __syncthreads();
-        export_tile_chunks(A, s_pos, s_start, rec_lo, rec_lo, rec_hi, h, v_tile, a, v_end);
+        export_tile_chunks<NAMED>(A, N, s_pos, s_start, rec_lo, rec_lo, rec_hi, h, v_tile, a, v_end);
     } else {
-        export_tile_chunks(A, A.pos, A.starts, 0, rec_lo, rec_hi, h, v_tile, a, v_end);
+        export_tile_chunks<NAMED>(A, N, A.pos, A.starts, 0, rec_lo, rec_hi, h, v_tile, a, v_end);
     }
+}
+__global__ __launch_bounds__(EXPORT_THREADS) void export_read_kernel(const ExportRead A)
+{
+    export_read_body<false>(A, ExportNames{nullptr, nullptr});
+}
+// the image of dnagpu_table_to_text_named: every header is its marker and the string of N
+__global__ __launch_bounds__(EXPORT_THREADS) void export_read_named_kernel(const ExportRead A, const ExportNames N)
+{
+    export_read_body<true>(A, N);
 }
 
 hipError_t launch_export_plan(const u64 *starts, u64 n, const u64 *numbers, u64 name_base, const ExportFmt &f, u32 *ex32,
@@ -323,6 +397,18 @@ hipError_t launch_export_plan(const u64 *starts, u64 n, const u64 *numbers, u64 
     const u64 blocks = (n + EXPORT_THREADS - 1) / EXPORT_THREADS;
     hipLaunchKernelGGL(export_plan_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(EXPORT_THREADS), 0, s, starts, n,
                        numbers, name_base, f, ex32, res2);
+    return hipGetLastError();
+}
+
+hipError_t launch_export_plan_named(const u64 *starts, u64 n, const u64 *name_off, const ExportFmt &f, u32 *ex32,
+                                    unsigned long long *res2, hipStream_t s)
+{
+    hipError_t e = hipMemsetAsync(res2, 0, 2 * sizeof(unsigned long long), s);
+    if (e != hipSuccess || n == 0)
+        return e;
+    const u64 blocks = (n + EXPORT_THREADS - 1) / EXPORT_THREADS;
+    hipLaunchKernelGGL(export_plan_named_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(EXPORT_THREADS), 0, s, starts, n,
+                       name_off, f, ex32, res2);
     return hipGetLastError();
 }
 
@@ -340,6 +426,16 @@ hipError_t launch_export_read(const ExportRead &a, hipStream_t s)
     const u64 v_end = (reinterpret_cast<uintptr_t>(a.dst) & 15) + a.count;
     hipLaunchKernelGGL(export_read_kernel, dim3((unsigned)((v_end + EXPORT_TILE_BYTES - 1) / EXPORT_TILE_BYTES)), dim3(EXPORT_THREADS),
                        0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_export_read_named(const ExportRead &a, const ExportNames &names, hipStream_t s)
+{
+    if (a.count == 0)
+        return hipSuccess;
+    const u64 v_end = (reinterpret_cast<uintptr_t>(a.dst) & 15) + a.count;
+    hipLaunchKernelGGL(export_read_named_kernel, dim3((unsigned)((v_end + EXPORT_TILE_BYTES - 1) / EXPORT_TILE_BYTES)),
+                       dim3(EXPORT_THREADS), 0, s, a, names);
     return hipGetLastError();
 }
 

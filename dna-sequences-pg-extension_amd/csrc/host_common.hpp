@@ -1,5 +1,5 @@
 // host_common.hpp -- what the host files of the C-ABI (dnagpu_api.hip, count_host.hip, sk_host.hip, multi_host.hip, query_host.hip,
-// filter_host.hip, index_host.hip, join_host.hip, hits_host.hip, take_host.hip, profile_host.hip, seqeq_host.hip, text_host.hip, reads_host.hip, export_host.hip, quals_host.hip, host_steps.hip, table_steps.hip) share
+// filter_host.hip, index_host.hip, join_host.hip, hits_host.hip, take_host.hip, profile_host.hip, seqeq_host.hip, text_host.hip, reads_host.hip, export_host.hip, quals_host.hip, names_host.hip, host_steps.hip, table_steps.hip) share
 // (internal, like kernels.hpp): the error macros, the context / dna / histogram objects, the buffer pool, and the few
 // functions one of the files calls in another.  Declarations only, plus the templates and macros that must be visible;
 // the definitions are in dnagpu_api.hip unless a section says otherwise.
@@ -519,6 +519,13 @@ struct dnagpu_seq_classes {
 struct dnagpu_quals {
     unsigned char *bytes = nullptr;     // pool memory: whole 16-byte chunks, at least one
     u64 n = 0;
+};
+
+// the names column of a table (names_host.hip): one string per sequence, none of its bytes '\n' or '\r'
+struct dnagpu_names {
+    unsigned char *bytes = nullptr;     // pool memory: names_alloc_bytes(total) bytes
+    u64 *off = nullptr;                 // pool memory: n + 1 offsets, off[0] = 0, off[n] = total
+    u64 n = 0, total = 0;
 };
 
 struct dnagpu_records {

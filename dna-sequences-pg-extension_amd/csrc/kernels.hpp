@@ -404,6 +404,48 @@ struct ExportRead {
     unsigned char *dst;
 };
 hipError_t launch_export_read(const ExportRead &a, hipStream_t s);
+// the named image (dnagpu_table_to_text_named): the header of record s is its marker and bytes [off[s],
+// off[s + 1]) of a names column, whose allocation reaches NAMES_SLACK bytes behind its last byte.  The plan and the sweep are
+// the bodies of the two above; a.numbers, a.prefix and a.name_base are not looked at.
+struct ExportNames {
+    const unsigned char *bytes;
+    const u64 *off;                          // n + 1 entries
+};
+hipError_t launch_export_plan_named(const u64 *starts, u64 n, const u64 *name_off, const ExportFmt &f, u32 *ex32,
+                                    unsigned long long *res2, hipStream_t s);
+hipError_t launch_export_read_named(const ExportRead &a, const ExportNames &names, hipStream_t s);
+
+// ---- the names column of a table (names_kernels.hip; the arithmetic is names_math.hpp's).
+// the sweep over a text: mask[c] = the bytes of chunk c (TEXT_CHUNK bytes) that end a name -- '\n', and with first_word
+// blank and tab --, tile_first[t] = the offset of the first of them in tile t (NAMES_NONE: none); res[NAMES_R_LONE_CR] |= 1
+// where a '\r' is not followed by '\n'
+hipError_t launch_names_ends(const unsigned char *text, u64 n, u32 n_tiles, bool first_word, u32 *mask, u32 *tile_first,
+                             unsigned long long *res, hipStream_t s);
+// the suffix minimum of tile_first in groups of NAMES_GROUP_TILES tiles: local[t] = the minimum over tile t and the tiles
+// behind it in its group, after[g] = the minimum over the groups behind group g.  group_min: names_groups(n_tiles) words.
+hipError_t launch_names_suffix_min(const u32 *tile_first, u32 n_tiles, u32 *local, u32 *group_min, u32 *after, hipStream_t s);
+// one thread per sequence: first[s] / len32[s] = where its name lies in the text; res[NAMES_R_TOTAL] += the lengths,
+// res[NAMES_R_BAD] |= 1 for a record_pos that is not the marker's inside the text or a src_record >= n_records (null:
+// sequence s is record s)
+struct NamesSpans {
+    const unsigned char *text;
+    u64 n;
+    u32 n_tiles;
+    u32 marker;
+    const u32 *mask, *local, *after;
+    const u64 *record_pos, *src_record;
+    u64 n_records, n_seqs;
+    u64 *first;
+    u32 *len32;
+    unsigned long long *res;
+};
+hipError_t launch_names_spans(const NamesSpans &a, hipStream_t s);
+// a caller's n + 1 offsets: res[NAMES_R_BAD] |= 1 unless off[0] == 0 and no pair decreases, res[NAMES_R_TOTAL] = off[n]
+hipError_t launch_names_offsets_check(const u64 *off, u64 n, unsigned long long *res, hipStream_t s);
+// res[0] takes the minimum offset of a '\n' or '\r' in the total bytes at col (NAMES_NO_ERROR before the launch: none)
+hipError_t launch_names_validate(const unsigned char *col, u64 total, unsigned long long *res, hipStream_t s);
+// out3 = {the sequence whose name holds column byte pos, first[s] + its offset inside the name, src_record[s] (or s)}
+hipError_t launch_names_locate(const u64 *off, u64 n, u64 pos, const u64 *first, const u64 *src_record, u64 *out3, hipStream_t s);
 
 // ---- the quality column of a table (quals_kernels.hip; the byte arithmetic is quals_math.hpp's).
 // col: a caller's n bytes in a column's allocation (whole 16-byte chunks); res[0] takes the minimum of the error words

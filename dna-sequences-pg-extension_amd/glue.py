@@ -226,6 +226,14 @@ def lib():
         L.copy_reads_to_failed.argtypes = [vp]
         L.copy_reads_to_end.restype = None
         L.copy_reads_to_end.argtypes = [vp]
+        L.copy_reads_keep_names.restype = C.c_bool
+        L.copy_reads_keep_names.argtypes = [vp, C.c_bool]
+        L.copy_reads_name.restype = vp
+        L.copy_reads_name.argtypes = [vp, C.POINTER(C.c_size_t)]
+        L.copy_reads_to_add_named.restype = C.c_bool
+        L.copy_reads_to_add_named.argtypes = [vp, vp, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
+        L.copy_dna_to_add_named.restype = C.c_bool
+        L.copy_dna_to_add_named.argtypes = [vp, vp, C.c_char_p, C.c_size_t]
         L.kmer_index_create.restype = vp
         L.kmer_index_create.argtypes = [C.POINTER(_Kmer), C.c_uint64]
         L.kmer_index_rows.restype = C.c_uint64
@@ -919,6 +927,138 @@ def copy_reads_to(rows, quals, crlf=False):
         return b"".join(out)
     finally:
         lib().copy_reads_to_end(c)
+
+
+def _served_name(c):
+    n = C.c_size_t()
+    p = lib().copy_reads_name(c, C.byref(n))
+    return C.string_at(p, n.value) if p else None
+
+
+def copy_reads_named(pieces, format=3, ambiguous=0, fold_case=False, min_bases=0, first_word=False):
+    """copy_reads where every row carries the name of its source record (copy_reads_keep_names; FASTA or FASTQ) ->
+    ([dna], [record], [offset], [name bytes])"""
+    c = lib().copy_reads_begin(int(format), int(ambiguous), 2 if fold_case else 0, int(min_bases))
+    if not c:
+        raise _err()
+    try:
+        if not lib().copy_reads_keep_names(c, bool(first_word)):
+            raise _err()
+        rows, records, offsets, names = [], [], [], []
+        p, rec, off = C.c_void_p(), C.c_int64(), C.c_int64()
+
+        def drain():
+            while lib().copy_reads_next(c, C.byref(p), C.byref(rec), C.byref(off)):
+                rows.append(dna(p=p.value))
+                records.append(rec.value)
+                offsets.append(off.value)
+                names.append(_served_name(c))
+
+        def check(ok):
+            if not ok:
+                e = _err()
+                lib().copy_reads_next(c, None, C.byref(rec), None)
+                e.record = rec.value
+                raise e
+        for piece in pieces:
+            b = bytes(piece)
+            check(lib().copy_dna_feed(c, b, len(b), False))
+            drain()
+        check(lib().copy_dna_feed(c, None, 0, True))
+        drain()
+        return rows, records, offsets, names
+    finally:
+        lib().copy_dna_end(c)
+
+
+def trim_reads_named(pieces, first_word=False, ambiguous=0, fold_case=False, cut_front=0, cut_tail=0, min_bases=0, min_mean_q=0,
+                     low_q=0, low_frac=(0, 0)):
+    """trim_reads where every passing read carries its own name (copy_reads_keep_names) ->
+    ([dna], [record], [offset], [quality bytes], [name bytes])"""
+    c = lib().trim_reads_begin(int(ambiguous), 2 if fold_case else 0, int(cut_front), int(cut_tail), int(min_bases), int(min_mean_q),
+                               int(low_q), int(low_frac[0]), int(low_frac[1]))
+    if not c:
+        raise _err()
+    try:
+        if not lib().copy_reads_keep_names(c, bool(first_word)):
+            raise _err()
+        rows, records, offsets, quals, names = [], [], [], [], []
+        p, rec, off, q = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_void_p()
+
+        def drain():
+            while lib().trim_reads_next(c, C.byref(p), C.byref(rec), C.byref(off), C.byref(q)):
+                rows.append(dna(p=p.value))
+                records.append(rec.value)
+                offsets.append(off.value)
+                quals.append(C.string_at(q.value))
+                _libc.free(q.value)
+                names.append(_served_name(c))
+
+        def check(ok):
+            if not ok:
+                e = _err()
+                lib().trim_reads_next(c, None, C.byref(rec), None, None)
+                e.record = rec.value
+                raise e
+        for piece in pieces:
+            b = bytes(piece)
+            check(lib().copy_dna_feed(c, b, len(b), False))
+            drain()
+        check(lib().copy_dna_feed(c, None, 0, True))
+        drain()
+        return rows, records, offsets, quals, names
+    finally:
+        lib().copy_dna_end(c)
+
+
+def copy_reads_to_named(rows, names, quals, crlf=False):
+    """rows (dna) with their names and quality texts (bytes each) -> the FASTQ file's bytes, every header the row's own name"""
+    c = lib().copy_reads_to_begin(bool(crlf))
+    if not c:
+        raise _err()
+    try:
+        out = []
+        p, n = C.c_void_p(), C.c_size_t()
+
+        def drain():
+            while lib().copy_reads_to_next(c, C.byref(p), C.byref(n)):
+                out.append(C.string_at(p.value, n.value))
+        for row, nm, q in zip(rows, names, quals):
+            nm, q = bytes(nm), bytes(q)
+            if not lib().copy_reads_to_add_named(c, _as_dna(row).p, nm, len(nm), q, len(q)):
+                raise _err()
+            drain()
+        if not lib().copy_reads_to_finish(c):
+            raise _err()
+        drain()
+        return b"".join(out)
+    finally:
+        lib().copy_reads_to_end(c)
+
+
+def copy_dna_to_named(rows, names, format=2, line_width=0, crlf=False):
+    """rows (dna) with their names -> the FASTA (2) or FASTQ (3) file's bytes, every header the row's own name"""
+    c = lib().copy_dna_to_begin(int(format), int(line_width), bool(crlf))
+    if not c:
+        raise _err()
+    try:
+        out = []
+        p, n = C.c_void_p(), C.c_size_t()
+
+        def drain():
+            while lib().copy_dna_to_next(c, C.byref(p), C.byref(n)):
+                out.append(C.string_at(p.value, n.value))
+        for row, nm in zip(rows, names):
+            nm = bytes(nm)
+            if not lib().copy_dna_to_add_named(c, _as_dna(row).p, nm, len(nm)):
+                raise _err()
+            drain()
+        if not lib().copy_dna_to_finish(c):
+            raise _err()
+        drain()
+        return b"".join(out)
+    finally:
+        lib().copy_dna_to_end(c)
 
 
 class kmer_index:

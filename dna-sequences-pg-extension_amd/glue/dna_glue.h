@@ -356,6 +356,22 @@ bool copy_reads_to_finish(CopyDnaTo *c);
 bool copy_reads_to_next(CopyDnaTo *c, const char **bytes, size_t *n);
 bool copy_reads_to_failed(const CopyDnaTo *c);
 void copy_reads_to_end(CopyDnaTo *c);
+/* ---- the reads' own names: in through the names column, out into the headers ----
+ * copy_reads_keep_names: every row of a copy_reads / trim_reads handle for FASTA or FASTQ carries the name of its source
+ *   record -- the header line without its marker and terminator, with first_word cut before its first blank or tab
+ *   (dnagpu_names_from_text on every chunk; after a trim dnagpu_names_take on the passing ids).  Call it after the begin and
+ *   before the first feed: another format, or a call after feeding, is an ERROR (false).  Besides the loader's messages:
+ *   "invalid character in a read name" for a '\r' inside a name, reported as an input ERROR with its record.
+ * copy_reads_name = the name of the row last returned by copy_reads_next / trim_reads_next (NUL-terminated, *len its bytes;
+ *   valid until the next call of a _next or the end; NULL before the first row or without keep_names).
+ * copy_reads_to_add_named / copy_dna_to_add_named: the _add of copy_reads_to (FASTQ) / copy_dna_to (FASTA, FASTQ) where the
+ *   header is the row's name, name_len bytes (not NUL-terminated), instead of the row's number.  Rows with a name and rows
+ *   without one in the same handle are an ERROR; a '\r' or '\n' in a name is the library's "invalid character in a read
+ *   name", raised when the batch is written. */
+bool copy_reads_keep_names(CopyDna *c, bool first_word);
+const char *copy_reads_name(const CopyDna *c, size_t *len);
+bool copy_reads_to_add_named(CopyDnaTo *c, const Dna *row, const char *name, size_t name_len, const char *quality, size_t quality_len);
+bool copy_dna_to_add_named(CopyDnaTo *c, const Dna *row, const char *name, size_t name_len);
 
 /* ---- CREATE INDEX ... ON kmer_data_t USING spgist (kmer_sequence spgist_kmer_ops) and the index scans of `=`, `^@` and `@>`
  * over the stored column (dna--1.0.sql:304-314; test.sql:156-270) ----

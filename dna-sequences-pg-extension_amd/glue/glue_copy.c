@@ -26,6 +26,12 @@ struct CopyDna {
     bool trim;
     dnagpu_quals_trim_options trim_opt;
     char **qual;                                 /* per row of rows[]: malloc'd, NUL-terminated (NULL once handed out) */
+    /* copy_reads_keep_names: every row has the name of its source record */
+    bool fed, keep_names, first_word;
+    char **name;                                 /* per row of rows[]: malloc'd, NUL-terminated (NULL once served) */
+    uint64_t *name_len;
+    char *served_name;                           /* the name of the row last returned by a _next; freed by the next one */
+    uint64_t served_len;
 };
 
 CopyDna *copy_dna_begin(int format)
@@ -82,8 +88,72 @@ CopyDna *trim_reads_begin(int ambiguous, unsigned flags, uint32_t cut_front, uin
 /* room for `need` rows: rows[] and the per-row arrays of the object's kind, which grow together */
 static bool copy_grow(CopyDna *c, uint64_t need)
 {
-    return glue_grow((void **[]){(void **)&c->rows, (void **)&c->src_record, (void **)&c->src_offset, (void **)&c->qual},
-                     c->trim ? 4 : c->reads ? 3 : 1, &c->cap_rows, need);
+    void **cols[6] = {(void **)&c->rows, (void **)&c->src_record, (void **)&c->src_offset};
+    int n = c->reads ? 3 : 1;
+    if (c->trim)
+        cols[n++] = (void **)&c->qual;
+    if (c->keep_names) {
+        cols[n++] = (void **)&c->name;
+        cols[n++] = (void **)&c->name_len;
+    }
+    return glue_grow(cols, n, &c->cap_rows, need);
+}
+
+bool copy_reads_keep_names(CopyDna *c, bool first_word)
+{
+    if (!c->reads || (c->format != DNAGPU_TEXT_FASTA && c->format != DNAGPU_TEXT_FASTQ)) {
+        ereport_error("copy_reads_keep_names: only FASTA and FASTQ (copy_reads_begin with format 2 or 3, trim_reads_begin) have names");
+        return false;
+    }
+    if (c->fed) {
+        ereport_error("copy_reads_keep_names: called after the first bytes were fed");
+        return false;
+    }
+    c->keep_names = true;
+    c->first_word = first_word;
+    return true;
+}
+
+const char *copy_reads_name(const CopyDna *c, size_t *len)
+{
+    if (len)
+        *len = c->served_name ? (size_t)c->served_len : 0;
+    return c->served_name;
+}
+
+/* the m strings of nm as the names of rows at .. at + m of c (room is there): malloc'd, NUL-terminated */
+static bool names_rows(CopyDna *c, const dnagpu_names *nm, uint64_t m, uint64_t at)
+{
+    const uint64_t total = dnagpu_names_bytes(nm);
+    uint64_t *off = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(m + 1));
+    char *bytes = (char *)malloc((size_t)total + 1);
+    bool ok = off && bytes;
+    if (!ok)
+        ereport_error("out of memory");
+    ok = ok && gpu_ok(dnagpu_names_offsets(g_ctx, nm, 0, m + 1, off, 0)) && gpu_ok(dnagpu_names_read(g_ctx, nm, 0, total, bytes, 0));
+    for (uint64_t i = 0; i < m; i++)
+        c->name[at + i] = NULL;
+    for (uint64_t i = 0; ok && i < m; i++) {
+        const uint64_t len = off[i + 1] - off[i];
+        char *t = (char *)malloc((size_t)len + 1);
+        if (!t) {
+            ereport_error("out of memory");
+            ok = false;
+            break;
+        }
+        memcpy(t, bytes + off[i], (size_t)len);
+        t[len] = 0;
+        c->name[at + i] = t;
+        c->name_len[at + i] = len;
+    }
+    if (!ok)
+        for (uint64_t i = 0; i < m; i++) {
+            free(c->name[at + i]);
+            c->name[at + i] = NULL;
+        }
+    free(off);
+    free(bytes);
+    return ok;
 }
 
 /* the tail of a load: the bytes accounted for are dropped; a record longer than the chunk doubles the chunk */
@@ -101,7 +171,7 @@ static bool copy_consumed(CopyDna *c, uint64_t consumed, bool more, const char *
  * entries) with its qualities, trimmed and filtered on the device: the passing reads appended as rows with their source
  * record, the offset of their first kept base in it, and their quality text.  *appended = how many. */
 static bool trim_load(CopyDna *c, const dnagpu_dna *d, uint64_t text_bytes, const uint64_t *rec, const uint64_t *off, uint64_t n_seqs,
-                      uint64_t *appended)
+                      const dnagpu_names *names, uint64_t *appended)
 {
     dnagpu_quals *q = NULL, *tq = NULL;
     dnagpu_dna *td = NULL;
@@ -165,6 +235,19 @@ static bool trim_load(CopyDna *c, const dnagpu_dna *d, uint64_t text_bytes, cons
         c->src_record[c->n_rows + i] = c->first_record + rec[s];
         c->src_offset[c->n_rows + i] = off[s] + (seg_first[i] - starts[s]);
     }
+    if (names) {                                                          /* the passing reads' own names */
+        dnagpu_names *tn = NULL;
+        ok = gpu_ok(dnagpu_names_take(g_ctx, names, seg_seq, m, 0, &tn)) && names_rows(c, tn, m, c->n_rows);
+        if (tn)
+            dnagpu_names_free(g_ctx, tn);
+        if (!ok) {
+            for (uint64_t j = 0; j < m; j++) {
+                dna_free(c->rows[c->n_rows + j]);
+                free(c->qual[c->n_rows + j]);
+            }
+            goto done;
+        }
+    }
     *appended = m;
     ok = true;
 done:
@@ -186,39 +269,64 @@ static bool copy_load_reads(CopyDna *c, uint64_t n, bool more)
     const dnagpu_reads_options opt = {c->format, c->ambiguous, c->flags | (more ? DNAGPU_READS_MORE : 0u), 0u, c->min_bases};
     dnagpu_dna *d = NULL;
     dnagpu_reads_report rep;
-    uint64_t cap = n / 32 + 1024, *rec = NULL, *off = NULL;
+    uint64_t cap = n / 32 + 1024, *rec = NULL, *off = NULL, *pos = NULL;
     for (;;) {
-        bool ok = cols_alloc(cap, &rec, &off, NULL);
+        const uint64_t pos_cap = c->keep_names ? cap : 0;                     /* (the records' offsets: only the names need them) */
+        bool ok = cols_alloc(cap, &rec, &off, c->keep_names ? &pos : NULL);
         if (ok) {
-            const int rc = dnagpu_reads_from_text(g_ctx, c->in.buf, n, 0, &opt, &d, NULL, 0, rec, off, cap, &rep);
+            const int rc = dnagpu_reads_from_text(g_ctx, c->in.buf, n, 0, &opt, &d, pos, pos_cap, rec, off, cap, &rep);
             ok = loader_ok(rc, rep.bad_pos, rep.bad_record, c->first_record, &c->bad_line);
         }
-        if (ok && rep.sequences <= cap)
+        if (ok && rep.sequences <= cap && (!c->keep_names || rep.records <= cap))
             break;
         if (ok)
             dnagpu_dna_free(g_ctx, d);
         free(rec);
         free(off);
+        free(pos);
+        pos = NULL;
         if (!ok)
             return false;
-        cap = rep.sequences;
+        cap = rep.sequences > rep.records ? rep.sequences : rep.records;
+    }
+    dnagpu_names *names = NULL;
+    if (c->keep_names) {                                                  /* the names of the same bytes */
+        dnagpu_names_report nrep;
+        const int rc = dnagpu_names_from_text(g_ctx, c->in.buf, more ? rep.consumed : n, 0, c->format,
+                                              c->first_word ? DNAGPU_NAMES_FIRST_WORD : 0u, pos, rep.records, rec, rep.sequences, &names,
+                                              &nrep);
+        if (!loader_ok(rc, nrep.bad_pos, nrep.bad_record, c->first_record, &c->bad_line)) {
+            dnagpu_dna_free(g_ctx, d);
+            free(rec);
+            free(off);
+            free(pos);
+            return false;
+        }
     }
     if (c->next == c->n_rows)                                             /* everything served: the arrays start over */
         c->n_rows = c->next = 0;
     uint64_t added = rep.sequences;
     bool ok;
     if (c->trim) {                                                        /* the qualities of the same bytes, then the trim */
-        ok = trim_load(c, d, more ? rep.consumed : n, rec, off, rep.sequences, &added);
+        ok = trim_load(c, d, more ? rep.consumed : n, rec, off, rep.sequences, names, &added);
     } else {
         ok = copy_grow(c, c->n_rows + rep.sequences) && (rep.sequences == 0 || table_rows(d, rep.sequences, c->rows + c->n_rows));
+        if (ok && names && !names_rows(c, names, rep.sequences, c->n_rows)) {
+            for (uint64_t i = 0; i < rep.sequences; i++)                      /* the rows of this load are not kept */
+                dna_free(c->rows[c->n_rows + i]);
+            ok = false;
+        }
         for (uint64_t i = 0; ok && i < rep.sequences; i++) {
             c->src_record[c->n_rows + i] = c->first_record + rec[i];
             c->src_offset[c->n_rows + i] = off[i];
         }
     }
+    if (names)
+        dnagpu_names_free(g_ctx, names);
     dnagpu_dna_free(g_ctx, d);
     free(rec);
     free(off);
+    free(pos);
     if (!ok)
         return false;
     c->n_rows += added;
@@ -260,6 +368,7 @@ bool copy_dna_feed(CopyDna *c, const char *bytes, size_t n, bool last)
         ereport_error("copy_dna: the bytes are missing");
         return false;
     }
+    c->fed = true;
     if (!gs_bytes_append(&c->in, bytes, n)) {
         ereport_error("out of memory");
         c->life.failed = true;
@@ -307,6 +416,12 @@ bool copy_reads_next(CopyDna *c, Dna **row, int64_t *record, int64_t *offset)
         *record = (int64_t)c->src_record[i];
     if (offset)
         *offset = (int64_t)c->src_offset[i];
+    if (c->keep_names) {                                                  /* copy_reads_name: this row's, until the next call */
+        free(c->served_name);
+        c->served_name = c->name[i];
+        c->served_len = c->name_len[i];
+        c->name[i] = NULL;
+    }
     return copy_dna_next(c, row, NULL);
 }
 
@@ -337,6 +452,11 @@ void copy_dna_end(CopyDna *c)
     for (uint64_t i = 0; c->qual && i < c->n_rows; i++)
         free(c->qual[i]);
     free(c->qual);
+    for (uint64_t i = 0; c->name && i < c->n_rows; i++)
+        free(c->name[i]);
+    free(c->name);
+    free(c->name_len);
+    free(c->served_name);
     for (uint64_t i = 0; i < c->n_rows; i++)
         dna_free(c->rows[i]);
     free(c->rows);

@@ -21,6 +21,11 @@ struct CopyDnaTo {
     bool reads;
     char *qual;                                  /* the quality bytes of the open batch, one per base */
     uint64_t cap_qual;
+    /* _add_named: the headers are the rows' own names */
+    int named;                                   /* 0: no row yet, 1: every row comes with its name, 2: none does */
+    char *names;                                 /* the names of the open batch, back to back */
+    uint64_t *name_off;                          /* name_off[0 .. b.n_seqs]: where each begins */
+    uint64_t cap_names, cap_name_off, n_name_bytes;
 };
 
 CopyDnaTo *copy_dna_to_begin(int format, uint32_t line_width, bool crlf)
@@ -82,9 +87,18 @@ static bool copy_to_flush(void *self)
             const int rc = dnagpu_quals_upload(g_ctx, c->qual, c->b.n_bases, 0, &q, &qrep);
             ok = loader_ok(rc, qrep.bad_pos, qrep.bad_record, 0, NULL);
         }
-        ok = ok && gpu_ok(dnagpu_table_to_text(g_ctx, d, &opt, &img)) && copy_to_read(c, img, q);
+        dnagpu_names *nm = NULL;
+        if (ok && c->named == 1) {
+            dnagpu_names_report nrep;
+            const int rc = dnagpu_names_upload(g_ctx, c->names, c->name_off, c->b.n_seqs, 0, &nm, &nrep);
+            ok = loader_ok(rc, nrep.bad_pos, nrep.bad_record, 0, NULL);
+        }
+        ok = ok && gpu_ok(nm ? dnagpu_table_to_text_named(g_ctx, d, nm, &opt, &img) : dnagpu_table_to_text(g_ctx, d, &opt, &img)) &&
+             copy_to_read(c, img, q);
         if (img)
             dnagpu_text_image_free(g_ctx, img);
+        if (nm)
+            dnagpu_names_free(g_ctx, nm);
         if (q)
             dnagpu_quals_free(g_ctx, q);
         if (d)
@@ -92,7 +106,37 @@ static bool copy_to_flush(void *self)
         c->rows_before += c->b.n_seqs;
     }
     rb_clear(&c->b);
+    c->n_name_bytes = 0;
     return ok;
+}
+
+/* named and unnamed rows do not mix in one handle */
+static bool copy_to_kind(CopyDnaTo *c, int kind, const char *who)
+{
+    if (c->named && c->named != kind) {
+        ereport_error("%s: rows with a name and rows without one in the same COPY", who);
+        return !(c->life.failed = true);
+    }
+    c->named = kind;
+    return true;
+}
+
+/* the name of the row that is added next, behind the names of the batch that takes the row (copy_reads_to_add's first step) */
+static bool copy_to_name(CopyDnaTo *c, const Dna *row, const char *name, size_t name_len)
+{
+    if (rb_spills(&c->b, row->length, c->limit_bases) && !copy_to_flush(c))
+        return !(c->life.failed = true);
+    if (!rb_grow((void **)&c->names, &c->cap_names, (c->n_name_bytes + name_len) / 8 + 1) ||
+        !rb_grow((void **)&c->name_off, &c->cap_name_off, c->b.n_seqs + 2)) {
+        ereport_error("out of memory");
+        return !(c->life.failed = true);
+    }
+    if (name_len)
+        memcpy(c->names + c->n_name_bytes, name, name_len);
+    c->name_off[0] = 0;
+    c->n_name_bytes += name_len;
+    c->name_off[c->b.n_seqs + 1] = c->n_name_bytes;
+    return true;
 }
 
 /* the row into the open batch, by the add policy at limit_bases */
@@ -113,7 +157,24 @@ bool copy_dna_to_add(CopyDnaTo *c, const Dna *row)
         ereport_error("copy_dna_to: the row is missing");
         return false;
     }
-    return copy_to_add(c, row);
+    return copy_to_kind(c, 2, "copy_dna_to") && copy_to_add(c, row);
+}
+
+bool copy_dna_to_add_named(CopyDnaTo *c, const Dna *row, const char *name, size_t name_len)
+{
+    if (!gs_may_add(&c->life) || c->reads) {
+        ereport_error("copy_dna_to: a row added after the last one or after the COPY failed");
+        return false;
+    }
+    if (c->format == DNAGPU_TEXT_LINES) {
+        ereport_error("copy_dna_to: one sequence per line (format 1) has no names");
+        return false;
+    }
+    if (!row || (name_len && !name)) {
+        ereport_error("copy_dna_to: the row or its name is missing");
+        return false;
+    }
+    return copy_to_kind(c, 1, "copy_dna_to") && copy_to_name(c, row, name, name_len) && copy_to_add(c, row);
 }
 
 CopyDnaTo *copy_reads_to_begin(bool crlf)
@@ -124,20 +185,26 @@ CopyDnaTo *copy_reads_to_begin(bool crlf)
     return c;
 }
 
-bool copy_reads_to_add(CopyDnaTo *c, const Dna *row, const char *quality, size_t quality_len)
+static bool reads_to_add(CopyDnaTo *c, const Dna *row, const char *name, size_t name_len, bool named, const char *quality,
+                         size_t quality_len)
 {
     if (!gs_may_add(&c->life) || !c->reads) {
         ereport_error("copy_reads_to: a row added after the last one or after the COPY failed");
         return false;
     }
-    if (!row || (quality_len && !quality)) {
-        ereport_error("copy_reads_to: the row or its quality text is missing");
+    if (!row || (quality_len && !quality) || (name_len && !name)) {
+        ereport_error(named ? "copy_reads_to: the row, its name or its quality text is missing"
+                            : "copy_reads_to: the row or its quality text is missing");
         return false;
     }
+    if (!copy_to_kind(c, named ? 1 : 2, "copy_reads_to"))
+        return false;
     if ((uint64_t)quality_len != row->length) {
         ereport_error("FASTQ quality line length differs from the sequence's");
         return !(c->life.failed = true);
     }
+    if (named && !copy_to_name(c, row, name, name_len))                       /* (flushes a batch the row would spill) */
+        return false;
     /* the policy's first step here, in front of it: the qualities of the open batch leave with it, the row's go behind the
      * qualities of the batch that takes the row */
     if (rb_spills(&c->b, row->length, c->limit_bases) && !copy_to_flush(c))
@@ -149,6 +216,16 @@ bool copy_reads_to_add(CopyDnaTo *c, const Dna *row, const char *quality, size_t
     if (quality_len)
         memcpy(c->qual + c->b.n_bases, quality, quality_len);
     return copy_to_add(c, row);
+}
+
+bool copy_reads_to_add(CopyDnaTo *c, const Dna *row, const char *quality, size_t quality_len)
+{
+    return reads_to_add(c, row, NULL, 0, false, quality, quality_len);
+}
+
+bool copy_reads_to_add_named(CopyDnaTo *c, const Dna *row, const char *name, size_t name_len, const char *quality, size_t quality_len)
+{
+    return reads_to_add(c, row, name, name_len, true, quality, quality_len);
 }
 
 bool copy_reads_to_finish(CopyDnaTo *c) { return copy_dna_to_finish(c); }
@@ -185,6 +262,8 @@ void copy_dna_to_end(CopyDnaTo *c)
     free(c->text);
     free(c->text_len);
     free(c->qual);
+    free(c->names);
+    free(c->name_off);
     rb_free(&c->b);
     free(c);
 }

@@ -603,6 +603,90 @@ int      dnagpu_text_image_read_quals(dnagpu_ctx *ctx, const dnagpu_text_image *
  * It is here for the reason dnagpu_text_geometry, dnagpu_text_out_geometry and dnagpu_quals_geometry are: the copy takes another
  * path past each of these sizes, and a caller's tests can only place their cases on the edges if the library names them. */
 int      dnagpu_quals_copy_geometry(uint64_t *chunk_bytes, uint64_t *tile_bytes, uint64_t *lds_segments);
+
+/* ---- The names column of a table of reads: dnagpu_names.
+ *
+ * A column is an owned object (dnagpu_names_free) of variable-length byte strings, one per sequence of a table: n + 1
+ *   uint64 offsets (offsets[0] = 0, non-decreasing) and offsets[n] bytes in device memory; string s is bytes [offsets[s],
+ *   offsets[s + 1]).  No byte of a column is '\n' or '\r'; that is checked wherever a column is made, so no later call has
+ *   an error path for it.  An empty string is a name ("@\n" is a header the loaders accept).  A column holds at most 2^32 - 1
+ *   strings and 2^32 - 1 bytes.  On every error of every call below *out is left as it was and nothing stays allocated.
+ * dnagpu_names_upload: a column from the caller's arrays (both host memory, or both device memory when on_device != 0).
+ *   Checks, in order: a NULL ctx or out, or NULL offsets with n > 0, is DNAGPU_ERR_BAD_ARG; n > 2^32 - 1 is
+ *   DNAGPU_ERR_TOO_LARGE; NULL bytes with offsets[n] != 0 is DNAGPU_ERR_BAD_ARG (host offsets: here; device offsets: after the
+ *   total below).  These need no device.  Then, on the device over all entries: offsets[0] != 0 or a decreasing pair is
+ *   DNAGPU_ERR_BAD_ARG; offsets[n] > 2^32 - 1 is DNAGPU_ERR_TOO_LARGE; a '\n' or '\r' is DNAGPU_ERR_BAD_ARG, "invalid character
+ *   in a read name": the lowest offset is found on the device and reported with the character in report->bad_pos / bad_char
+ *   (report may be NULL; bad_record stays ~0).  n == 0 gives a valid empty column (offsets and bytes are not looked at).
+ * dnagpu_names_sequences / dnagpu_names_bytes: n and offsets[n]; 0 for NULL; no device.
+ * dnagpu_names_offsets: entries [first, first + count) of the n + 1 offsets to out (host memory, or device memory when
+ *   out_on_device != 0) by dnagpu_dna_sequence_starts' window rule: first > n + 1 or count > n + 1 - first is
+ *   DNAGPU_ERR_BAD_ARG; count == 0 is DNAGPU_OK; a NULL ctx or names, or NULL out with count > 0, is DNAGPU_ERR_BAD_ARG.
+ * dnagpu_names_read: bytes [first_byte, first_byte + count) of the column by dnagpu_quals_read's window rule.
+ *
+ * dnagpu_names_from_text: the names of the table that dnagpu_reads_from_text (or dnagpu_table_from_text, FASTA) made from
+ *   the same bytes.  format is DNAGPU_TEXT_FASTA or DNAGPU_TEXT_FASTQ.  record_pos is the array the loader wrote, n_records
+ *   entries: the offset of each source record's '>' or '@'.  src_record is the loader's per-sequence array, n_seqs entries;
+ *   NULL: sequence s is record s, and n_seqs must equal n_records.  Both are device memory iff text_on_device.  With
+ *   DNAGPU_READS_MORE the caller passes the loader's `consumed` as n_bytes, or the whole chunk: a name never reaches beyond
+ *   its line.
+ *   The header line of record r starts at record_pos[r] and ends before the first '\n' at or after that byte, or at n_bytes
+ *   if there is none; a '\r' directly before that '\n' belongs to the terminator.  The name of sequence s is that line of
+ *   record src_record[s] without its first byte; with flags & DNAGPU_NAMES_FIRST_WORD it is cut before its first ' ' or
+ *   '\t'.  Under SPLIT every piece of a record gets a copy of the record's name; nothing is appended or invented.
+ *   Checks, in order: a NULL ctx or out, NULL text with n_bytes > 0, or NULL record_pos with n_records > 0, is
+ *   DNAGPU_ERR_BAD_ARG; a format other than FASTA or FASTQ (DNAGPU_TEXT_LINES has no names) is DNAGPU_ERR_BAD_ARG; flags other
+ *   than 0 or 1 are DNAGPU_ERR_BAD_ARG; NULL src_record with n_seqs != n_records is DNAGPU_ERR_BAD_ARG; n_bytes, n_records or
+ *   n_seqs > 2^32 - 1 is DNAGPU_ERR_TOO_LARGE.  These need no device.  n_seqs == 0 gives a valid empty column.  Then, found on
+ *   the device over all entries: record_pos[r] >= n_bytes for a record some sequence names, a byte there that is not the
+ *   format's marker, or src_record[s] >= n_records, is DNAGPU_ERR_BAD_ARG with no offset.  Then a 64-bit total of the names
+ *   above 2^32 - 1 is DNAGPU_ERR_TOO_LARGE, judged before the column is allocated.  Then a '\r' that remains inside a name
+ *   is DNAGPU_ERR_BAD_ARG, "invalid character in a read name": report->bad_pos is the text offset of the first such byte in
+ *   the lowest-numbered sequence whose name has one, bad_record its record, bad_char '\r'.
+ *   The call waits for its work.  The success path reads back once; a second read-back happens only where the text holds a
+ *   '\r' that no '\n' follows (anywhere: such a text has its names validated after the copy).
+ * dnagpu_names_take: the names of the sequences seq_ids[0 .. n_ids) in that order -- dnagpu_dna_take's rules: ids may repeat
+ *   and come in any order, they are uint64, host memory or device memory when on_device != 0 (the buffer of
+ *   dnagpu_seq_hits_select or the seg_seq of dnagpu_quals_trim goes straight in).  A NULL ctx, names or out, or NULL seq_ids
+ *   with n_ids > 0, is DNAGPU_ERR_BAD_ARG; n_ids > 2^32 - 1 is DNAGPU_ERR_TOO_LARGE (no device).  An id >= the column's
+ *   sequences is DNAGPU_ERR_BAD_ARG, found over all entries before anything is allocated for the result; a total above
+ *   2^32 - 1 bytes is DNAGPU_ERR_TOO_LARGE.  n_ids == 0 gives a valid empty column.  Given the same ids, the result is the
+ *   names of the table dnagpu_dna_take returns.
+ * dnagpu_table_to_text_named: dnagpu_table_to_text where the name of sequence s is the column's string s; name_prefix,
+ *   name_base and numbers are ignored (prefix_len must still be <= 64).  Checks, in order: a NULL ctx, table, names, opt or
+ *   out; the option checks of dnagpu_table_to_text; a format that is not FASTA or FASTQ; a non-empty stream without a
+ *   sequence set; dnagpu_names_sequences(names) != the table's sequences -- all DNAGPU_ERR_BAD_ARG and without a device; then
+ *   the limit on the bytes that are no bases, DNAGPU_ERR_TOO_LARGE.  The result is an ordinary dnagpu_text_image:
+ *   dnagpu_text_image_bytes, _read, _record_pos, _read_quals, _free, the window and tiling rules and the "no byte outside the
+ *   window is touched" rule hold unchanged.  The image BORROWS the column as it borrows the table.
+ * dnagpu_names_geometry (no device): the sweep of dnagpu_names_from_text marks the bytes that end a name per chunk_bytes of
+ *   text; a name ends in the marks of the tile of tile_bytes it begins in, or else where a suffix minimum over the tiles
+ *   says, which is formed in groups of group_tiles tiles and then over the groups. */
+typedef struct dnagpu_names dnagpu_names;
+#define DNAGPU_NAMES_FIRST_WORD 1u     /* a name ends before its first ' ' or '\t' */
+typedef struct dnagpu_names_report {
+    uint64_t bad_pos;     /* "invalid character in a read name": upload: the offset in bytes; from_text: in the text; ~0 otherwise */
+    uint64_t bad_record;  /* dnagpu_names_from_text: the record bad_pos lies in; ~0 otherwise */
+    char     bad_char;    /* the character, else 0 */
+    char     reserved[7];
+} dnagpu_names_report;
+int      dnagpu_names_upload(dnagpu_ctx *ctx, const char *bytes, const uint64_t *offsets, uint64_t n, int on_device,
+                             dnagpu_names **out, dnagpu_names_report *report);
+uint64_t dnagpu_names_sequences(const dnagpu_names *names);
+uint64_t dnagpu_names_bytes(const dnagpu_names *names);
+int      dnagpu_names_offsets(dnagpu_ctx *ctx, const dnagpu_names *names, uint64_t first, uint64_t count, uint64_t *out,
+                              int out_on_device);
+int      dnagpu_names_read(dnagpu_ctx *ctx, const dnagpu_names *names, uint64_t first_byte, uint64_t count, char *out,
+                           int out_on_device);
+void     dnagpu_names_free(dnagpu_ctx *ctx, dnagpu_names *names);
+int      dnagpu_names_from_text(dnagpu_ctx *ctx, const char *text, uint64_t n_bytes, int text_on_device, int format, unsigned flags,
+                                const uint64_t *record_pos, uint64_t n_records, const uint64_t *src_record, uint64_t n_seqs,
+                                dnagpu_names **out, dnagpu_names_report *report);
+int      dnagpu_names_take(dnagpu_ctx *ctx, const dnagpu_names *names, const uint64_t *seq_ids, uint64_t n_ids, int on_device,
+                           dnagpu_names **out);
+int      dnagpu_table_to_text_named(dnagpu_ctx *ctx, const dnagpu_dna *table, const dnagpu_names *names,
+                                    const dnagpu_text_out_options *opt, dnagpu_text_image **out);
+int      dnagpu_names_geometry(uint64_t *chunk_bytes, uint64_t *tile_bytes, uint64_t *group_tiles);
 /* Same over an arbitrary array of n keys of k bases already in device memory.  dev_keys is used as
  * scratch and its contents are unspecified afterwards. */
 int dnagpu_count_keys(dnagpu_ctx *ctx, uint64_t *dev_keys, uint64_t n, int k, dnagpu_hist **out);
