@@ -200,6 +200,45 @@ class TrimResult:
     seg_len: object = None
 
 
+ADAPTERS_DISCARD_UNTRIMMED = 1        # dnagpu_dna_adapters: the segments without a hit do not pass
+ADAPTERS_DISCARD_TRIMMED = 2          # those with one do not
+NO_ADAPTER = 2 ** 64 - 1              # out_adapter of a segment without a hit
+
+
+class _AdaptersOptionsC(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("err_num", "err_den", "min_overlap", "flags")] + \
+               [("min_bases", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+_ADAPTERS_REPORT_FIELDS = ("segments", "passed", "trimmed", "bases_in", "bases_kept", "bases_cut", "failed_short", "failed_discarded")
+
+
+class _AdaptersReportC(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in _ADAPTERS_REPORT_FIELDS] + [("per_adapter", C.c_uint64 * 32)]
+
+
+@dataclasses.dataclass
+class AdaptersResult:
+    """what Context.dna_adapters returns: the dnagpu_adapters_report's counters and per_adapter (32 counts); out_len /
+    out_adapter / out_mismatch: uint64 per input segment; pass_seq / pass_first / pass_len: the passing segments in input
+    order, at most cap of them"""
+    segments: int = 0
+    passed: int = 0
+    trimmed: int = 0
+    bases_in: int = 0
+    bases_kept: int = 0
+    bases_cut: int = 0
+    failed_short: int = 0
+    failed_discarded: int = 0
+    per_adapter: object = None
+    out_len: object = None
+    out_adapter: object = None
+    out_mismatch: object = None
+    pass_seq: object = None
+    pass_first: object = None
+    pass_len: object = None
+
+
 class _TextOutOptionsC(C.Structure):
     _fields_ = [("format", C.c_int), ("flags", C.c_uint), ("line_width", C.c_uint32), ("prefix_len", C.c_uint32),
                 ("name_prefix", C.c_char_p), ("name_base", C.c_uint64), ("numbers", C.c_void_p), ("numbers_on_device", C.c_int),
@@ -369,6 +408,9 @@ def lib():
     L.dnagpu_quals_trim.argtypes = [vp, vp, vp, C.POINTER(_QualsTrimOptionsC), vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_int,
                                     C.POINTER(_QualsTrimReportC)]
     L.dnagpu_quals_geometry.argtypes = [u64p, u64p, u64p]
+    L.dnagpu_dna_adapters.argtypes = [vp, vp, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(_AdaptersOptionsC), vp, vp, vp, C.c_uint64,
+                                      C.c_int, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.POINTER(_AdaptersReportC)]
+    L.dnagpu_adapters_geometry.argtypes = [u64p, u64p, u64p]
     L.dnagpu_names_upload.argtypes = [vp, vp, vp, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(_NamesReportC)]
     L.dnagpu_names_sequences.argtypes = [vp]
     L.dnagpu_names_sequences.restype = C.c_uint64
@@ -532,6 +574,13 @@ def quals_geometry():
     """(group_bases, wave_bases, tile_bases): the length limits of dnagpu_quals_trim's paths (needs no device)"""
     g, w, t = C.c_uint64(), C.c_uint64(), C.c_uint64()
     _chk(lib().dnagpu_quals_geometry(C.byref(g), C.byref(w), C.byref(t)))
+    return g.value, w.value, t.value
+
+
+def adapters_geometry():
+    """(group_bases, wave_bases, tile_bases): the segment lengths at which dnagpu_dna_adapters changes path (needs no device)"""
+    g, w, t = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _chk(lib().dnagpu_adapters_geometry(C.byref(g), C.byref(w), C.byref(t)))
     return g.value, w.value, t.value
 
 
@@ -1730,6 +1779,57 @@ class Context:
         rep = _QualsTrimReportC()
         _chk(lib().dnagpu_quals_trim(self.h, table.h, quals.h, C.byref(o), *dev_per, *dev_seg, cap, 1, C.byref(rep)))
         return TrimResult(**{f: int(getattr(rep, f)) for f in _TRIM_REPORT_FIELDS})
+
+    @staticmethod
+    def _adapters_args(adapters, err, min_overlap, min_bases, flags):
+        texts = [a.encode() if isinstance(a, str) else bytes(a) for a in adapters]
+        arr = (C.c_char_p * max(len(texts), 1))(*texts)
+        return arr, len(texts), _AdaptersOptionsC(err[0], err[1], min_overlap, flags, min_bases, 0)
+
+    @staticmethod
+    def _adapters_result(rep):
+        r = AdaptersResult(**{f: int(getattr(rep, f)) for f in _ADAPTERS_REPORT_FIELDS})
+        r.per_adapter = [int(x) for x in rep.per_adapter]
+        return r
+
+    def dna_adapters(self, dna, adapters, seg_first=None, seg_len=None, seg_seq=None, n_segs=None, err=(0, 1), min_overlap=1,
+                     min_bases=0, flags=0, cap=None, want=True):
+        """the 3' adapter cut of the segments (seg_first[i], seg_len[i]) of dna's stream -- both None: of every sequence of
+        the table -- under the adapters (texts of the qkmer alphabet), the error rate err = (num, den) and min_overlap ->
+        AdaptersResult (dnagpu_dna_adapters).  seg_seq: ids carried to pass_seq (None: i); cap: at most so many passing
+        segments are written (None: all); want=False: the report only"""
+        f = None if seg_first is None else np.ascontiguousarray(seg_first, dtype=np.uint64)
+        ln = None if seg_len is None else np.ascontiguousarray(seg_len, dtype=np.uint64)
+        sq = None if seg_seq is None else np.ascontiguousarray(seg_seq, dtype=np.uint64)
+        n = int(n_segs) if n_segs is not None else (f.size if f is not None else ln.size if ln is not None else dna.n_sequences)
+        for a in (f, ln, sq):
+            if a is not None and a.size != n:
+                raise ValueError("seg_first, seg_len and seg_seq must hold one entry per segment")
+        cap = n if cap is None else int(cap)
+        arr, n_ad, opt = self._adapters_args(adapters, err, min_overlap, min_bases, flags)
+        rep = _AdaptersReportC()
+        per = [np.empty(max(n, 1), dtype=np.uint64) for _ in range(3)] if want else [None] * 3
+        seg = [np.empty(max(cap, 1), dtype=np.uint64) for _ in range(3)] if want else [None] * 3
+        ptr = lambda a: None if a is None else (a.ctypes.data if a.size else self._one.ctypes.data)
+        _chk(lib().dnagpu_dna_adapters(self.h, dna.h, arr, n_ad, C.byref(opt), ptr(sq), ptr(f), ptr(ln), n, 0, *[ptr(a) for a in per],
+                                       *[ptr(a) for a in seg], cap if want else 0, 0, C.byref(rep)))
+        r = self._adapters_result(rep)
+        if want:
+            r.out_len, r.out_adapter, r.out_mismatch = (a[:n] for a in per)
+            m = min(r.passed, cap)
+            r.pass_seq, r.pass_first, r.pass_len = (a[:m] for a in seg)
+        return r
+
+    def dna_adapters_device(self, dna, adapters, n_segs, dev_in=(None,) * 3, in_on_device=1, dev_per=(None,) * 3, dev_pass=(None,) * 3,
+                            cap=0, out_on_device=1, err=(0, 1), min_overlap=1, min_bases=0, flags=0):
+        """the same over raw pointers: dev_in = (seg_seq, seg_first, seg_len), dev_per = (out_len, out_adapter, out_mismatch),
+        dev_pass = (pass_seq, pass_first, pass_len), each a pointer or None, in device memory where the flag beside it says so
+        -> AdaptersResult with the counters only"""
+        arr, n_ad, opt = self._adapters_args(adapters, err, min_overlap, min_bases, flags)
+        rep = _AdaptersReportC()
+        _chk(lib().dnagpu_dna_adapters(self.h, dna.h, arr, n_ad, C.byref(opt), *dev_in, n_segs, in_on_device, *dev_per, *dev_pass, cap,
+                                       out_on_device, C.byref(rep)))
+        return self._adapters_result(rep)
 
     def unpack(self, dna, first=0, count=None):
         if count is None:

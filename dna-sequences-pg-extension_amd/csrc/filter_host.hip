@@ -9,7 +9,7 @@ using namespace dnagpu;
 // ------------------------------------------------------------------------------------------------
 // filters: reference operator semantics -> FilterDev
 // IUPAC sets as 4-bit masks over codes (bit0 = A, bit1 = T, bit2 = C, bit3 = G), dna.c:1064-1081.
-static int iupac_set(char c)
+int dnagpu::iupac_set(char c)
 {
     switch (c) {
     case 'A': return 0x1;

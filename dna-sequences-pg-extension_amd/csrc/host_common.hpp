@@ -1,5 +1,5 @@
 // host_common.hpp -- what the host files of the C-ABI (dnagpu_api.hip, count_host.hip, sk_host.hip, multi_host.hip, query_host.hip,
-// filter_host.hip, index_host.hip, join_host.hip, hits_host.hip, take_host.hip, profile_host.hip, seqeq_host.hip, text_host.hip, reads_host.hip, export_host.hip, quals_host.hip, names_host.hip, host_steps.hip, table_steps.hip) share
+// filter_host.hip, index_host.hip, join_host.hip, hits_host.hip, take_host.hip, profile_host.hip, seqeq_host.hip, text_host.hip, reads_host.hip, export_host.hip, quals_host.hip, names_host.hip, adapters_host.hip, host_steps.hip, table_steps.hip) share
 // (internal, like kernels.hpp): the error macros, the context / dna / histogram objects, the buffer pool, and the few
 // functions one of the files calls in another.  Declarations only, plus the templates and macros that must be visible;
 // the definitions are in dnagpu_api.hip unless a section says otherwise.
@@ -416,6 +416,9 @@ int text_input_error(dnagpu_ctx *ctx, PoolScope &ps, const TextErrorIn &in, u64 
 // *op_error: the operator's own ERROR, which the reference raises only when a row reaches the operator; *none: no row can
 // match.
 int build_filter_bits(const dnagpu_filter *f, int k, FilterBits *out, bool *none, int *op_error);
+// a letter of the qkmer alphabet as a 4-bit mask over the codes (bit0 = A, bit1 = T, bit2 = C, bit3 = G; 'U': 0), else -1:
+// the one routine that `@>` and the adapters of dnagpu_dna_adapters are validated by
+int iupac_set(char c);
 
 // ---------------------------------------------------------------- count_host.hip
 struct TreeResult {

@@ -481,6 +481,30 @@ hipError_t launch_quals_verdict(const u64 *starts, u64 n_seqs, const QualsTrimOp
 hipError_t launch_quals_segments(const u32 *flags, const u32 *rank, const u64 *first, const u64 *len, u64 n_seqs, u64 cap, u64 *seg_seq,
                                  u64 *seg_first, u64 *seg_len, hipStream_t s);
 
+// ---- the 3' adapter cut of the segments of a stream (adapters_kernels.hip; the window arithmetic and the
+// hit key are adapters_math.hpp's).  The segments: (first[i], len[i]), or with first == null sequence i of starts.
+struct AdapterDesc;
+struct AdapterSegs {
+    const u64 *first, *len, *starts;
+    u64 n;
+};
+// the words of res: launch_take_segments' two (the second: a segment leaves the stream), the report's sums, and the segments
+// cut by each adapter.  The launches below do nothing once res[ADAPTERS_R_BAD] is set.
+enum {
+    ADAPTERS_R_SUM, ADAPTERS_R_BAD, ADAPTERS_R_PASSED, ADAPTERS_R_TRIMMED, ADAPTERS_R_BASES_IN, ADAPTERS_R_BASES_KEPT, ADAPTERS_R_SHORT,
+    ADAPTERS_R_DISCARDED, ADAPTERS_R_ADAPTER, ADAPTERS_R_WORDS = ADAPTERS_R_ADAPTER + 32
+};
+// keys[i] = the hit key of segment i's cut, or ADAPTERS_NONE.  lists: 2 n words, counts2: 2 words (scratch: the longer segments
+// by class).  Three launches: groups of lanes, waves, workgroups.
+hipError_t launch_adapters_find(const u64 *words, const AdapterSegs &g, const AdapterDesc *ads, u32 n_ads, const unsigned long long *bad,
+                                u64 *keys, u32 *lists, u32 *counts2, hipStream_t s);
+// out_len / out_adapter / out_mismatch (any may be null) and pass_flags[i] = segment i passes; res += the sums (zeroed by the caller)
+hipError_t launch_adapters_verdict(const AdapterSegs &g, const u64 *keys, u64 min_bases, u32 flags, u64 *out_len, u64 *out_adapter,
+                                   u64 *out_mismatch, u32 *pass_flags, unsigned long long *res, hipStream_t s);
+// rank: the scanned flags; the passing segments in input order, at most cap of them, seg_seq (null: i) carried through
+hipError_t launch_adapters_pass(const AdapterSegs &g, const u64 *seg_seq, const u64 *keys, const u32 *pass_flags, const u32 *rank, u64 cap,
+                                const unsigned long long *bad, u64 *pass_seq, u64 *pass_first, u64 *pass_len, hipStream_t s);
+
 // ---- equal sequences (seqeq_kernels.hip; classes, items, realigned word and fingerprint are
 // seqeq_math.hpp's).  A table, or a window of one: starts = seq_starts + seq_first, n + 1 entries.
 struct SeqTable {

@@ -216,6 +216,10 @@ def lib():
         L.trim_reads_begin.argtypes = [C.c_int, C.c_uint, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.trim_reads_next.restype = C.c_bool
         L.trim_reads_next.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(vp)]
+        L.trim_reads_add_adapter.restype = C.c_bool
+        L.trim_reads_add_adapter.argtypes = [vp, C.c_char_p]
+        L.trim_reads_adapter_options.restype = C.c_bool
+        L.trim_reads_adapter_options.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint]
         L.copy_reads_to_begin.restype = vp
         L.copy_reads_to_begin.argtypes = [C.c_bool]
         for f in (L.copy_reads_to_add, L.copy_reads_to_finish, L.copy_reads_to_next, L.copy_reads_to_failed):
@@ -866,16 +870,29 @@ def copy_reads(pieces, format=3, ambiguous=0, fold_case=False, min_bases=0):
         lib().copy_dna_end(c)
 
 
-def trim_reads(pieces, ambiguous=0, fold_case=False, cut_front=0, cut_tail=0, min_bases=0, min_mean_q=0, low_q=0, low_frac=(0, 0)):
+def _set_adapters(c, adapters, adapter_opt):
+    """trim_reads_add_adapter for every text of adapters and trim_reads_adapter_options(*adapter_opt) on the handle c;
+    adapter_opt = (err_num, err_den, min_overlap, flags) or None: the handle's defaults"""
+    for a in adapters or ():
+        if not lib().trim_reads_add_adapter(c, a.encode() if isinstance(a, str) else bytes(a)):
+            raise _err()
+    if adapter_opt is not None and not lib().trim_reads_adapter_options(c, *[int(x) for x in adapter_opt]):
+        raise _err()
+
+
+def trim_reads(pieces, ambiguous=0, fold_case=False, cut_front=0, cut_tail=0, min_bases=0, min_mean_q=0, low_q=0, low_frac=(0, 0),
+               adapters=None, adapter_opt=None):
     """FASTQ with its qualities, quality-trimmed and filtered on the device: pieces = the file's bytes in order, in pieces of
     any size -> ([dna], [record], [offset], [quality bytes]) of the passing reads in file order; offset = the index of the
-    read's first kept base in its source record's sequence.  With all thresholds 0 it is the plain load with qualities.  An
+    read's first kept base in its source record's sequence.  With all thresholds 0 it is the plain load with qualities.
+    adapters: 3' adapters (qkmer texts) cut behind the quality trim, adapter_opt = (err_num, err_den, min_overlap, flags).  An
     input ERROR raises GlueError with the library's message and .record = the source record it belongs to (-1: none)"""
     c = lib().trim_reads_begin(int(ambiguous), 2 if fold_case else 0, int(cut_front), int(cut_tail), int(min_bases), int(min_mean_q),
                                int(low_q), int(low_frac[0]), int(low_frac[1]))
     if not c:
         raise _err()
     try:
+        _set_adapters(c, adapters, adapter_opt)
         rows, records, offsets, quals = [], [], [], []
         p, rec, off, q = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_void_p()
 
@@ -972,7 +989,7 @@ def copy_reads_named(pieces, format=3, ambiguous=0, fold_case=False, min_bases=0
 
 
 def trim_reads_named(pieces, first_word=False, ambiguous=0, fold_case=False, cut_front=0, cut_tail=0, min_bases=0, min_mean_q=0,
-                     low_q=0, low_frac=(0, 0)):
+                     low_q=0, low_frac=(0, 0), adapters=None, adapter_opt=None):
     """trim_reads where every passing read carries its own name (copy_reads_keep_names) ->
     ([dna], [record], [offset], [quality bytes], [name bytes])"""
     c = lib().trim_reads_begin(int(ambiguous), 2 if fold_case else 0, int(cut_front), int(cut_tail), int(min_bases), int(min_mean_q),
@@ -982,6 +999,7 @@ def trim_reads_named(pieces, first_word=False, ambiguous=0, fold_case=False, cut
     try:
         if not lib().copy_reads_keep_names(c, bool(first_word)):
             raise _err()
+        _set_adapters(c, adapters, adapter_opt)
         rows, records, offsets, quals, names = [], [], [], [], []
         p, rec, off, q = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_void_p()
 

@@ -372,6 +372,18 @@ bool copy_reads_keep_names(CopyDna *c, bool first_word);
 const char *copy_reads_name(const CopyDna *c, size_t *len);
 bool copy_reads_to_add_named(CopyDnaTo *c, const Dna *row, const char *name, size_t name_len, const char *quality, size_t quality_len);
 bool copy_dna_to_add_named(CopyDnaTo *c, const Dna *row, const char *name, size_t name_len);
+/* ---- 3' adapters of a trim_reads handle: cut on the device behind the quality trim ----
+ * trim_reads_add_adapter: one more adapter (1 .. 32 letters of the qkmer alphabet, at most 32 adapters) of a trim_reads
+ *   handle.  Every chunk then goes, behind the quality trim, through dnagpu_dna_adapters: the trim's passing lists stay in
+ *   device memory and are its input, a read is cut at its first hit, and min_bases is applied again to the final length; the
+ *   gathers and the names take are given that call's passing lists.  trim_reads_next's offset is unchanged: a 3' cut moves no
+ *   start.  With no adapter added the handle behaves exactly as without this call.
+ * trim_reads_adapter_options: the error rate err_num / err_den (a hit has mismatches * err_den <= err_num * overlap), min_overlap
+ *   (1 .. 32) and flags (DNAGPU_ADAPTERS_DISCARD_*; not both).  Without this call: no mismatch, min_overlap 3, no flag.
+ * Both after trim_reads_begin and before the first feed: called later, on another handle, or with a bad adapter or option, an
+ *   ERROR (false). */
+bool trim_reads_add_adapter(CopyDna *c, const char *adapter);
+bool trim_reads_adapter_options(CopyDna *c, uint32_t err_num, uint32_t err_den, uint32_t min_overlap, unsigned flags);
 
 /* ---- CREATE INDEX ... ON kmer_data_t USING spgist (kmer_sequence spgist_kmer_ops) and the index scans of `=`, `^@` and `@>`
  * over the stored column (dna--1.0.sql:304-314; test.sql:156-270) ----

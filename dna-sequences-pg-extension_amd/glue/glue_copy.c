@@ -26,6 +26,10 @@ struct CopyDna {
     bool trim;
     dnagpu_quals_trim_options trim_opt;
     char **qual;                                 /* per row of rows[]: malloc'd, NUL-terminated (NULL once handed out) */
+    /* trim_reads_add_adapter: the passing reads of the trim are cut at their 3' adapter (none added: no such step) */
+    Qkmer adapter[32];
+    uint32_t n_adapters;
+    dnagpu_adapters_options ad_opt;
     /* copy_reads_keep_names: every row has the name of its source record */
     bool fed, keep_names, first_word;
     char **name;                                 /* per row of rows[]: malloc'd, NUL-terminated (NULL once served) */
@@ -82,7 +86,53 @@ CopyDna *trim_reads_begin(int ambiguous, unsigned flags, uint32_t cut_front, uin
     c->trim = true;
     const dnagpu_quals_trim_options o = {cut_front, cut_tail, min_mean_q, low_q, low_num, low_den, min_bases, 0};
     c->trim_opt = o;
+    const dnagpu_adapters_options a = {0, 1, 3, 0, min_bases, 0};
+    c->ad_opt = a;
     return c;
+}
+
+/* the two calls that make a trim_reads handle cut adapters: only between the begin and the first feed */
+static bool adapters_may_change(const CopyDna *c, const char *who)
+{
+    if (!c->trim) {
+        ereport_error("%s: only a trim_reads handle cuts adapters", who);
+        return false;
+    }
+    if (c->fed) {
+        ereport_error("%s: called after the first bytes were fed", who);
+        return false;
+    }
+    return true;
+}
+
+bool trim_reads_add_adapter(CopyDna *c, const char *adapter)
+{
+    if (!adapters_may_change(c, "trim_reads_add_adapter"))
+        return false;
+    if (c->n_adapters == 32) {
+        ereport_error("trim_reads_add_adapter: a handle takes at most 32 adapters");
+        return false;
+    }
+    if (!qkmer_in(adapter, &c->adapter[c->n_adapters]))                   /* (the letters of a qkmer, 1 .. 32 of them) */
+        return false;
+    c->n_adapters++;
+    return true;
+}
+
+bool trim_reads_adapter_options(CopyDna *c, uint32_t err_num, uint32_t err_den, uint32_t min_overlap, unsigned flags)
+{
+    if (!adapters_may_change(c, "trim_reads_adapter_options"))
+        return false;
+    const unsigned both = DNAGPU_ADAPTERS_DISCARD_UNTRIMMED | DNAGPU_ADAPTERS_DISCARD_TRIMMED;
+    if (err_den < 1 || err_num > err_den || min_overlap < 1 || min_overlap > 32 || (flags & ~both) || (flags & both) == both) {
+        ereport_error("trim_reads_adapter_options: the error rate must be at most 1, min_overlap 1 .. 32, and at most one discard flag set");
+        return false;
+    }
+    c->ad_opt.err_num = err_num;
+    c->ad_opt.err_den = err_den;
+    c->ad_opt.min_overlap = min_overlap;
+    c->ad_opt.flags = flags;
+    return true;
 }
 
 /* room for `need` rows: rows[] and the per-row arrays of the object's kind, which grow together */
@@ -178,6 +228,7 @@ static bool trim_load(CopyDna *c, const dnagpu_dna *d, uint64_t text_bytes, cons
     dnagpu_quals_report qrep;
     dnagpu_quals_trim_report trep;
     uint64_t *seg = NULL, *starts = NULL;
+    void *dev = NULL;
     char *text = NULL;
     bool ok = false;
     *appended = 0;
@@ -195,10 +246,27 @@ static bool trim_load(CopyDna *c, const dnagpu_dna *d, uint64_t text_bytes, cons
         goto done;
     }
     uint64_t *seg_seq = seg, *seg_first = seg + n_seqs, *seg_len = seg + 2 * n_seqs;
-    if (!gpu_ok(dnagpu_quals_trim(g_ctx, d, q, &c->trim_opt, NULL, NULL, NULL, NULL, seg_seq, seg_first, seg_len, n_seqs, 0, &trep)) ||
-        !gpu_ok(dnagpu_dna_sequence_starts(g_ctx, d, 0, n_seqs + 1, starts, 0)))
+    uint64_t m = 0;
+    if (c->n_adapters) {                                                  /* the trim's lists stay on the device: the adapters' input */
+        const char *texts[32];
+        dnagpu_adapters_report arep;
+        for (uint32_t a = 0; a < c->n_adapters; a++)
+            texts[a] = c->adapter[a].sequence;
+        if (!gpu_ok(dnagpu_buffer_alloc(g_ctx, 3 * 8 * n_seqs, &dev)))
+            goto done;
+        uint64_t *dv = (uint64_t *)dev;
+        if (!gpu_ok(dnagpu_quals_trim(g_ctx, d, q, &c->trim_opt, NULL, NULL, NULL, NULL, dv, dv + n_seqs, dv + 2 * n_seqs, n_seqs, 1, &trep)) ||
+            !gpu_ok(dnagpu_dna_adapters(g_ctx, d, texts, c->n_adapters, &c->ad_opt, dv, dv + n_seqs, dv + 2 * n_seqs, trep.passed, 1, NULL,
+                                        NULL, NULL, seg_seq, seg_first, seg_len, n_seqs, 0, &arep)))
+            goto done;
+        m = arep.passed;
+    } else {
+        if (!gpu_ok(dnagpu_quals_trim(g_ctx, d, q, &c->trim_opt, NULL, NULL, NULL, NULL, seg_seq, seg_first, seg_len, n_seqs, 0, &trep)))
+            goto done;
+        m = trep.passed;
+    }
+    if (!gpu_ok(dnagpu_dna_sequence_starts(g_ctx, d, 0, n_seqs + 1, starts, 0)))
         goto done;
-    const uint64_t m = trep.passed;
     if (m == 0) {
         ok = true;
         goto done;
@@ -254,6 +322,8 @@ done:
     free(text);
     free(seg);
     free(starts);
+    if (dev)
+        dnagpu_buffer_free(g_ctx, dev);
     if (td)
         dnagpu_dna_free(g_ctx, td);
     if (tq)

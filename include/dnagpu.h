@@ -604,6 +604,63 @@ int      dnagpu_text_image_read_quals(dnagpu_ctx *ctx, const dnagpu_text_image *
  * path past each of these sizes, and a caller's tests can only place their cases on the edges if the library names them. */
 int      dnagpu_quals_copy_geometry(uint64_t *chunk_bytes, uint64_t *tile_bytes, uint64_t *lds_segments);
 
+/* ---- Adapter trimming: dnagpu_dna_adapters.  Segments in, segments out.
+ *
+ * The 3' adapter cut of every segment of a packed stream, with mismatches and IUPAC letters, on the device.
+ *   Input: src, and n_segs segments of its stream: seg_first / seg_len are stream coordinates (uint64; host memory, or device
+ *   memory when on_device != 0) -- exactly what dnagpu_quals_trim writes as seg_first / seg_len or as out_first / out_len.
+ *   Both NULL: segment i is sequence i of the table's set (src must then have a set, and n_segs must not exceed its
+ *   sequences).  seg_seq (optional, as the lists) is carried through unchanged to pass_seq; NULL: the id is i.
+ *   Adapters: n_adapters (1 .. 32) NUL-terminated texts of 1 .. 32 letters of the qkmer alphabet, validated by the routine
+ *   `@>` is validated by; 'U' matches no base, as it does there.  S_a[j] = the set of letter j of adapter a, L_a its length.
+ *   The match rule -- Hamming distance only, no insertions or deletions.  For a segment with the bases b[0 .. n), a position
+ *   p in 0 .. n-1 and an adapter a:  o = min(L_a, n - p),  m = #{ j < o : b[p + j] not in S_a[j] };  (p, a) is a hit iff
+ *   o >= min(min_overlap, L_a) and m * err_den <= err_num * o (64-bit integer comparisons).  The segment's cut is the hit with
+ *   the least (p, m, a) in lexicographic order: the lowest position wins (the "first position" rule of fastp and
+ *   Trimmomatic), at one position the fewest mismatches, then the lowest adapter index.  With no hit nothing is cut.  No base
+ *   outside [seg_first, seg_first + seg_len) is ever compared -- a partial overlap at the end of a read does not look at the
+ *   head of the next one -- and words[n_words] is never read.
+ *   Outputs, all uint64, host memory or device memory when out_on_device != 0; any may be NULL.  Per input segment i:
+ *   out_len[i] = p of the cut, or n; out_adapter[i] = a, or ~0; out_mismatch[i] = m, or 0.  A segment passes iff its kept
+ *   length is > 0 and >= min_bases and no discard flag excludes it (DISCARD_UNTRIMMED: the segments without a hit;
+ *   DISCARD_TRIMMED: those with one).  The passing segments come in input order as pass_seq / pass_first / pass_len, at most
+ *   pass_cap of them (the report carries the full count): lists that go straight into dnagpu_dna_gather, dnagpu_quals_gather
+ *   and dnagpu_names_take.  The report (cleared on entry; its read is the call's only read-back on the success path):
+ *   segments, passed, trimmed (segments with a hit), bases_in = bases_kept + bases_cut over all segments, failing ones
+ *   included, failed_short and failed_discarded (in that order of precedence), and per_adapter[a] = the segments cut by
+ *   adapter a.
+ *   Checks, in order: a NULL ctx, src, opt or adapters (or a NULL text) is DNAGPU_ERR_BAD_ARG; an adapter count outside
+ *   1 .. 32, a length outside 1 .. 32, err_den == 0, err_num > err_den, min_overlap outside 1 .. 32, unknown flags, both
+ *   discard flags, or a non-zero reserved is DNAGPU_ERR_BAD_ARG; a letter outside the alphabet is DNAGPU_ERR_QKMER_INVALID;
+ *   only one of seg_first / seg_len is DNAGPU_ERR_BAD_ARG; both NULL on a non-empty stream without a set, or with n_segs above
+ *   the set's sequences, is DNAGPU_ERR_BAD_ARG; n_segs > 2^32 - 1 is DNAGPU_ERR_TOO_LARGE.  These need no device.  Then, found
+ *   on the device over all entries before any output is written, a segment that leaves the stream (seg_first > length or
+ *   seg_len > length - seg_first) is DNAGPU_ERR_BAD_ARG.  On every error the outputs are untouched.  n_segs == 0 is DNAGPU_OK
+ *   with an all-zero report.  The call waits for its work.
+ *   dnagpu_adapters_geometry names the paths by segment length (needs no device): at most group_bases bases are handled by a
+ *   group of 16 lanes of one wave, at most wave_bases by a wave, more by a workgroup in tiles of tile_bases positions, from
+ *   the front until a tile holds a hit. */
+#define DNAGPU_ADAPTERS_DISCARD_UNTRIMMED 1u
+#define DNAGPU_ADAPTERS_DISCARD_TRIMMED   2u
+typedef struct dnagpu_adapters_options {
+    uint32_t err_num;      /* a hit has m * err_den <= err_num * o */
+    uint32_t err_den;      /* >= 1, err_num <= err_den */
+    uint32_t min_overlap;  /* 1 .. 32; for adapter a: min(min_overlap, L_a) */
+    uint32_t flags;        /* DNAGPU_ADAPTERS_DISCARD_*; not both */
+    uint64_t min_bases;    /* passes iff the kept length >= min_bases (and > 0) */
+    uint64_t reserved;     /* 0 */
+} dnagpu_adapters_options;
+typedef struct dnagpu_adapters_report {
+    uint64_t segments, passed, trimmed, bases_in, bases_kept, bases_cut, failed_short, failed_discarded;
+    uint64_t per_adapter[32];
+} dnagpu_adapters_report;
+int      dnagpu_dna_adapters(dnagpu_ctx *ctx, const dnagpu_dna *src, const char *const *adapters, uint32_t n_adapters,
+                             const dnagpu_adapters_options *opt, const uint64_t *seg_seq, const uint64_t *seg_first,
+                             const uint64_t *seg_len, uint64_t n_segs, int on_device, uint64_t *out_len, uint64_t *out_adapter,
+                             uint64_t *out_mismatch, uint64_t *pass_seq, uint64_t *pass_first, uint64_t *pass_len,
+                             uint64_t pass_cap, int out_on_device, dnagpu_adapters_report *report);
+int      dnagpu_adapters_geometry(uint64_t *group_bases, uint64_t *wave_bases, uint64_t *tile_bases);
+
 /* ---- The names column of a table of reads: dnagpu_names.
  *
  * A column is an owned object (dnagpu_names_free) of variable-length byte strings, one per sequence of a table: n + 1
